@@ -3,6 +3,7 @@
 bench.py -- rays/s of the sequential ray-trace hot path, forward + backward, on N MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg3a|cfg2|cfg5] [--mode strict|fast]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -13,7 +14,18 @@ kernel, per-ray outputs materialised as the reference API returns them, spot mom
 compute_rms2d (closed form on the moments; one tiny all-reduce when N > 1) -> backward (walk-back
 adjoint kernel) -> gradients of the loss w.r.t. the trace parameters (c, t, mu, z, cy) [-> one
 tiny all-reduce when N > 1].  The pupil coordinates are resident in HBM before the timed region.
-The K-step region is timed `--repeats` times (default 3) after ONE warm-up; `value` is the median.
+After W warm-up steps, a region of exactly K steps is timed `--repeats` times (default 1; 3 with --full);
+`value` and `ms_per_step` come from the median region.
+
+A plain run measures the headline only: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.
+--full adds everything else this script reports: per-kernel times and rooflines, the other arithmetic mode,
+the secondary workloads ("also"), the rays x rows sweep, the HIP-graph child, the Adam loop and lens
+minibatch children, the CPU baseline and the gradient checks (each still switchable off by its --no-* flag).
+
+--dump-outputs DIR writes what the caller of the timed path received from the LAST timed step of rank 0 as
+DIR/<name>.npy: rms, grad_<leaf> for every differentiable trace_skew argument, and the per-ray outputs x, y, cx,
+cy, ok, back of trace_skew (float32; a fixed sample of 2^20 rays drawn with seed 0 when the fan is larger).
+The inputs depend only on the arguments, so two builds can be compared output for output.
 
 Workloads:
   cfg3a (default, the headline): BASELINE configs[2] AS WRITTEN -- synthesized double Gauss, 11 rows (10 refracting
@@ -53,7 +65,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3, help="how often the K-step region is timed (value = median)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how often the K-step region is timed (value = median); default 1, 3 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--workload", default="cfg3a", choices=["cfg3a", "cfg3", "cfg3s", "cfg2", "cfg5"])
     ap.add_argument("--mode", default=os.environ.get("TORCHOPTICS_AMD_MODE", "strict"), choices=["strict", "fast"])
     ap.add_argument("--log2-pupil", type=int, default=None, help="override log2 of pupil points per GPU")
@@ -74,7 +91,12 @@ def parse():
     ap.add_argument("--cpu-log2-rays", type=int, default=20, help="log2 of the gradient-check sample (rays)")
     ap.add_argument("--cpu-full-log2-rays", type=int, default=24,
                     help="log2 of the rays of the timed CPU baseline (chunked at 2^22 rays)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
+    if not a.full:      # a plain run: the headline figure only
+        a.no_cpu_baseline = a.no_other_mode = a.no_also = a.no_sweep = a.no_graph_child = a.no_fp64_check = True
+    return a
 
 
 # ------------------------------------------------------------------------------------------ workloads
@@ -132,11 +154,13 @@ class Job:
         self.n_per_field_total = self.meta["P_total"] * self.meta["W"]
         self.rays_local = self.meta["F"] * self.meta["W"] * self.meta["P_local"]
         self.rays_total = self.rays_local * world
+        self.kept = None        # (x, y, cx, cy, ok, back) of the last step run with keep=True
 
-    def step(self):
+    def step(self, keep=False):
         import torchoptics_amd as ta
         from torchoptics_amd import dist as tl_dist
         a = self.args
+        self.kept = None        # freed before the step allocates: the allocation pattern of a step without keep
         for p in self.leaves:
             p.grad = None
         if self.penalty_rate is not None:
@@ -144,6 +168,8 @@ class Job:
             out = ta.trace_skew(a["x"], a["y"], a["z"], a["cx"], a["cy"], a["c"], a["t"], a["mu"], a["mask"], "sum", **self.asph)
             rms = ta.compute_rms2d(out[0], out[1], out[4], group=self.group, n_per_field=self.n_per_field_total)
             (rms + self.penalty_rate * ta.ray_tracing.penalty_sum(out[6], self.meta["S"])).backward()
+            if keep:
+                self.kept = tuple(out[:6])
             return rms.detach()
         x, y, cx, cy, ok, back = ta.trace_skew(a["x"], a["y"], a["z"], a["cx"], a["cy"], a["c"], a["t"], a["mu"],
                                                a["mask"], **self.asph)
@@ -151,6 +177,8 @@ class Job:
         rms.backward()
         if self.group is not None:
             tl_dist.all_reduce_grads(self.leaves, self.group)
+        if keep:
+            self.kept = (x, y, cx, cy, ok, back)
         return rms.detach()
 
 
@@ -168,9 +196,11 @@ def sync(group):
     torch.cuda.synchronize()
 
 
-def timed(job, mode, steps, warmup, repeats, graph, backend, device):
+def timed(job, mode, steps, warmup, repeats, graph, backend, device, kernel_timing=True):
     """W untimed warm-up steps, then `repeats` regions of exactly K steps, each between barrier+synchronize;
-    every region's time is the max over ranks.  Returns (list of seconds, kernel ms dict, rms)."""
+    every region's time is the max over ranks.  Returns (list of seconds, kernel ms dict, rms).
+    kernel_timing: event pairs around every trace kernel call of the eager regions (the kernel ms dict; empty
+    without).  The outputs of the last timed step stay in job.kept."""
     from torchoptics_amd import ops
     ops.set_default_mode(mode)
     group = job.group
@@ -187,7 +217,7 @@ def timed(job, mode, steps, warmup, repeats, graph, backend, device):
             p_.grad = None
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=cap):
-            r = job.step()
+            r = job.step(keep=True)          # static outputs: every replay rewrites them
         for _ in range(warmup):
             g.replay()
         for _ in range(repeats):
@@ -202,16 +232,18 @@ def timed(job, mode, steps, warmup, repeats, graph, backend, device):
             r = job.step()
         for _ in range(repeats):
             sync(group)
-            ops.enable_timing(True)
+            if kernel_timing:
+                ops.enable_timing(True)
             t0 = time.perf_counter()
-            for _ in range(steps):
-                r = job.step()
+            for i in range(steps):
+                r = job.step(keep=i == steps - 1)
             sync(group)
             times.append(time.perf_counter() - t0)
-            k = ops.timing_ms()
-            ops.enable_timing(False)
-            for key, v in k.items():
-                km.setdefault(key, []).append(v)
+            if kernel_timing:
+                k = ops.timing_ms()
+                ops.enable_timing(False)
+                for key, v in k.items():
+                    km.setdefault(key, []).append(v)
         km = {key: (statistics.median(v) if all(q is not None for q in v) else None) for key, v in km.items()}
     if group is not None:
         tmax = torch.tensor(times, dtype=torch.float64, device="cpu" if backend == "gloo" else device)
@@ -356,6 +388,32 @@ def summarize(job, times, steps):
                 repeats_ms_per_step=[t / steps * 1e3 for t in times])
 
 
+DUMP_MAX_RAYS = 1 << 20        # 6 per-ray arrays x 4 B x 2^20 = 24 MB at most
+
+
+def dump_outputs(job, rms, out_dir):
+    """--dump-outputs: the loss, the leaf gradients and the per-ray outputs of the last timed step (job.kept) as
+    out_dir/<name>.npy in float32.  Fans larger than DUMP_MAX_RAYS are sampled at the same sorted ray indices every
+    run (numpy default_rng(0), without replacement), so equal arguments give comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rms": rms.detach().float().reshape(1)}
+    for k in LEAF_NAMES:
+        if k in job.args and job.args[k].grad is not None:
+            arrays["grad_" + k] = job.args[k].grad.detach().float()
+    n = job.kept[0].numel()
+    idx = None
+    if n > DUMP_MAX_RAYS:
+        pick = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_RAYS, replace=False))
+        idx = torch.from_numpy(pick).to(job.kept[0].device)
+    for name, t in zip(("x", "y", "cx", "cy", "ok", "back"), job.kept):
+        flat = t.detach().reshape(-1)
+        assert flat.numel() == n, (name, tuple(t.shape))
+        arrays[name] = (flat if idx is None else flat.index_select(0, idx)).float()
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+    log(f"outputs of the last timed step written to {out_dir} ({len(arrays)} arrays)")
+
+
 # ------------------------------------------------------------------------------------------ main
 def main():
     a = parse()
@@ -389,9 +447,13 @@ def main():
     log(f"workload {a.workload}, mode {a.mode}, world {world}, graph {a.graph}")
     job = Job(a.workload, device, world, rank, group, a.log2_pupil)
     meta = job.meta
-    times, kern_ms, rms = timed(job, a.mode, a.steps, a.warmup, a.repeats, a.graph, a.backend, device)
+    times, kern_ms, rms = timed(job, a.mode, a.steps, a.warmup, a.repeats, a.graph, a.backend, device,
+                                kernel_timing=a.full)
     head = summarize(job, times, a.steps)
-    final_grads = grad_report(job, group, a.backend, device)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(job, rms, a.dump_outputs)
+    job.kept = None
+    final_grads = grad_report(job, group, a.backend, device) if a.full else None
     fp64_full = None
     if world == 1 and not a.graph and not a.no_fp64_check:
         try:
@@ -477,7 +539,7 @@ def main():
     if solo and group is None and not a.graph and not a.no_graph_child:
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--graph", "--steps", str(a.steps), "--warmup", str(a.warmup),
-               "--repeats", str(a.repeats), "--workload", a.workload, "--mode", a.mode, "--no-cpu-baseline",
+               "--repeats", str(a.repeats), "--workload", a.workload, "--mode", a.mode, "--full", "--no-cpu-baseline",
                "--no-other-mode"]
         if a.no_also:
             cmd += ["--no-also"]
@@ -554,6 +616,7 @@ def main():
             "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "repeats": a.repeats, "repeats_ms_per_step": head["repeats_ms_per_step"], "n_ranks_seen": n_seen,
+            "full": bool(a.full),
             "config": {"workload": workload_label(a.workload, meta, job),
                        "arith_mode": a.mode, "backward_algorithm": "walk-back from the forward outputs (checkpoint kernel "
                        "as on-device fallback for ill-conditioned fans)" if inv else "checkpoint",

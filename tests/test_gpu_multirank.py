@@ -13,8 +13,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-other-mode", "--no-also",
-          "--no-sweep", "--no-graph-child", "--no-fp64-check"]
+COMMON = ["--steps", "3", "--warmup", "1", "--repeats", "1", "--full", "--no-cpu-baseline", "--no-other-mode", "--no-also",
+          "--no-sweep", "--no-graph-child", "--no-fp64-check"]       # --full: final_grads
 
 
 def _run(cmd, timeout=420):

@@ -147,7 +147,12 @@ def test_padded_lens_batch_gradients_equal_reference(prec):
             continue
         want = g["gin_" + n + prec]
         got = np.zeros_like(want) if got is None else got.numpy()
+        scale = np.linalg.norm(g["gin_c64"])
         if same_cpu_math():
             assert np.array_equal(got, want), f"G11: d/d{n} differs (rel {rel_l2(got, want):.2e})"
-        else:
+        elif np.linalg.norm(g["gin_" + n + "64"]) > 1e-6 * scale:
             assert rel_l2(got, want) <= (1e-9 if prec else 1e-3), f"G11: d/d{n} rel {rel_l2(got, want):.2e}"
+        else:
+            # zero by symmetry (cx = 0, fields along y: rms is even in cx): on either CPU rounding noise, measured against
+            # the size of the lens gradient as in test_input_gradients_equal_reference
+            assert np.linalg.norm(got) <= 1e-6 * scale, f"G11: d/d{n} = {np.linalg.norm(got):.2e} is not ~0"
