@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from zoom20_rows import lens_args
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -23,31 +24,6 @@ def ta():
     from torchoptics_amd import _lib
     _lib.lib()
     return torchoptics_amd
-
-
-def lens_args(ta, n_rows, n_rays=(16, 16)):
-    """Kernel arguments for the first `n_rows` rows of zoom20 (n_rows <= 20) or zoom20 + dummies."""
-    from torchoptics_amd import prescriptions as P
-    lens, specs, leaves = P.zoom20("cpu", requires_grad=False)
-    tr = ta.RayTracer(mode="circular", n_rays=n_rays, rel_fields=(0., 0.6, 1.), wavelengths=("C", "d", "F"),
-                      default_device="cpu")
-    a = tr.assemble(specs, lens)
-    S = a["c"].shape[-1]
-    if n_rows <= S:
-        for k in ("c", "t", "mu", "mask"):
-            a[k] = a[k][..., :n_rows].contiguous()
-        if n_rows < S:                      # image plane right behind the last kept row
-            a["t"] = a["t"].clone()
-            a["t"][..., -1] = 0.5
-    else:
-        extra = n_rows - S
-        t_last = a["t"][..., -1:].clone()
-        a["c"] = torch.cat((a["c"], torch.zeros(1, 1, 1, 1, extra)), -1)
-        a["mu"] = torch.cat((a["mu"], torch.ones(1, 1, 1, a["mu"].shape[3], extra)), -1)
-        a["mask"] = torch.cat((a["mask"], torch.ones(1, 1, 1, 1, extra, dtype=torch.bool)), -1)
-        gaps = torch.full((1, 1, 1, 1, extra), 0.05)
-        a["t"] = torch.cat((a["t"][..., :-1], gaps, t_last - 0.05 * extra), -1)
-    return a
 
 
 @pytest.mark.parametrize("n_rows", [1, 2, 3, 4, 5, 8, 9, 12, 13, 16, 17, 20, 21, 24, 25, 28, 32])
