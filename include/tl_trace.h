@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define TL_ABI_VERSION 13
+#define TL_ABI_VERSION 14
 #define TL_MAX_SURFACES 32       /* rows per lens the backward kernels are built for */
 #define TL_NMOM 10               /* per-field sums, see tl_trace_fwd */
 #define TL_MAX_POLY 4            /* even aspheric terms a4,a6,a8,a10 */
@@ -132,7 +132,8 @@ size_t tl_workspace_bytes(const tl_problem *p);
  *               (ray_tracing_lite.py:641-657), NaN -> 0, i.e. sumQ * n_sequence of
  *               optics_simulator_lite.py:441-448.  All reduced in a fixed order (bitwise reproducible).
  *   stacks    : [3][S][F,W,P] float (nullable, p->aggregate only): the per-surface stacks
- *               z_RELU | theta_norm | theta_prime_norm that trace_skew(aggregate=True) returns.
+ *               z_RELU | theta_norm | theta_prime_norm that trace_skew(aggregate=True) returns
+ *               (their gradient: `g_stacks` of tl_trace_bwd_stacks / tl_trace_bwd_from_outputs_stacks).
  */
 int tl_trace_fwd(const tl_problem *p,
                  float *x, float *y, float *cx, float *cy, uint8_t *ok, uint8_t *back,
@@ -200,6 +201,37 @@ int tl_trace_bwd_from_outputs(const tl_problem *p,
                               float *g_kappa, float *g_poly,
                               float *g_x_in, float *g_y_in,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The two backward calls above with a gradient for the per-surface penalty stacks (ABI 14): after `g_stacks` the
+ * arguments are exactly theirs, and tl_trace_bwd / tl_trace_bwd_from_outputs are these calls with g_stacks = NULL.
+ *   g_stacks : [3][S][F,W,P] float (nullable; [3][S][B,F,W,P] for a lens batch), dense, in the layout of tl_trace_fwd's
+ *              `stacks` output: the upstream gradient of z_RELU | theta_norm | theta_prime_norm of every row and ray.
+ *              Needs p->aggregate (TL_EINVAL, before any HIP call, otherwise).  Per ray r and row k:
+ *                - ray ok after row k: theta and theta' are differentiated through cos^2 with the clamp conventions of
+ *                  the fused seed (entry 8 of g_moments), z_RELU passes the gradient where z > 0;
+ *                - ray not ok after row k (parked): theta = theta' = 1 carry no gradient, z_RELU = max(-t_k, 0) gives
+ *                  d/dt_k only.
+ *              It adds to entry 8 of g_moments: a loss may read both the fused sum and the stacks.  The routing is that of
+ *              the penalty term (tl_trace_bwd_from_outputs: the walk-back for 3..20 rows, P >= 256, aspheric hits stored;
+ *              the checkpoint kernel otherwise).  No host synchronisation: the calls can be recorded into a HIP graph.
+ */
+int tl_trace_bwd_stacks(const tl_problem *p, const float *g_stacks,
+                        const float *gx, const float *gy, const float *gcx, const float *gcy,
+                        const double *g_moments, const float *g_opd,
+                        float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy,
+                        float *g_kappa, float *g_poly, float *g_n_index,
+                        float *g_x_in, float *g_y_in,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int tl_trace_bwd_from_outputs_stacks(const tl_problem *p, const float *g_stacks,
+                                     const float *gx, const float *gy, const float *gcx, const float *gcy,
+                                     const double *g_moments,
+                                     const float *x_fwd, const float *y_fwd, const float *cx_fwd, const float *cy_fwd,
+                                     const uint8_t *ok_fwd, const double *moments_fwd,
+                                     float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy,
+                                     float *g_kappa, float *g_poly,
+                                     float *g_x_in, float *g_y_in,
+                                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Spot moments of arbitrary per-ray tensors (same TL_NMOM layout): the reduction inside

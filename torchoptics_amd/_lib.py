@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TORCHOPTICS_AMD_LIB: another build of the same library (an A/B variant written by build.build_library(tag=...))
 LIB_PATH = os.environ.get("TORCHOPTICS_AMD_LIB") or os.path.join(_HERE, "libtltrace.so")
 
-TL_ABI_VERSION = 13
+TL_ABI_VERSION = 14
 TL_NMOM = 10
 TL_MAX_SURFACES = 32
 TL_MAX_POLY = 4
@@ -49,6 +49,8 @@ _SIGNATURES = {
     "tl_trace_fwd": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 9 + [_VP, C.c_size_t, _VP]),
     "tl_trace_bwd": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 17 + [_VP, C.c_size_t, _VP]),
     "tl_trace_bwd_from_outputs": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 21 + [_VP, C.c_size_t, _VP]),
+    "tl_trace_bwd_stacks": (C.c_int, [C.POINTER(tl_problem), _VP] + [_VP] * 17 + [_VP, C.c_size_t, _VP]),
+    "tl_trace_bwd_from_outputs_stacks": (C.c_int, [C.POINTER(tl_problem), _VP] + [_VP] * 21 + [_VP, C.c_size_t, _VP]),
     "tl_spot_moments": (C.c_int, [C.c_int32] * 4 + [_VP] * 3 + [C.c_int64] * 3 + [_VP, _VP, C.c_size_t, _VP]),
     "tl_spot_rms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP, _VP, _VP]),
     "tl_unsup_loss": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP, C.c_double, C.c_float, _VP, _VP, _VP, _VP, _VP]),

@@ -682,8 +682,18 @@ int tl_trace_bwd(const tl_problem *p, const float *gx, const float *gy, const fl
                  float *g_cy, float *g_kappa, float *g_poly, float *g_n_index, float *g_x_in, float *g_y_in, void *workspace,
                  size_t workspace_bytes, void *stream)
 {
+    return tl_trace_bwd_stacks(p, nullptr, gx, gy, gcx, gcy, g_moments, g_opd, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly,
+                               g_n_index, g_x_in, g_y_in, workspace, workspace_bytes, stream);
+}
+
+int tl_trace_bwd_stacks(const tl_problem *p, const float *g_stacks, const float *gx, const float *gy, const float *gcx,
+                        const float *gcy, const double *g_moments, const float *g_opd, float *g_c, float *g_t, float *g_mu,
+                        float *g_z, float *g_cx, float *g_cy, float *g_kappa, float *g_poly, float *g_n_index, float *g_x_in,
+                        float *g_y_in, void *workspace, size_t workspace_bytes, void *stream)
+{
     int rc = check_problem(p);
     if (rc) return rc;
+    if (g_stacks && !p->aggregate) return fail(TL_EINVAL, "g_stacks needs tl_problem.aggregate (the stacks are its outputs)");
     if ((g_opd != nullptr) != (g_n_index != nullptr)) return fail(TL_EINVAL, "g_opd and g_n_index must be given together");
     if (g_opd && !p->n_index) return fail(TL_EINVAL, "the gradient of the optical path length needs tl_problem.n_index");
     if (!g_c || !g_t || !g_mu || !g_z || !g_cx || !g_cy) return fail(TL_EINVAL, "a parameter-gradient output is NULL");
@@ -710,8 +720,8 @@ int tl_trace_bwd(const tl_problem *p, const float *gx, const float *gy, const fl
     if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd");
     double *part = (double *)workspace;
     int herr = (p->mode == TL_MODE_FAST)
-                   ? tl_fast::api_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, part, pl.nbx, pl.R, st, g_opd)
-                   : tl_strict::api_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, part, pl.nbx, pl.R, st, g_opd);
+                   ? tl_fast::api_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, part, pl.nbx, pl.R, st, g_opd, g_stacks)
+                   : tl_strict::api_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, part, pl.nbx, pl.R, st, g_opd, g_stacks);
     if (herr) return hip_fail(herr, "trace_bwd_kernel launch");
     const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0) + (g_opd ? p->W * (p->S + 1) : 0);
     hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, ns, p->F, p->W, p->S, pl.nbx, g_c,
@@ -729,8 +739,21 @@ int tl_trace_bwd_from_outputs(const tl_problem *p, const float *gx, const float 
                               float *g_poly, float *g_x_in, float *g_y_in, void *workspace, size_t workspace_bytes,
                               void *stream)
 {
+    return tl_trace_bwd_from_outputs_stacks(p, nullptr, gx, gy, gcx, gcy, g_moments, x_fwd, y_fwd, cx_fwd, cy_fwd, ok_fwd,
+                                            moments_fwd, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly, g_x_in, g_y_in,
+                                            workspace, workspace_bytes, stream);
+}
+
+int tl_trace_bwd_from_outputs_stacks(const tl_problem *p, const float *g_stacks, const float *gx, const float *gy,
+                                     const float *gcx, const float *gcy, const double *g_moments, const float *x_fwd,
+                                     const float *y_fwd, const float *cx_fwd, const float *cy_fwd, const uint8_t *ok_fwd,
+                                     const double *moments_fwd, float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx,
+                                     float *g_cy, float *g_kappa, float *g_poly, float *g_x_in, float *g_y_in, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
     int rc = check_problem(p);
     if (rc) return rc;
+    if (g_stacks && !p->aggregate) return fail(TL_EINVAL, "g_stacks needs tl_problem.aggregate (the stacks are its outputs)");
     if (!g_c || !g_t || !g_mu || !g_z || !g_cx || !g_cy) return fail(TL_EINVAL, "a parameter-gradient output is NULL");
     // p->cond_flags (written by the forward) is the ok bytes with the conditioning flag: it is read instead of ok_fwd
     if (p->cond_flags) ok_fwd = p->cond_flags;
@@ -742,12 +765,12 @@ int tl_trace_bwd_from_outputs(const tl_problem *p, const float *gx, const float 
     // the penalty term is walked back by the unrolled kernels only (3..20 rows, aspheric rows with stored hits);
     // other lenses take the checkpoint kernel for every ray
     if (p->aggregate && !(tl_walk_unrolled(p->S, p->P) && hits_ok))
-        return tl_trace_bwd(p, gx, gy, gcx, gcy, g_moments, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly,
-                            nullptr, g_x_in, g_y_in, workspace, workspace_bytes, stream);
+        return tl_trace_bwd_stacks(p, g_stacks, gx, gy, gcx, gcy, g_moments, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa,
+                                   g_poly, nullptr, g_x_in, g_y_in, workspace, workspace_bytes, stream);
     if ((g_kappa || g_poly) && !p->surf_kind) return fail(TL_EINVAL, "g_kappa / g_poly need aspheric rows (surf_kind)");
     if (p->surf_kind && (!g_kappa || !g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
-    if (p->P == 0) return tl_trace_bwd(p, gx, gy, gcx, gcy, g_moments, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly,
-                                       nullptr, g_x_in, g_y_in, workspace, workspace_bytes, stream);
+    if (p->P == 0) return tl_trace_bwd_stacks(p, g_stacks, gx, gy, gcx, gcy, g_moments, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy,
+                                              g_kappa, g_poly, nullptr, g_x_in, g_y_in, workspace, workspace_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(p->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -770,9 +793,11 @@ int tl_trace_bwd_from_outputs(const tl_problem *p, const float *gx, const float 
     //  forward call of the same step, see reduce_moments_kernel, so a poisoned replay does not stick.)
     int herr = (p->mode == TL_MODE_FAST)
                    ? tl_fast::api_bwd_inv(*p, gx, gy, gcx, gcy, g_moments, x_fwd, y_fwd, cx_fwd, cy_fwd, ok_fwd,
-                                          moments_fwd, g_x_in, g_y_in, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st)
+                                          moments_fwd, g_x_in, g_y_in, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st,
+                                          g_stacks)
                    : tl_strict::api_bwd_inv(*p, gx, gy, gcx, gcy, g_moments, x_fwd, y_fwd, cx_fwd, cy_fwd, ok_fwd,
-                                            moments_fwd, g_x_in, g_y_in, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st);
+                                            moments_fwd, g_x_in, g_y_in, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st,
+                                            g_stacks);
     if (herr) return hip_fail(herr, "trace_bwd_inv_kernel launch");
     const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0);
     hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, p->S, p->F, p->W, p->S, pl.nbx, g_c, g_t,

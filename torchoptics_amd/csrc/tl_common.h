@@ -39,12 +39,13 @@ static inline bool tl_walk_unrolled(int S, int P) { return S >= TL_INVU_MIN && S
                 hipStream_t st);                                                                     \
     int api_bwd(const tl_problem &p, const float *gx, const float *gy, const float *gcx,              \
                 const float *gcy, const double *gmom, float *gxin, float *gyin, double *part,         \
-                int nbx, int R, hipStream_t st, const float *gopd);                                  \
+                int nbx, int R, hipStream_t st, const float *gopd, const float *gstk);               \
     int api_bwd_inv(const tl_problem &p, const float *gx, const float *gy, const float *gcx,          \
                     const float *gcy, const double *gmom, const float *fx, const float *fy,           \
                     const float *fcx, const float *fcy, const uint8_t *fok, const double *fmom,       \
                     float *gxin, float *gyin, double *part_inv, double *part_ck, unsigned *poison,    \
-                    unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st);           \
+                    unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st,            \
+                    const float *gstk);                                                              \
     int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st); \
     }
 TL_DECLARE_MODE(tl_strict)

@@ -10,13 +10,13 @@ int api_fwd(const tl_problem &p, float *x, float *y, float *cx, float *cy, uint8
 { return tl_fast_impl::launch_fwd(p, x, y, cx, cy, ok, back, opd, stacks, part, nbx, R, st); }
 int api_bwd(const tl_problem &p, const float *gx, const float *gy, const float *gcx, const float *gcy,
             const double *gmom, float *gxin, float *gyin, double *part, int nbx, int R, hipStream_t st,
-            const float *gopd)
-{ return tl_fast_impl::launch_bwd(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, nullptr, nullptr, 0u, gopd); }
+            const float *gopd, const float *gstk)
+{ return tl_fast_impl::launch_bwd(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, nullptr, nullptr, 0u, gopd, nullptr, gstk); }
 int api_bwd_inv(const tl_problem &p, const float *gx, const float *gy, const float *gcx, const float *gcy,
                 const double *gmom, const float *fx, const float *fy, const float *fcx, const float *fcy,
                 const uint8_t *fok, const double *fmom, float *gxin, float *gyin, double *part_inv, double *part_ck,
-                unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st)
-{ return tl_fast_impl::launch_bwd_inv(p, gx, gy, gcx, gcy, gmom, fx, fy, fcx, fcy, fok, fmom, gxin, gyin, part_inv, part_ck, poison, token, nbx, R, nbx_ck, R_ck, st); }
+                unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st, const float *gstk)
+{ return tl_fast_impl::launch_bwd_inv(p, gx, gy, gcx, gcy, gmom, fx, fy, fcx, fcy, fok, fmom, gxin, gyin, part_inv, part_ck, poison, token, nbx, R, nbx_ck, R_ck, st, gstk); }
 int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st)
 { return tl_fast_impl::launch_selftest_arith(a, b, n, quot, root, st); }
 }

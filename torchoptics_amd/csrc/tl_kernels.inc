@@ -309,6 +309,12 @@ __device__ __forceinline__ float theta_from_cos(const float u)
 }
 __device__ __forceinline__ float theta_norm(const float cos2) { return theta_from_cos(tl_sqrt(cos2)); }
 
+// Upstream gradient of the three penalty quantities of one row of one ray: z_RELU, theta_norm, theta_prime_norm.  The
+// fused seed gq (moment 8: the per-ray sum of all three) enters them alike (pen_seed); a per-ray seed from the stacks
+// (PEN == kPenRay, tl_trace_bwd_stacks) adds its own value to each.
+struct PenSeed { float z, th, thp; };
+__device__ __forceinline__ PenSeed pen_seed(const float g) { return PenSeed{g, g, g}; }
+
 // Forward intermediates of one (live-branch) surface step that its adjoint needs.
 struct StepVals {
     float e, m2, tmp, cos2;           // intersection: e = -(r.d), m2 = |r|^2 - e^2, tmp = c m2 - 2 mz, cos2 = cos_i^2
@@ -354,7 +360,7 @@ __device__ __forceinline__ StepVals step_vals(const Ray &in, const float c, cons
 // reference passes through, so only the smooth branch is differentiated; rays that fail
 // anywhere have exactly zero gradient and are masked by the caller).
 // in : state entering the surface     v : forward intermediates     a : adjoint of the state leaving it (in/out)
-// PEN: gq = upstream gradient of the per-ray sum (theta + theta' + zRELU) at this surface, zpos = the
+// PEN: gq = upstream gradients of zRELU, theta and theta' at this surface (PenSeed), zpos = the
 // ray's z leaving the surface is > 0 (zRELU active).  theta = acos(u)/h with u = cos_i:
 // d theta/d cos2_i = -1/(2 h u sqrt(1-u^2)), zero where the clamp at 1-1e-7 is active; for theta'
 // 1 - cos_t^2 = mu^2 (1 - cos_i^2).
@@ -364,7 +370,7 @@ __device__ __forceinline__ StepVals step_vals(const Ray &in, const float c, cons
 // autograd show there (DESIGN.md "Penalty term").
 template <bool PEN, bool WALK = false>
 __device__ __forceinline__ void step_adjoint(const Ray &in, const float c, const float mu, const StepVals &v, Adj &a,
-                                             float &g_c, float &g_t, float &g_mu, const float gq = 0.0f,
+                                             float &g_c, float &g_t, float &g_mu, const PenSeed gq = PenSeed{},
                                              const bool zpos = false, const float b_d_opd = 0.0f)
 {
 #pragma clang fp contract(fast)
@@ -372,7 +378,7 @@ __device__ __forceinline__ void step_adjoint(const Ray &in, const float c, const
     //  re-associate, and every row of every ray pays for each of these instructions: 13 fewer than the literal
     //  transcription of the chain rule, same values to rounding.)
     // ---- reverse: z5 = z4 - t   (zRELU of the penalty term acts on z5)
-    if (PEN && zpos) a.z += gq;
+    if (PEN && zpos) a.z += gq.z;
     g_t = -a.z;
     // cz3 = sqrt(1 - (cx3^2 + cy3^2)):  d cz3 = -(cx3 dcx3 + cy3 dcy3) / cz3
     const float b_cz_r = a.cz * v.r_z;
@@ -398,18 +404,19 @@ __device__ __forceinline__ void step_adjoint(const Ray &in, const float c, const
         //  1 - u^2, whose relative error grows like 1/sin^2 towards normal incidence, exactly where this factor is large)
         //  The clamp is then decided on that sine too -- u = fp32 sqrt(1 - s2) rounds to <= 1 - 2^-23 exactly when
         //  s2 > 3 2^-24, kPenS2Min -- so that the decision and the value it guards cannot disagree.)
-        const float gh = -gq * (1.0f / kHalfPi);                       // 2 * (0.5 / (pi/2)): twice the adjoint
+        const float gh = -gq.th * (1.0f / kHalfPi);                    // 2 * (0.5 / (pi/2)): twice the adjoint
+        const float ght = -gq.thp * (1.0f / kHalfPi);                  // ... of theta'
         if (WALK) {
             const float s2t = (mu * mu) * v.s2;                        // sin^2 on the refraction side
             pen_cos2_x2 = (v.s2 > kPenS2Min) ? gh * __builtin_amdgcn_rsqf((1.0f - v.s2) * v.s2) : 0.0f;
-            w += (s2t > kPenS2Min) ? gh * __builtin_amdgcn_rsqf((1.0f - s2t) * s2t) : 0.0f;
+            w += (s2t > kPenS2Min) ? ght * __builtin_amdgcn_rsqf((1.0f - s2t) * s2t) : 0.0f;
         } else {
             const float u = tl_sqrt(v.cos2);
             const float uu = u * u, s2f = 1.0f - uu;
             pen_cos2_x2 = (u <= kAcosHi) ? gh * __builtin_amdgcn_rsqf(uu * s2f) : 0.0f;
             const float ut = tl_sqrt(1.0f - (mu * mu) * s2f);           // the forward's cos_t
             const float utt = ut * ut;
-            w += (ut <= kAcosHi) ? gh * __builtin_amdgcn_rsqf(utt * (1.0f - utt)) : 0.0f;
+            w += (ut <= kAcosHi) ? ght * __builtin_amdgcn_rsqf(utt * (1.0f - utt)) : 0.0f;
         }
     }
     const float mw = mu * w;
@@ -457,7 +464,7 @@ __device__ __forceinline__ void step_adjoint(const Ray &in, const float c, const
 
 template <bool PEN>
 __device__ __forceinline__ void step_bwd(const Ray &in, const float c, const float mu, Adj &a,
-                                         float &g_c, float &g_t, float &g_mu, const float gq = 0.0f,
+                                         float &g_c, float &g_t, float &g_mu, const PenSeed gq = PenSeed{},
                                          const bool zpos = false, const float b_d_opd = 0.0f, float *d_out = nullptr)
 {
     const StepVals v = step_vals(in, c, mu);
@@ -644,11 +651,11 @@ __device__ __forceinline__ AsphVals asph_vals(const Ray &in, const float zout, c
 
 // Adjoint of step_fwd_asph for a ray alive after the step.  ds/d(anything) comes from the implicit function theorem
 // on F(s; .) = 0, so the Newton iterations are never differentiated.  g_asph = (d/dkappa, d/da4, d/da6, d/da8, d/da10).
-// PEN: gq = upstream gradient of this row's theta + theta' + zRELU (see step_adjoint), zpos = zRELU active.
+// PEN: gq = upstream gradients of this row's zRELU, theta and theta' (see step_adjoint), zpos = zRELU active.
 // b_s_opd: upstream gradient of the optical path length times n_k.
 template <bool PEN = false, bool WALK = false>
 __device__ __forceinline__ void asph_adjoint(const Ray &in, const Asph &A, const float mu, const AsphVals &v, Adj &a,
-                                             float &g_c, float &g_t, float &g_mu, float g_asph[5], const float gq = 0.0f,
+                                             float &g_c, float &g_t, float &g_mu, float g_asph[5], const PenSeed gq = PenSeed{},
                                              const bool zpos = false, const float b_s_opd = 0.0f)
 {
 #pragma clang fp contract(fast)
@@ -661,7 +668,7 @@ __device__ __forceinline__ void asph_adjoint(const Ray &in, const Asph &A, const
     const float rho2 = rho * rho, rho3 = rho2 * rho, rho4 = rho2 * rho2;
     const float sag2 = 0.25f * K * c3 * rq3 + (2.0f * A.a0 + rho * (6.0f * A.a1 + rho * (12.0f * A.a2 + rho * (20.0f * A.a3))));
     // ---- reverse
-    if (PEN && zpos) a.z += gq;
+    if (PEN && zpos) a.z += gq.z;
     g_t = -a.z;
     const float b_czsq = a.cz * (0.5f * r_z);
     const float b_cx3 = a.cx - 2.0f * cx3 * b_czsq;
@@ -680,8 +687,8 @@ __device__ __forceinline__ void asph_adjoint(const Ray &in, const Asph &A, const
         const float hh = 0.5f / kHalfPi;
         const float u = fabsf(cos_i);
         const float s2t = (mu * mu) * s2;
-        pen_cos2_i = (WALK ? s2 > kPenS2Min : u <= kAcosHi) ? -gq * hh * tl_rsq(s2) * tl_rcp(u) : 0.0f;
-        b_cos2_t += (WALK ? s2t > kPenS2Min : cos_t <= kAcosHi) ? -gq * hh * tl_rsq(s2t) * r_t : 0.0f;
+        pen_cos2_i = (WALK ? s2 > kPenS2Min : u <= kAcosHi) ? -gq.th * hh * tl_rsq(s2) * tl_rcp(u) : 0.0f;
+        b_cos2_t += (WALK ? s2t > kPenS2Min : cos_t <= kAcosHi) ? -gq.thp * hh * tl_rsq(s2t) * r_t : 0.0f;
     }
     b_mu -= b_g * cos_i + 2.0f * mu * s2 * b_cos2_t;
     const float b_cos_i = (-b_g * mu + 2.0f * (mu * mu) * cos_i * b_cos2_t) + 2.0f * cos_i * pen_cos2_i;
@@ -741,7 +748,7 @@ __device__ __forceinline__ void asph_adjoint(const Ray &in, const Asph &A, const
 template <bool PEN = false>
 __device__ __forceinline__ void step_bwd_asph(const Ray &in, const float zout, const Asph &A, const float t,
                                               const float mu, Adj &a, float &g_c, float &g_t, float &g_mu,
-                                              float g_asph[5], const float gq = 0.0f, const bool zpos = false,
+                                              float g_asph[5], const PenSeed gq = PenSeed{}, const bool zpos = false,
                                               const float b_s_opd = 0.0f, float *s_out = nullptr)
 {
     const AsphVals v = asph_vals(in, zout, A, t, mu);
@@ -1203,14 +1210,20 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_plain_kernel(
 // keeps gradient for rays that die LATER: theta_k / zRELU_k of the surfaces a ray passed alive were
 // computed before it was parked, so the reverse sweep starts, per ray, at its last live surface
 // (`live` bit k = ok after surface k); parked rays only feed d/dt_k through zRELU = max(-t_k, 0).
-template <int NS, bool ASPH, bool PEN>
+// PEN is tri-state (PenMode): kPenNone; kPenUniform, the fused seed gq of moment 8 for every row and ray; kPenRay, gq plus
+// the per-ray seeds of the stacks (gstk: [3][S][rows of the grid * P], the layout of tl_trace_fwd's `stacks`), read row
+// by row inside the reverse sweep.  A ray that died on the way is differentiated whenever a stack seed is given, even
+// with gq = 0 (a loss on the stacks alone).  gstk is NULL and never read for the other two.
+enum PenMode : int { kPenNone = 0, kPenUniform = 1, kPenRay = 2 };
+template <int NS, bool ASPH, int PEN>
 __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
     const tl_problem pa, const float *__restrict__ gx, const float *__restrict__ gy,
     const float *__restrict__ gcx, const float *__restrict__ gcy, const double *__restrict__ gmom,
     float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part, const int /*plan hint, unused*/,
     const double *__restrict__ fb_mom, const unsigned *__restrict__ fb_poison, const unsigned fb_token,
-    const float *__restrict__ gopd, const uint8_t *__restrict__ dead_ok)
+    const float *__restrict__ gopd, const uint8_t *__restrict__ dead_ok, const float *__restrict__ gstk)
 {
+    constexpr bool PENB = PEN != kPenNone, STK = PEN == kPenRay;
     // launched as the fallback of a walk-back kernel (fb_poison given): run only when that launch did not do the job --
     // or, for the penalty term (dead_ok = the forward's ok bytes: 0 dead, 1 live), over exactly the rays the walk-back cannot take:
     // those that died on the way still carry the gradient of the rows they passed alive.  Waves none of whose rays
@@ -1368,7 +1381,7 @@ __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
         if (!allow_back) ok = ok && !((dz < 0.0f) && ok && ((mbits >> (S - 1)) & 1u));
 
         const int64_t o = (int64_t)fw * p.P + ip;
-        if (__ballot(PEN ? (take && gq != 0.0f) || alive : alive) == 0ull) {   // wave-uniform: nothing to differentiate
+        if (__ballot(PEN ? (take && (STK || gq != 0.0f)) || alive : alive) == 0ull) {   // wave-uniform: nothing to differentiate
             if (take) { if (gxin) gxin[o] = 0.0f; if (gyin) gyin[o] = 0.0f; }
             continue;
         }
@@ -1407,17 +1420,25 @@ __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
                 const float zout = (k + 1 < NS && k + 1 < S) ? ck[k + 1 < NS ? k + 1 : k].z : z_last;
                 const float b_d_opd = gopd ? go * uload(n_w, k) : 0.0f;
                 float d_k = 0.0f;                                  // marching distance of this row (gopd only)
+                PenSeed sk = pen_seed(gq);                         // this row's seeds of zRELU, theta, theta'
+                if (STK && take) {
+                    const size_t n_st = (size_t)gridDim.y * p.P;
+                    const float *__restrict__ q = gstk + ((size_t)k * n_st + (size_t)o);
+                    sk.z += q[0];
+                    sk.th += q[(size_t)S * n_st];
+                    sk.thp += q[2 * (size_t)S * n_st];
+                }
                 if (ASPH && ((kbits >> k) & 1u)) {
                     float ga[5];
-                    step_bwd_asph<PEN>(ck[k], zout, load_asph(p, k), uload(p.t, k), uload(mu_w, k), a, g_c, g_t, g_mu, ga, gq, zout > 0.0f,
-                                       b_d_opd, gopd ? &d_k : nullptr);
+                    step_bwd_asph<PENB>(ck[k], zout, load_asph(p, k), uload(p.t, k), uload(mu_w, k), a, g_c, g_t, g_mu, ga, sk, zout > 0.0f,
+                                        b_d_opd, gopd ? &d_k : nullptr);
 #pragma unroll
                     for (int j = 0; j < 5; ++j) {
                         const float v = wave_sum_f32(lk ? ga[j] : 0.0f);
                         if ((tid & 63) == 0) sasph[5 * k + j][tid >> 6] += v;
                     }
                 } else {
-                    step_bwd<PEN>(ck[k], uload(p.c, k), uload(mu_w, k), a, g_c, g_t, g_mu, gq, zout > 0.0f, b_d_opd, gopd ? &d_k : nullptr);
+                    step_bwd<PENB>(ck[k], uload(p.c, k), uload(mu_w, k), a, g_c, g_t, g_mu, sk, zout > 0.0f, b_d_opd, gopd ? &d_k : nullptr);
                 }
                 if (PEN && !lk) { a.x = a.y = a.z = a.cx = a.cy = a.cz = 0.0f; }     // parked after k: nothing flows below
                 if (gopd) {
@@ -1429,7 +1450,7 @@ __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
                     sacc[NS + k][tid] = s_t + g_t;
                     sacc[2 * NS + k][tid] = s_mu + g_mu;
                 } else if (PEN && take && -uload(p.t, k) > 0.0f) {
-                    sacc[NS + k][tid] = s_t - gq;     // parked ray: zRELU_k = max(0 - t_k, 0)
+                    sacc[NS + k][tid] = s_t - sk.z;   // parked ray: zRELU_k = max(0 - t_k, 0)
                 }
             }
         }
@@ -1889,16 +1910,20 @@ __device__ __forceinline__ float sag_at(const Asph &A, const float rho, float &r
 //   the rows they passed alive, which only a forward re-trace can give: the checkpoint kernel queued behind this one
 //   runs over exactly those rays (selective pass, whole waves skipped where every ray lived) and the reduction adds
 //   the two partial arrays.
-template <int NS, bool ASPH, bool PEN>
-__global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN)) void trace_bwd_inv_unrolled_kernel(
+// PEN (PenMode, see trace_bwd_kernel) == kPenRay: the live rays add their per-ray stack seeds (gstk, see trace_bwd_kernel)
+//   to gq, row by row: three loads per row, issued at the top of the row so that the walk of the row hides them.  Dead lanes
+//   take zero seeds; rays that died on the way reach the checkpoint pass through the scan map, as above.
+template <int NS, bool ASPH, int PEN>
+__global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)) void trace_bwd_inv_unrolled_kernel(
     const tl_problem pa, const float *__restrict__ gx, const float *__restrict__ gy,
     const float *__restrict__ gcx, const float *__restrict__ gcy, const double *__restrict__ gmom,
     const float *__restrict__ fx, const float *__restrict__ fy, const float *__restrict__ fcx,
     const float *__restrict__ fcy, const uint8_t *__restrict__ fok, const double *__restrict__ fmom,
     float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part, const int /*plan hint, unused*/,
-    unsigned *__restrict__ poison, const unsigned token)
+    unsigned *__restrict__ poison, const unsigned token, const float *__restrict__ gstk)
 {
 #pragma clang fp contract(fast)       // see TL_REVERSE_CONTRACT above
+    constexpr bool PENB = PEN != kPenNone, STK = PEN == kPenRay;
     // no per-ray flags in `fok` (see trace_bwd_inv_kernel): the checkpoint kernel does this batch
     if (fmom && !pa.cond_flags && ill_conditioned(fmom, pa.F * tl_lenses(pa))) return;
     extern __shared__ float sacc_dyn[];                         // [2 NS][SLOTS]: g_t rows, then g_mu rows [; ASPH: [2 slots][kBlock]]
@@ -2071,6 +2096,13 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN)) void trace
                 if (asph_p) TL_LOAD_HIT(__popc(kbits & ((1u << kp) - 1u)), px_s, py_s);
             }
             const bool zpos = PEN && (hz - t_k) > 0.0f;                      // zRELU of this row is active
+            PenSeed sk = pen_seed(gq_l);                                     // this row's seeds of zRELU, theta, theta'
+            if (STK) {                                                       // (kPenRay) + the stacks' seeds of this ray
+                const float *sq_ = gstk + ((size_t)k * n_rays_all + (size_t)ob);
+                float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+                if (valid) { s0 = sq_[ut]; s1 = (sq_ + (size_t)NS * n_rays_all)[ut]; s2 = (sq_ + (size_t)(2 * NS) * n_rays_all)[ut]; }
+                sk.z += alive ? s0 : 0.0f; sk.th += alive ? s1 : 0.0f; sk.thp += alive ? s2 : 0.0f;
+            }
             StepVals v;
             AsphVals av;
             Asph A;
@@ -2176,14 +2208,14 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN)) void trace
             float g_c, g_t, g_mu;
             if (asph_k) {
                 float ga[5];
-                asph_adjoint<PEN, true>(in, A, mu, av, a, g_c, g_t, g_mu, ga, gq_l, zpos);
+                asph_adjoint<PENB, true>(in, A, mu, av, a, g_c, g_t, g_mu, ga, sk, zpos);
                 // lane q of every quad keeps the quad's sum of term q (kappa, a4, a6 | a8, a10) in two private slots
                 const int jk = __popc(kbits & ((1u << k) - 1u));
                 sasph_dyn[(2 * jk) * kBlock + tid] += quad_term_sums(ga[0], ga[1], ga[2], q_odd, q_hi);
                 sasph_dyn[(2 * jk + 1) * kBlock + tid] += quad_term_sums(ga[3], ga[4], 0.0f, q_odd, q_hi);
             } else {
                 v.inv_den = tl_rcp_adj(in.cz + v.cos_i);
-                step_adjoint<PEN, true>(in, c, mu, v, a, g_c, g_t, g_mu, gq_l, zpos);
+                step_adjoint<PENB, true>(in, c, mu, v, a, g_c, g_t, g_mu, sk, zpos);
             }
             dx = ix; dy = iy; dz = iz;                         // the ray between surfaces k-1 and k
             r_c[k] += g_c;
@@ -2330,15 +2362,18 @@ template <int NS>
 static int launch_bwd_ns(const tl_problem &p, const float *gx, const float *gy, const float *gcx,
                          const float *gcy, const double *gmom, float *gxin, float *gyin,
                          double *part, int nbx, int R, hipStream_t st, const double *fb_mom, const unsigned *fb_poison,
-                         unsigned fb_token, const float *gopd, const uint8_t *dead_ok)
+                         unsigned fb_token, const float *gopd, const uint8_t *dead_ok, const float *gstk)
 {
     dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
+    // (gstk: the per-ray stack seeds, kPenRay; the caller has checked p.aggregate)
 #define TL_BWD(ASPH_, PEN_) \
-    hipLaunchKernelGGL((trace_bwd_kernel<NS, ASPH_, PEN_>), grid, block, 0, st, p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, R, fb_mom, fb_poison, fb_token, gopd, dead_ok)
-    if (p.surf_kind && p.aggregate) TL_BWD(true, true);
-    else if (p.surf_kind) TL_BWD(true, false);
-    else if (p.aggregate) TL_BWD(false, true);
-    else TL_BWD(false, false);
+    hipLaunchKernelGGL((trace_bwd_kernel<NS, ASPH_, PEN_>), grid, block, 0, st, p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, R, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk)
+    if (p.surf_kind && p.aggregate && gstk) TL_BWD(true, kPenRay);
+    else if (p.surf_kind && p.aggregate) TL_BWD(true, kPenUniform);
+    else if (p.surf_kind) TL_BWD(true, kPenNone);
+    else if (p.aggregate && gstk) TL_BWD(false, kPenRay);
+    else if (p.aggregate) TL_BWD(false, kPenUniform);
+    else TL_BWD(false, kPenNone);
 #undef TL_BWD
     return (int)hipGetLastError();
 }
@@ -2348,17 +2383,17 @@ static int launch_bwd(const tl_problem &p, const float *gx, const float *gy, con
                       const float *gcy, const double *gmom, float *gxin, float *gyin, double *part,
                       int nbx, int R, hipStream_t st, const double *fb_mom = nullptr,
                       const unsigned *fb_poison = nullptr, unsigned fb_token = 0u, const float *gopd = nullptr,
-                      const uint8_t *dead_ok = nullptr)
+                      const uint8_t *dead_ok = nullptr, const float *gstk = nullptr)
 {
     const int ns = tl_bwd_bucket(p.S);
     switch (ns) {
-    case 4:  return launch_bwd_ns<4>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
-    case 8:  return launch_bwd_ns<8>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
-    case 12: return launch_bwd_ns<12>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
-    case 16: return launch_bwd_ns<16>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
-    case 20: return launch_bwd_ns<20>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
-    case 24: return launch_bwd_ns<24>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
-    case 32: return launch_bwd_ns<32>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok);
+    case 4:  return launch_bwd_ns<4>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 8:  return launch_bwd_ns<8>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 12: return launch_bwd_ns<12>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 16: return launch_bwd_ns<16>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 20: return launch_bwd_ns<20>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 24: return launch_bwd_ns<24>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 32: return launch_bwd_ns<32>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
     default: return -1;
     }
 }
@@ -2370,7 +2405,7 @@ static int launch_bwd_inv(const tl_problem &p, const float *gx, const float *gy,
                           const double *gmom, const float *fx, const float *fy, const float *fcx, const float *fcy,
                           const uint8_t *fok, const double *fmom, float *gxin, float *gyin, double *part_inv,
                           double *part_ck, unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck,
-                          hipStream_t st)
+                          hipStream_t st, const float *gstk = nullptr)
 {
     dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
     // TL_INV_LDS_PAD (bytes, development only): extra dynamic LDS per block = fewer resident blocks per CU, to measure how
@@ -2385,10 +2420,11 @@ static int launch_bwd_inv(const tl_problem &p, const float *gx, const float *gy,
 #define TL_INV_ARGS p, gx, gy, gcx, gcy, gmom, fx, fy, fcx, fcy, fok, fmom, gxin, gyin, part_inv, R, poison, token
 #define TL_INVU_V(NS_, ASPH_, PEN_) \
     hipLaunchKernelGGL((trace_bwd_inv_unrolled_kernel<NS_, ASPH_, PEN_>), grid, block, \
-                       (NS_ < kInvUnrollPairMin ? 2 : 1) * lds + lds_asph + lds_pad, st, TL_INV_ARGS)
+                       (NS_ < kInvUnrollPairMin ? 2 : 1) * lds + lds_asph + lds_pad, st, TL_INV_ARGS, gstk)
 #define TL_INVU(NS_) \
-    case NS_: if (asph && pen) TL_INVU_V(NS_, true, true); else if (asph) TL_INVU_V(NS_, true, false); \
-              else if (pen) TL_INVU_V(NS_, false, true); else TL_INVU_V(NS_, false, false); break
+    case NS_: if (asph && pen && gstk) TL_INVU_V(NS_, true, kPenRay); else if (asph && pen) TL_INVU_V(NS_, true, kPenUniform); \
+              else if (asph) TL_INVU_V(NS_, true, kPenNone); else if (pen && gstk) TL_INVU_V(NS_, false, kPenRay); \
+              else if (pen) TL_INVU_V(NS_, false, kPenUniform); else TL_INVU_V(NS_, false, kPenNone); break
     if (tl_walk_unrolled(p.S, p.P) && !rolled_only && (!asph || hits)) {     // (no skip there for waves past the end of a small pupil)
         switch (p.S) {
 #ifdef TL_INVU_DEV      // development builds: the row counts of the bench workloads only (compile time)
@@ -2412,7 +2448,7 @@ static int launch_bwd_inv(const tl_problem &p, const float *gx, const float *gy,
     const int herr = (int)hipGetLastError();
     if (herr) return herr;
     return launch_bwd(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part_ck, nbx_ck, R_ck, st, fmom, poison, token, nullptr,
-                      (pen || p.cond_flags) ? fok : nullptr);
+                      (pen || p.cond_flags) ? fok : nullptr, gstk);
 }
 
 }  // namespace TL_NS

@@ -329,8 +329,10 @@ public:
         Tensor opd_out = want_opd ? opd.permute({0, 1, 3, 2}) : at::empty({0}, fopt);
         Tensor stk_out = stacks.defined() ? stacks.permute({0, 1, 2, 3, 5, 4}) : at::empty({0}, fopt);
         Tensor rms_out = rms.defined() ? rms : at::empty({0}, fopt);
-        if (want_opd) ctx->mark_non_differentiable({ok, back, stk_out});
-        else ctx->mark_non_differentiable({ok, back, stk_out, opd_out});
+        // the stacks are differentiable (their gradient reaches tl_trace_bwd*_stacks as g_stacks); the placeholders are not
+        if (want_opd) ctx->mark_non_differentiable({ok, back});
+        else ctx->mark_non_differentiable({ok, back, opd_out});
+        if (!stacks.defined()) ctx->mark_non_differentiable({stk_out});
         if (!rms.defined()) ctx->mark_non_differentiable({rms_out});
         return {xo, yo, cxo, cyo, ok, back, moments, opd_out, stk_out, rms_out};
     }
@@ -358,7 +360,12 @@ public:
             gmom = gmom.defined() ? gmom + via_rms : via_rms;
         }
         if (gopd.defined() && (!n.n_index.defined() || gopd.numel() == 0)) gopd = Tensor();
-        if (!gx.defined() && !gy.defined() && !gcx.defined() && !gcy.defined() && !gmom.defined() && !gopd.defined()) return out;
+        // gradient of the per-surface stacks [3,S,B,F,P,W] -> g_stacks [3][S][B,F,W,P], the layout of the forward's output
+        Tensor gstk;
+        if (aggregate && g.size() > 8 && g[8].defined() && g[8].numel() > 0) gstk = f32(g[8]).permute({0, 1, 2, 3, 5, 4}).contiguous();
+        if (!gx.defined() && !gy.defined() && !gcx.defined() && !gcy.defined() && !gmom.defined() && !gopd.defined() &&
+            !gstk.defined())
+            return out;
         const bool asph = n.kind.defined();
         const at::Device dev = n.x_e.device();
         c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
@@ -385,8 +392,8 @@ public:
         {
             Timed timed(1, st);
             if (use_inv)
-                check(tl_trace_bwd_from_outputs(
-                          &prob, (const float *)ptr(gxd), (const float *)ptr(gyd), (const float *)ptr(gcxd),
+                check(tl_trace_bwd_from_outputs_stacks(
+                          &prob, (const float *)ptr(gstk), (const float *)ptr(gxd), (const float *)ptr(gyd), (const float *)ptr(gcxd),
                           (const float *)ptr(gcyd), (const double *)ptr(gmd), (const float *)ptr(fx), (const float *)ptr(fy),
                           (const float *)ptr(fcx), (const float *)ptr(fcy), (const uint8_t *)ptr(fok), (const double *)ptr(fmom),
                           (float *)g_c.data_ptr(), (float *)g_t.data_ptr(), (float *)g_mu.data_ptr(), (float *)g_z.data_ptr(),
@@ -394,7 +401,8 @@ public:
                           (float *)ptr(gxin), (float *)ptr(gyin), ws.data_ptr(), (size_t)ws.numel(), (void *)st),
                       "tl_trace_bwd_from_outputs");
             else
-                check(tl_trace_bwd(&prob, (const float *)ptr(gxd), (const float *)ptr(gyd), (const float *)ptr(gcxd),
+                check(tl_trace_bwd_stacks(&prob, (const float *)ptr(gstk), (const float *)ptr(gxd), (const float *)ptr(gyd),
+                                   (const float *)ptr(gcxd),
                                    (const float *)ptr(gcyd), (const double *)ptr(gmd), (const float *)ptr(gopdd),
                                    (float *)g_c.data_ptr(), (float *)g_t.data_ptr(), (float *)g_mu.data_ptr(),
                                    (float *)g_z.data_ptr(), (float *)g_cx.data_ptr(), (float *)g_cy.data_ptr(),

@@ -294,13 +294,16 @@ class TraceFunction(torch.autograd.Function):
             flags = [torch.empty(0, dtype=torch.bool, device=dev) for _ in range(2)]
         opd_out = opd.permute(0, 1, 3, 2) if want_opd else torch.empty(0, device=dev)
         stk_out = stacks.permute(0, 1, 2, 3, 5, 4) if stacks is not None else torch.empty(0, device=dev)
-        ctx.mark_non_differentiable(*flags, stk_out)
+        # the stacks are differentiable (their gradient reaches tl_trace_bwd*_stacks as g_stacks); the placeholders are not
+        ctx.mark_non_differentiable(*flags)
         if not want_opd:
             ctx.mark_non_differentiable(opd_out)
+        if stacks is None:
+            ctx.mark_non_differentiable(stk_out)
         return (*outs, *flags, moments, opd_out, stk_out)
 
     @staticmethod
-    def backward(ctx, gx, gy, gcx, gcy, _gok, _gback, gmom, gopd, _gstk):
+    def backward(ctx, gx, gy, gcx, gcy, _gok, _gback, gmom, gopd, gstk):
         (x_e, y_e, z, cx, cy, c, t, mu, mask_u8, kappa, poly, kind_u8, fx, fy, fcx, fcy, fok, fmom,
          n_index, hits, cond) = ctx.saved_tensors
         dev = x_e.device
@@ -309,7 +312,12 @@ class TraceFunction(torch.autograd.Function):
         n_in = 20
         if gopd is not None and (n_index is None or gopd.numel() == 0):
             gopd = None
-        if gx is None and gy is None and gcx is None and gcy is None and gmom is None and gopd is None:
+        # gradient of the per-surface stacks [3,S,B,F,P,W] -> g_stacks [3][S][B,F,W,P], the layout of the forward's output
+        gstkd = None
+        if ctx.aggregate and gstk is not None and gstk.numel() > 0:
+            gstkd = gstk.to(torch.float32).permute(0, 1, 2, 3, 5, 4).contiguous()
+        if (gx is None and gy is None and gcx is None and gcy is None and gmom is None and gopd is None
+                and gstkd is None):
             return (None,) * n_in
         asph = kind_u8 is not None
         lib = _lib.lib()
@@ -340,16 +348,16 @@ class TraceFunction(torch.autograd.Function):
         g_n = new(B, W, S + 1) if gopdd is not None else None
         with _on_device(dev), _Timed("bwd", dev):
             if ctx.use_inv:
-                rc = lib.tl_trace_bwd_from_outputs(
-                    C.byref(prob), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd), _lib.ptr(gcyd), _lib.ptr(gmd),
+                rc = lib.tl_trace_bwd_from_outputs_stacks(
+                    C.byref(prob), _lib.ptr(gstkd), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd), _lib.ptr(gcyd), _lib.ptr(gmd),
                     _lib.ptr(fx), _lib.ptr(fy), _lib.ptr(fcx), _lib.ptr(fcy), _lib.ptr(fok), _lib.ptr(fmom),
                     *[_lib.ptr(q) for q in parts[:6]], _lib.ptr(g_kappa), _lib.ptr(g_poly), _lib.ptr(gxin),
                     _lib.ptr(gyin), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
             else:
-                rc = lib.tl_trace_bwd(C.byref(prob), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd), _lib.ptr(gcyd),
-                                      _lib.ptr(gmd), _lib.ptr(gopdd), *[_lib.ptr(q) for q in parts[:6]], _lib.ptr(g_kappa),
-                                      _lib.ptr(g_poly), _lib.ptr(g_n), _lib.ptr(gxin), _lib.ptr(gyin), _lib.ptr(ws),
-                                      ws.numel(), _stream_ptr(dev))
+                rc = lib.tl_trace_bwd_stacks(C.byref(prob), _lib.ptr(gstkd), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd),
+                                             _lib.ptr(gcyd), _lib.ptr(gmd), _lib.ptr(gopdd), *[_lib.ptr(q) for q in parts[:6]],
+                                             _lib.ptr(g_kappa), _lib.ptr(g_poly), _lib.ptr(g_n), _lib.ptr(gxin), _lib.ptr(gyin),
+                                             _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
         _lib.check(rc, "tl_trace_bwd")
         g_c, g_t, g_mu, g_z, g_cx, g_cy = parts
         need = ctx.needs_input_grad

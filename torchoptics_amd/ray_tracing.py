@@ -227,8 +227,10 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
 
     Extras (not in the reference):
       aggregate   True: a 7th return value `stacks` = {'z_RELU', 'theta_norm', 'theta_prime_norm'}, each a
-                  list of S tensors [1,F,P,W] as in the reference (:641-657).  The stacks are plain values;
-                  the differentiable quantity is their fused sum, see `penalty_sum(stacks, n_sequence)`.
+                  list of S tensors [1,F,P,W] as in the reference (:641-657), differentiable like the reference's:
+                  any function of them back-propagates through the trace's backward kernels (per-ray, per-row seeds).
+                  `penalty_sum(stacks, n_sequence)` on the returned PenaltyStacks reads the fused sum instead, and
+                  the two may be mixed in one loss (their gradients add).
                   'sum': the same 7th value WITHOUT the per-surface tensors -- only the fused sums that
                   `penalty_sum` / `unsupervised_loss` read (the lists are 12 S bytes of HBM writes per ray);
       mode        'strict' | 'fast' arithmetic (default ops.get_default_mode());
@@ -384,7 +386,8 @@ def _trace_skew_in_lens_chunks(nb, B, x, y, z, cx, cy, c, t, mu, mask, aggregate
 class PenaltyStacks(dict):
     """The `stacks` dict of trace_skew(aggregate=True): three lists of S per-surface tensors, plus
     `q_sum` = sum over all rays of (sum theta + sum theta' + sum z_RELU) with NaN -> 0, fused into the
-    trace kernel and differentiable through its backward kernel (the lists themselves are values only)."""
+    trace kernel.  Both are differentiable through the trace's backward kernels: the lists per ray and row
+    (weights, single terms, single rows), `q_sum` as one seed for all of them."""
 
     def __init__(self, stk, moments, n_lens=1):
         super().__init__()
@@ -404,7 +407,8 @@ class PenaltyStacks(dict):
 
 def penalty_sum(stacks, n_sequence: int):
     """sumQ of the reference's compute_loss_out (optics_simulator_lite.py:441-448):
-    Q = (sum_k theta + sum_k theta' + sum_k z_RELU) / n_sequence per ray, NaN -> 0, summed over rays."""
+    Q = (sum_k theta + sum_k theta' + sum_k z_RELU) / n_sequence per ray, NaN -> 0, summed over rays.
+    A PenaltyStacks reads the fused sum; a plain dict of the lists is summed here, differentiably, through the lists."""
     if isinstance(stacks, PenaltyStacks):
         return (stacks.q_sum / n_sequence).to(torch.float32)
     q = (torch.stack(stacks['theta_norm'], 0).sum(0) + torch.stack(stacks['theta_prime_norm'], 0).sum(0)
