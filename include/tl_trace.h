@@ -32,6 +32,7 @@ extern "C" {
 #define TL_NMOM 10               /* per-field sums, see tl_trace_fwd */
 #define TL_MAX_POLY 4            /* even aspheric terms a4,a6,a8,a10 */
 #define TL_MAX_HIT_SLOTS 8       /* aspheric rows per lens whose hit points tl_trace_fwd can hand to the walk-back */
+#define TL_MAX_AIM_ITER 16       /* Newton steps of tl_ray_aim_iter (RayTracer n_ray_aiming_iter) */
 
 enum {
     TL_OK = 0,
@@ -309,6 +310,27 @@ int tl_ray_aim(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const
                const float *n_d, const uint8_t *mask, const float *kappa, const float *poly, const uint8_t *surf_kind,
                const float *z, const float *hfov, const float *fields, const float *epd, int32_t allow_backward,
                float *x_scale, float *y_scale, float *y_offset, void *stream);
+
+/*
+ * Ray aiming, N iterations (RayTracer(n_ray_aiming_iter=N), any mode, with or without a vignetting function): tl_ray_aim's
+ * arguments with n_iter, tee_ref and rs before the outputs, in one launch for any N.  Per (lens, field, wavelength):
+ *   p0    the reference tee points (bottom y, top y, sagittal x) = tee_ref[b,f,0..2], default (-1, 1, 1); the meridional
+ *         rays sit at pupil x = 0, the sagittal ray at y = (p0.bottom + p0.top) / 2 (apply_vignetting of the tee rays)
+ *   rs    stop radius: rs[b] when given ('paraxial': magnification * epd / 2), else the on-axis d-line marginal ray
+ *   step k = 1..N: trace the tee rays at p0 + s_{k-1} to the stop, error e = stop / rs - p0, s_k = s_{k-1} - e / J;
+ *         J = d(xs_rel + ys_rel)/dp at k = 1 (the reference's; N = 1 is tl_ray_aim's result bit for bit), the stop
+ *         coordinate's own partial (d xs/d xp sagittal, d ys/d yp meridional) at k >= 2.  A dead ray or a non-finite
+ *         step: no step in that iteration.
+ *   map   affine through (p0 -> p0 + s_N):  x_scale = (p0.x + s.x) / p0.x,
+ *         y_scale = ((p0.u + s.u) - (p0.l + s.l)) / (p0.u - p0.l),  y_offset = (p0.l s.u - p0.u s.l) / (p0.l - p0.u)
+ *   n_iter in 1..TL_MAX_AIM_ITER; tee_ref [B,F,3] float nullable; rs [B] float nullable.  TL_EINVAL (before any HIP call)
+ *   for a bad argument.  One 16-lane group per (lens, field, wavelength): an iteration costs one trace of latency.
+ */
+int tl_ray_aim_iter(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const float *c, const float *t, const float *n,
+                    const float *n_d, const uint8_t *mask, const float *kappa, const float *poly, const uint8_t *surf_kind,
+                    const float *z, const float *hfov, const float *fields, const float *epd, int32_t allow_backward,
+                    int32_t n_iter, const float *tee_ref, const float *rs, float *x_scale, float *y_scale, float *y_offset,
+                    void *stream);
 
 /*
  * The aimed fan, [B,F,W,P] floats (consecutive pupil points contiguous), from one shared relative pupil grid xp, yp [P] and

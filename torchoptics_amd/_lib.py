@@ -17,6 +17,7 @@ TL_NMOM = 10
 TL_MAX_SURFACES = 32
 TL_MAX_POLY = 4
 TL_MAX_HIT_SLOTS = 8
+TL_MAX_AIM_ITER = 16
 MODE_STRICT, MODE_FAST = 0, 1
 
 
@@ -64,6 +65,7 @@ _SIGNATURES = {
     "tl_trace_bwd_f64": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 15 + [_VP, C.c_size_t, _VP]),
     "tl_selftest_arith": (C.c_int, [C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "tl_ray_aim": (C.c_int, [C.c_int32] * 5 + [_VP] * 12 + [C.c_int32] + [_VP] * 4),
+    "tl_ray_aim_iter": (C.c_int, [C.c_int32] * 5 + [_VP] * 12 + [C.c_int32] * 2 + [_VP] * 6),
 }
 EXPORTS = tuple(_SIGNATURES)
 

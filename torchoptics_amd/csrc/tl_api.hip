@@ -605,6 +605,98 @@ __global__ __launch_bounds__(64) void ray_aim_kernel(int B, int F, int W, int K,
     y_offset[i] = (float)(((-1.0) * step[1] - (1.0) * step[0]) / (-2.0));
 }
 
+// ---------------------------------------------------------------- iterated ray aiming (n_ray_aiming_iter = N >= 1)
+// N Newton steps on the tee rays, then the affine map from the reference points p0 to the converged ones (DESIGN.md,
+// "Iterated ray aiming").  Step k traces the tee rays at p0 + s_{k-1} (s = accumulated step, s_0 = 0); step 1 takes the
+// reference's Jacobian d(xs_rel + ys_rel)/dp -- so N = 1 is ray_aim_kernel's result bit for bit --, steps k >= 2 the
+// stop coordinate's own partial (d xs/d xp sagittal, d ys/d yp meridional: the sum's converges only linearly on the
+// sagittal ray, and can diverge).  A dead ray or a non-finite step: no step in that iteration.
+// Layout: one 16-lane group per (lens, field, wavelength), four per wave.  Lanes 0..8 trace tee ray g / 3 at offset
+// {0, +h, -h}[g % 3] each iteration, lane 9 the marginal ray once (when rs is not given); the results go round the
+// group by __shfl and every lane of it takes the same steps.  An iteration costs one trace of latency, not nine.
+constexpr int kAimGroup = 16;
+
+__global__ __launch_bounds__(64) void ray_aim_iter_kernel(int B, int F, int W, int K, const float *__restrict__ c,
+                                                          const float *__restrict__ t, const float *__restrict__ n,
+                                                          const float *__restrict__ n_d, const uint8_t *__restrict__ mask,
+                                                          const float *__restrict__ kappa, const float *__restrict__ poly,
+                                                          const uint8_t *__restrict__ kind, const float *__restrict__ z,
+                                                          const float *__restrict__ hfov, const float *__restrict__ fields,
+                                                          const float *__restrict__ epd, int allow_back, int n_iter,
+                                                          const float *__restrict__ tee_ref, const float *__restrict__ rs_in,
+                                                          float *__restrict__ x_scale, float *__restrict__ y_scale,
+                                                          float *__restrict__ y_offset)
+{
+    const int g = threadIdx.x % kAimGroup;
+    const int i = blockIdx.x * (64 / kAimGroup) + threadIdx.x / kAimGroup;
+    if (i >= B * F * W) return;                                          // whole groups only: the shuffles stay inside one
+    const int w = i % W, f = (i / W) % F, b = i / (W * F);
+    AimLens L;
+    L.K = K; L.W = W; L.allow_back = allow_back != 0;
+    L.c = c + (size_t)b * K; L.t = t + (size_t)b * K; L.n = n + (size_t)b * K * W; L.n_d = n_d + (size_t)b * K;
+    L.mask = mask + (size_t)b * K;
+    L.kind = kind ? kind + (size_t)b * K : nullptr;
+    L.kappa = kind ? kappa + (size_t)b * K : nullptr;
+    L.poly = kind ? poly + (size_t)b * K * 4 : nullptr;
+    const double z0 = (double)z[b], half = 0.5 * (double)epd[b];
+    const double cy0 = sin((double)(hfov[b] * fields[f]));               // the correctly rounded sine of the fp32 angle (assemble)
+    const double cyf = (double)(float)cy0;
+    double rs;
+    bool ok_m = true;
+    if (rs_in) {
+        rs = (double)rs_in[b];
+    } else {
+        double xs, rs_l = 0.0;
+        bool ok_l = false;
+        if (g == 9) ok_l = aim_trace(L, -1, 0.0, half, z0, 0.0, 0.0, xs, rs_l);   // compute_pupil_radius, as ray_aim_kernel
+        rs = __shfl(rs_l, 9, kAimGroup);
+        ok_m = __shfl((int)ok_l, 9, kAimGroup) != 0;
+    }
+    // reference points (bottom y, top y, sagittal x); the sagittal ray sits at the middle of the two meridional ones in y
+    // (what apply_vignetting makes of pupil y = 0), the meridional rays at x = 0
+    double p0[3] = {-1.0, 1.0, 1.0};
+    if (tee_ref) {
+        const float *tr = tee_ref + ((size_t)b * F + f) * 3;
+        p0[0] = (double)tr[0]; p0[1] = (double)tr[1]; p0[2] = (double)tr[2];
+    }
+    const double y_sag = 0.5 * (p0[0] + p0[1]);
+    const double h = 1e-4;
+    const int r = g / 3, v = g % 3;                                      // lanes 0..8: ray r at offset 0 / +h / -h
+    const double off = (v == 0) ? 0.0 : (v == 1 ? h : -h);
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < n_iter && ok_m; ++k) {                           // n_iter <= TL_MAX_AIM_ITER (host check)
+        double xo = 0.0, yo = 0.0;
+        bool ok = false;
+        if (g < 9) {
+            const double py_m = (r == 0) ? p0[0] + s[0] : p0[1] + s[1];          // (selects: no lane-indexed array)
+            const double px = (r == 2) ? p0[2] + s[2] : 0.0, py = (r == 2) ? y_sag : py_m;
+            const double ex = (r == 2) ? off : 0.0, ey = (r == 2) ? 0.0 : off;
+            ok = aim_trace(L, w, (px + ex) * half, (py + ey) * half, z0, 0.0, cyf, xo, yo);
+        }
+        double step[3];
+        for (int q = 0; q < 3; ++q) {
+            const double x0 = __shfl(xo, 3 * q, kAimGroup), y0 = __shfl(yo, 3 * q, kAimGroup);
+            const double xa = __shfl(xo, 3 * q + 1, kAimGroup), ya = __shfl(yo, 3 * q + 1, kAimGroup);
+            const double xb = __shfl(xo, 3 * q + 2, kAimGroup), yb = __shfl(yo, 3 * q + 2, kAimGroup);
+            const int ok3 = __shfl((int)ok, 3 * q, kAimGroup) & __shfl((int)ok, 3 * q + 1, kAimGroup) &
+                            __shfl((int)ok, 3 * q + 2, kAimGroup);
+            step[q] = 0.0;
+            if (!ok3) continue;
+            const double j = (k == 0) ? ((xa + ya) - (xb + yb)) / (2.0 * h * rs)   // the reference's d(xs_rel + ys_rel)
+                                      : ((q == 2) ? xa - xb : ya - yb) / (2.0 * h * rs);
+            const double pos = ((q == 2) ? x0 : y0) / rs;
+            const double d = -(pos - p0[q]) / j;
+            step[q] = (d - d == 0.0) ? d : 0.0;                           // non-finite -> no step
+        }
+        for (int q = 0; q < 3; ++q) s[q] = (k == 0) ? step[q] : s[q] + step[q];   // (s_1 = d_1 as is, a signed zero too)
+    }
+    if (g != 0) return;
+    // the affine map through (p0 -> p0 + s); with p0 = (-1, 1, 1) ray_aim_kernel's expressions, operation for operation
+    x_scale[i] = (float)((p0[2] + s[2]) / p0[2]);
+    y_scale[i] = (float)(((p0[1] + s[1]) - (p0[0] + s[0])) / (p0[1] - p0[0]));
+    y_offset[i] = (float)((p0[0] * s[1] - p0[1] * s[0]) / (p0[0] - p0[1]));
+}
+
 extern "C" {
 
 int tl_version(void) { return TL_ABI_VERSION; }
@@ -964,6 +1056,31 @@ int tl_ray_aim(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const
                        kappa, poly, surf_kind, z, hfov, fields, epd, allow_backward, x_scale, y_scale, y_offset);
     const int herr = (int)hipGetLastError();
     if (herr) return hip_fail(herr, "ray_aim_kernel launch");
+    return TL_OK;
+}
+
+int tl_ray_aim_iter(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const float *c, const float *t, const float *n,
+                    const float *n_d, const uint8_t *mask, const float *kappa, const float *poly, const uint8_t *surf_kind,
+                    const float *z, const float *hfov, const float *fields, const float *epd, int32_t allow_backward,
+                    int32_t n_iter, const float *tee_ref, const float *rs, float *x_scale, float *y_scale, float *y_offset,
+                    void *stream)
+{
+    if (B < 1 || F < 1 || W < 1 || K < 1 || K > TL_MAX_SURFACES || !c || !t || !n || !n_d || !mask || !z || !hfov || !fields ||
+        !epd || !x_scale || !y_scale || !y_offset)
+        return fail(TL_EINVAL, "tl_ray_aim_iter: bad argument");
+    if (n_iter < 1 || n_iter > TL_MAX_AIM_ITER)
+        return fail(TL_EINVAL, "tl_ray_aim_iter: n_iter must be in 1..TL_MAX_AIM_ITER");
+    if ((surf_kind != nullptr) != (kappa != nullptr) || (surf_kind != nullptr) != (poly != nullptr))
+        return fail(TL_EINVAL, "tl_ray_aim_iter: surf_kind, kappa and poly must be given together (or all NULL)");
+    const int64_t groups = (int64_t)B * F * W, per_block = 64 / kAimGroup;
+    if (groups > INT32_MAX / kAimGroup) return fail(TL_EINVAL, "tl_ray_aim_iter: B*F*W too large");
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    hipLaunchKernelGGL(ray_aim_iter_kernel, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(64), 0,
+                       (hipStream_t)stream, B, F, W, K, c, t, n, n_d, mask, kappa, poly, surf_kind, z, hfov, fields, epd,
+                       allow_backward, n_iter, tee_ref, rs, x_scale, y_scale, y_offset);
+    const int herr = (int)hipGetLastError();
+    if (herr) return hip_fail(herr, "ray_aim_iter_kernel launch");
     return TL_OK;
 }
 

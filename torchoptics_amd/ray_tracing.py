@@ -21,8 +21,9 @@ from .paraxial import (compute_last_curvature, compute_magnification, compute_pu
                        compute_pupil_radius, get_first_order, interface_propagation_abcd, reduce_abcd)
 
 _LINES = {'C': 656.3, 'd': 587.6, 'F': 486.1}
-# ray aiming through the fused kernel tl_ray_aim (GPU, fp32 lenses, 'real' mode, no vignetting function); False: the
-# reference's sequence of tensor ops (two traces + autograd), kept for CPU tensors, the other modes and as the checker
+# ray aiming through the fused kernel tl_ray_aim_iter (GPU, fp32 lenses; at n_ray_aiming_iter = 1 'real' mode without a
+# vignetting function only); False: the reference's sequence of tensor ops (two traces + autograd per step), kept for
+# fp64 / CPU tensors, the other N = 1 cases and as the checker
 _AIM_KERNEL = True
 
 
@@ -667,10 +668,12 @@ class RayTracer:
         return trace_skew(a['x'], a['y'], a['z'], a['cx'], a['cy'], a['c'], a['t'], a['mu'], a['mask'],
                           aggregate, self.allow_backward_rays, mode=self.arith, **extra)
 
-    def _ray_aiming_kernel(self, specs2stop, lens2stop, z=None):
-        """ray_aiming as ONE kernel (tl_ray_aim): marginal ray, the three tee rays with their Jacobian, the Newton step
-        and the affine pupil map, per (lens, field, wavelength) in fp64 registers -- instead of two eager traces, an
-        autograd pass and ~60 tensor ops (1.1 ms of host time per call for a 256-lens minibatch, 0.1 ms now)."""
+    def _ray_aiming_kernel(self, specs2stop, lens2stop, z=None, tee_ref=None, rs=None):
+        """ray_aiming as ONE kernel (tl_ray_aim_iter): marginal ray, the three tee rays with their Jacobian, the
+        n_ray_aiming_iter Newton steps and the affine pupil map, per (lens, field, wavelength) in fp64 registers --
+        instead of two eager traces, an autograd pass and ~60 tensor ops per step (1.1 ms of host time per call for a
+        256-lens minibatch, 0.1 ms now).  tee_ref [B,F,3] (vignetted tee points), rs [B] (stop radius): None = the
+        kernel's defaults (pupil (0,-1), (0,1), (1,0); the marginal ray)."""
         import ctypes as C
         from . import _lib
         from .lens_modeling import const_tensor
@@ -692,11 +695,12 @@ class RayTracer:
         hfov, epd = _dense(specs2stop.hfov.detach().float()), _dense(specs2stop.epd.detach().float())
         out = torch.empty((3, B, F, 1, W), dtype=torch.float32, device=dev)
         with ops._on_device(dev):
-            rc = _lib.lib().tl_ray_aim(dev.index, B, F, W, K, _lib.ptr(c), _lib.ptr(t), _lib.ptr(n), _lib.ptr(n_d), _lib.ptr(mask),
-                                       _lib.ptr(kap), _lib.ptr(pol), _lib.ptr(kind), _lib.ptr(z), _lib.ptr(hfov), _lib.ptr(fields),
-                                       _lib.ptr(epd), 1 if self.allow_backward_rays else 0, _lib.ptr(out[0]), _lib.ptr(out[1]),
-                                       _lib.ptr(out[2]), ops._stream_ptr(dev))
-        _lib.check(rc, "tl_ray_aim")
+            rc = _lib.lib().tl_ray_aim_iter(dev.index, B, F, W, K, _lib.ptr(c), _lib.ptr(t), _lib.ptr(n), _lib.ptr(n_d),
+                                            _lib.ptr(mask), _lib.ptr(kap), _lib.ptr(pol), _lib.ptr(kind), _lib.ptr(z), _lib.ptr(hfov),
+                                            _lib.ptr(fields), _lib.ptr(epd), 1 if self.allow_backward_rays else 0,
+                                            int(self.n_ray_aiming_iter), _lib.ptr(tee_ref), _lib.ptr(rs), _lib.ptr(out[0]),
+                                            _lib.ptr(out[1]), _lib.ptr(out[2]), ops._stream_ptr(dev))
+        _lib.check(rc, "tl_ray_aim_iter")
         x_scale, y_scale, y_offset = out[0], out[1], out[2]
 
         def remap(xp_rel, yp_rel):
@@ -722,49 +726,85 @@ class RayTracer:
 
     # -- ray aiming (ray_tracing_lite.py:129-208) ---------------------------------------------
     def ray_aiming(self, specs, lens, use_vig, front=None, z=None):
-        """One Newton step per iteration on the pupil coordinates of three 'tee' rays so that
-        they land on the stop where an ideal pupil would put them; returns the affine pupil
-        remap.  The Jacobian diagonal comes from the backward kernel's per-ray input grads.
+        """n_ray_aiming_iter Newton steps on the pupil coordinates of three 'tee' rays so that they land on the stop
+        where an ideal pupil would put them; returns the affine pupil remap through (reference points -> aimed ones).
+        Step 1 takes the reference's Jacobian d(xs_rel + ys_rel)/dp, steps >= 2 the stop coordinate's own partial
+        (DESIGN.md "Iterated ray aiming": the reference's text has no working N >= 2).
         `front`, `z`: lens.up_to_stop() and its pupil position [B] if the caller has them already (`lens` and `front`
         may then still be attached to a graph: nothing here differentiates through them)."""
+        from ._lib import TL_MAX_AIM_ITER
+        n_iter = int(self.n_ray_aiming_iter)
+        if n_iter > TL_MAX_AIM_ITER:
+            raise ValueError(f"n_ray_aiming_iter must be <= {TL_MAX_AIM_ITER}, got {n_iter}")
         if (lens.structure.stop_idx == 0).all():
             return lambda xp_rel, yp_rel: (xp_rel, yp_rel)
-        if self.n_ray_aiming_iter > 1:
-            raise NotImplementedError("n_ray_aiming_iter >= 2 fails in the reference as well (Appendix B4)")
+        if self.ray_aiming_mode not in ('real', 'paraxial'):
+            raise ValueError("ray_aiming_mode must be 'real' or 'paraxial'")
         specs2stop, lens2stop = specs.up_to_stop(), (lens.up_to_stop() if front is None else front)
-        if (self.ray_aiming_mode == 'real' and lens2stop.c.is_cuda and lens2stop.c.dtype == torch.float32
-                and not (use_vig and self.vig_fn is not None) and _AIM_KERNEL):
-            return self._ray_aiming_kernel(specs2stop, lens2stop, z)
+        vig = use_vig and self.vig_fn is not None
+        if lens2stop.c.is_cuda and lens2stop.c.dtype == torch.float32 and _AIM_KERNEL:
+            # N = 1: the kernel where tl_ray_aim ran ('real', no vignetting) -- the other N = 1 cases keep the op
+            # sequence below, so that no N = 1 result changes; N >= 2: every case
+            if self.ray_aiming_mode == 'real' and not vig:
+                return self._ray_aiming_kernel(specs2stop, lens2stop, z)
+            if n_iter > 1:
+                with torch.no_grad():
+                    rs = None
+                    if self.ray_aiming_mode == 'paraxial':
+                        rs = _dense((compute_magnification(lens2stop.detach()) * specs2stop.epd.detach() / 2).float())
+                    tee_ref = None
+                    if vig:
+                        xt0, yt0 = tee(None, self.default_device)
+                        shape = (len(lens), len(self.rel_fields), 3, 1)
+                        yv, xv = self._vignette(specs, yt0.expand(shape), xt0.expand(shape))
+                        tee_ref = torch.stack((yv[:, :, 0, 0], yv[:, :, 1, 0], xv[:, :, 2, 0]), dim=-1).float()
+                        tee_ref = _dense(tee_ref.expand(len(lens), len(self.rel_fields), 3))
+                return self._ray_aiming_kernel(specs2stop, lens2stop, z, tee_ref=tee_ref, rs=rs)
         if front is not None:
             lens2stop = lens2stop.detach()
         if self.ray_aiming_mode == 'paraxial':
             rs = (compute_magnification(lens2stop) * specs2stop.epd / 2).reshape(-1, 1, 1, 1)
-        elif self.ray_aiming_mode == 'real':
-            rs = compute_pupil_radius(specs2stop, lens2stop, default_device=self.default_device).reshape(-1, 1, 1, 1)
         else:
-            raise ValueError("ray_aiming_mode must be 'real' or 'paraxial'")
+            rs = compute_pupil_radius(specs2stop, lens2stop, default_device=self.default_device).reshape(-1, 1, 1, 1)
 
         xt0, yt0 = tee(None, self.default_device)
         shape = (len(lens), len(self.rel_fields), xt0.shape[2], len(self.wavelengths))
         xt_ref, yt_ref = xt0.expand(shape).clone(), yt0.expand(shape).clone()
         if use_vig and self.vig_fn is not None:
             yt_ref, xt_ref = self._vignette(specs, yt_ref, xt_ref)
-        with torch.enable_grad():
-            xt = xt_ref.clone().requires_grad_(True)
-            yt = yt_ref.clone().requires_grad_(True)
-            xs, ys, *_ = self.trace_rays(specs2stop, lens2stop, up_to_stop=True, use_vig=False, xy=(xt, yt))
-            xs_rel, ys_rel = xs / rs, ys / rs
-            # the reference back-propagates ones through xs_rel and then ys_rel into the same .grad
-            jx, jy = torch.autograd.grad(xs_rel.sum() + ys_rel.sum(), (xt, yt))
-        xs_rel, ys_rel, xt, yt = xs_rel.detach(), ys_rel.detach(), xt.detach(), yt.detach()
-        dx = -(xs_rel - xt_ref) / jx
-        dy = -(ys_rel - yt_ref) / jy
-        dx = torch.where(torch.isfinite(dx), dx, torch.zeros_like(dx))
-        dy = torch.where(torch.isfinite(dy), dy, torch.zeros_like(dy))
-        dx_s = dx[..., -1:, :]
-        dy_l, dy_u = dy[..., 0:1, :], dy[..., 1:2, :]
-        x_s = xt[..., -1:, :]
-        y_l, y_u = yt[..., 0:1, :], yt[..., 1:2, :]
+        # accumulated step of (x, y) per tee ray: only the sagittal x and the meridional y move
+        sx = torch.zeros_like(xt_ref)
+        sy = torch.zeros_like(yt_ref)
+        for k in range(n_iter):
+            with torch.enable_grad():
+                xt = (xt_ref + sx).detach().requires_grad_(True)
+                yt = (yt_ref + sy).detach().requires_grad_(True)
+                xs, ys, *_ = self.trace_rays(specs2stop, lens2stop, up_to_stop=True, use_vig=False, xy=(xt, yt))
+                xs_rel, ys_rel = xs / rs, ys / rs
+                if k == 0:
+                    # the reference back-propagates ones through xs_rel and then ys_rel into the same .grad
+                    jx, jy = torch.autograd.grad(xs_rel.sum() + ys_rel.sum(), (xt, yt))
+                else:
+                    # d xs/d xt of the sagittal ray and d ys/d yt of the meridional ones: every ray's outputs depend on
+                    # its own inputs only, so one pass seeded with xs_rel there and ys_rel here gives both partials
+                    sag = xt0 != 0
+                    jx, jy = torch.autograd.grad(torch.where(sag, xs_rel, torch.zeros_like(xs_rel)).sum()
+                                                 + torch.where(sag, torch.zeros_like(ys_rel), ys_rel).sum(), (xt, yt))
+            xs_rel, ys_rel = xs_rel.detach(), ys_rel.detach()
+            dx = -(xs_rel - xt_ref) / jx
+            dy = -(ys_rel - yt_ref) / jy
+            dx = torch.where(torch.isfinite(dx), dx, torch.zeros_like(dx))
+            dy = torch.where(torch.isfinite(dy), dy, torch.zeros_like(dy))
+            if n_iter == 1:
+                sx, sy = dx, dy                  # (the map below reads only the sagittal x and the meridional y steps)
+            else:
+                # only those move the rays traced by the next step: sagittal x (tee x = 1), meridional y (tee x = 0)
+                sx = sx + torch.where(xt0 != 0, dx, torch.zeros_like(dx))
+                sy = sy + torch.where(xt0 == 0, dy, torch.zeros_like(dy))
+        dx_s = sx[..., -1:, :]
+        dy_l, dy_u = sy[..., 0:1, :], sy[..., 1:2, :]
+        x_s = xt_ref[..., -1:, :]
+        y_l, y_u = yt_ref[..., 0:1, :], yt_ref[..., 1:2, :]
         y_scale = (y_u + dy_u - (y_l + dy_l)) / (y_u - y_l)
         y_offset = (y_l * dy_u - y_u * dy_l) / (y_l - y_u)
 
