@@ -61,10 +61,15 @@ int main(int argc, char **argv)
     HIP_OK(hipMalloc((void **)&g_z, 4)); HIP_OK(hipMalloc((void **)&g_cx, F * 4)); HIP_OK(hipMalloc((void **)&g_cy, F * 4));
     hipStream_t st;
     HIP_OK(hipStreamCreate(&st));
-    TL_OK_(tl_trace_fwd(&p, ox, oy, ocx, ocy, ok, back, nullptr, nullptr, mom, ws, wsz, st));
+    tl_rays rays = {};                 // blocks of named pointers: what is not assigned stays NULL = not wanted
+    rays.x = ox; rays.y = oy; rays.cx = ocx; rays.cy = ocy; rays.ok = ok; rays.back = back; rays.moments = mom;
+    TL_OK_(tl_trace_fwd(&p, &rays, ws, wsz, st));
     TL_OK_(tl_spot_rms(0, 1, F, (double)P * W, mom, rms, dmom, st));
-    TL_OK_(tl_trace_bwd(&p, nullptr, nullptr, nullptr, nullptr, dmom, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, ws, wsz, st));
+    tl_seeds seeds = {};
+    seeds.g_moments = dmom;
+    tl_grads grads = {};
+    grads.g_c = g_c; grads.g_t = g_t; grads.g_mu = g_mu; grads.g_z = g_z; grads.g_cx = g_cx; grads.g_cy = g_cy;
+    TL_OK_(tl_trace_bwd(&p, &seeds, &grads, ws, wsz, st));
     HIP_OK(hipStreamSynchronize(st));
     float h_rms, h_gc[3], h_gt[3], h_gmu[3];
     double h_mom[TL_NMOM];

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define TL_ABI_VERSION 14
+#define TL_ABI_VERSION 15
 #define TL_MAX_SURFACES 32       /* rows per lens the backward kernels are built for */
 #define TL_NMOM 10               /* per-field sums, see tl_trace_fwd */
 #define TL_MAX_POLY 4            /* even aspheric terms a4,a6,a8,a10 */
@@ -98,7 +98,7 @@ typedef struct tl_problem {
     uint8_t *cond_flags;         /* [B,F,W,P] bytes, nullable: the `ok` output with the conditioning flag -- 0 dead, 1 live, 2 live
                                     and ill-conditioned (smallest cos^2 of incidence or refraction below 0.01: the rays moment 9
                                     counts) -- WRITTEN by tl_trace_fwd (next to `ok`, which stays 0/1), READ by
-                                    tl_trace_bwd_from_outputs in place of ok_fwd.  With it, a launch that holds such rays is
+                                    tl_trace_bwd_from_outputs in place of fwd->ok.  With it, a launch that holds such rays is
                                     no longer handed to the checkpoint kernel as a whole: the walk-back differentiates the
                                     rays marked 1 and the checkpoint kernel exactly those marked 2 (waves without one skip
                                     their chunk); the two partial sums are added.  NULL: one ill-conditioned ray sends the
@@ -113,17 +113,19 @@ size_t      tl_problem_size(void);       /* sizeof(tl_problem): lets a foreign-l
 size_t tl_workspace_bytes(const tl_problem *p);
 
 /*
- * Forward trace: replaces the whole Python loop trace_skew (ray_tracing_lite.py:594-675 =
- * find_marching_distance_spherical :525-545, update_ray_coordinates :514-522,
- * reset_bad_rays :574-591, apply_snell_spherical :548-571, image-plane transfer :659-663).
- *   (shapes for B = 1; with a lens batch every output gains a leading B: [B,F,W,P], moments [B,F,TL_NMOM],
- *    stacks [3][S][B,F,W,P])
- *   x,y,cx,cy : [F,W,P] float  (any may be NULL = not wanted)
- *   ok,back   : [F,W,P] uint8  (nullable)
+ * The buffers of a trace call, as three blocks of named device pointers (ABI 15).  A caller zero-initialises a block and
+ * assigns the members it has; the library reads a block during the call only.  Shapes for B = 1; with a lens batch
+ * every per-ray array gains a leading B: [B,F,W,P], moments [B,F,TL_NMOM], stacks [3][S][B,F,W,P].
+ *
+ * tl_rays -- what tl_trace_fwd writes (every member nullable = not wanted), and what tl_trace_bwd_from_outputs reads again:
+ *   x,y,cx,cy : [F,W,P] float
+ *   ok,back   : [F,W,P] uint8
  *   opd       : [F,W,P] float  optical path length sum_k n_k d_k + n_S d_image from the pupil plane
- *               to the image plane, 0 for failed rays; needs p->n_index (nullable; extension; its gradient:
- *               `g_opd` of tl_trace_bwd)
- *   moments   : [F,TL_NMOM] double (nullable), per field over (w,p):
+ *               to the image plane, 0 for failed rays; needs p->n_index (extension; its gradient: tl_seeds.g_opd)
+ *   stacks    : [3][S][F,W,P] float (p->aggregate only): the per-surface stacks
+ *               z_RELU | theta_norm | theta_prime_norm that trace_skew(aggregate=True) returns
+ *               (their gradient: tl_seeds.g_stacks)
+ *   moments   : [F,TL_NMOM] double, per field over (w,p):
  *               0 sum y | 1 sum ok*y | 2 sum ok*y^2 | 3 sum ok | 4 sum x | 5 sum ok*x |
  *               6 sum ok*x^2 | 7 sum back | 8 sum q (p->aggregate only) |
  *               9 number of ILL-CONDITIONED live rays: smallest cos^2 of incidence / refraction along the
@@ -132,58 +134,92 @@ size_t tl_workspace_bytes(const tl_problem *p);
  *               q = per-ray sum over the surfaces of theta_norm + theta_prime_norm + z_RELU
  *               (ray_tracing_lite.py:641-657), NaN -> 0, i.e. sumQ * n_sequence of
  *               optics_simulator_lite.py:441-448.  All reduced in a fixed order (bitwise reproducible).
- *   stacks    : [3][S][F,W,P] float (nullable, p->aggregate only): the per-surface stacks
- *               z_RELU | theta_norm | theta_prime_norm that trace_skew(aggregate=True) returns
- *               (their gradient: `g_stacks` of tl_trace_bwd_stacks / tl_trace_bwd_from_outputs_stacks).
  */
-int tl_trace_fwd(const tl_problem *p,
-                 float *x, float *y, float *cx, float *cy, uint8_t *ok, uint8_t *back,
-                 float *opd, float *stacks, double *moments,
-                 void *workspace, size_t workspace_bytes, void *stream);
+typedef struct tl_rays {
+    float *x, *y, *cx, *cy;
+    uint8_t *ok, *back;
+    float *opd;
+    float *stacks;
+    double *moments;
+} tl_rays;
+
+/*
+ * tl_seeds -- the upstream gradients of a backward call, each nullable:
+ *   gx,gy,gcx,gcy : [F,W,P] upstream gradients of the per-ray outputs
+ *   g_moments     : [F,TL_NMOM] double upstream gradient of `moments`; the per-ray
+ *                   seed  gM0 + ok*(gM1 + 2*y*gM2)  (and the x analogue) is formed in-kernel;
+ *                   entry 8 seeds the penalty term when p->aggregate
+ *   g_opd         : [F,W,P] upstream gradient of the optical path length output (needs p->n_index and
+ *                   tl_grads.g_n_index).  OPD = sum_k n_k d_k + n_S d_image: it enters the adjoint of every marching distance
+ *                   and so reaches c, t, mu, z, cx, cy, kappa, poly, x_in, y_in; g_n_index [W,S+1] = d/d n_index
+ *   g_stacks      : [3][S][F,W,P] float, dense, in the layout of tl_rays.stacks: the upstream gradient of
+ *                   z_RELU | theta_norm | theta_prime_norm of every row and ray.
+ *                   Needs p->aggregate (TL_EINVAL, before any HIP call, otherwise).  Per ray r and row k:
+ *                     - ray ok after row k: theta and theta' are differentiated through cos^2 with the clamp conventions of
+ *                       the fused seed (entry 8 of g_moments), z_RELU passes the gradient where z > 0;
+ *                     - ray not ok after row k (parked): theta = theta' = 1 carry no gradient, z_RELU = max(-t_k, 0) gives
+ *                       d/dt_k only.
+ *                   It adds to entry 8 of g_moments: a loss may read both the fused sum and the stacks.  The routing is that of
+ *                   the penalty term (tl_trace_bwd_from_outputs: the walk-back for 3..20 rows, P >= 256, aspheric hits stored;
+ *                   the checkpoint kernel otherwise).  No host synchronisation: the calls can be recorded into a HIP graph.
+ */
+typedef struct tl_seeds {
+    const float *gx, *gy, *gcx, *gcy;
+    const double *g_moments;
+    const float *g_opd;
+    const float *g_stacks;
+} tl_seeds;
+
+/*
+ * tl_grads -- the gradient outputs of a backward call:
+ *   g_c,g_t [S], g_mu [W,S], g_z [1], g_cx,g_cy [F] : float, required, OVERWRITTEN (not accumulated); summed over the
+ *                   rays in fp64 in a fixed order and rounded once.  Lens batch: per lens, [B,S], [B,W,S], [B],
+ *                   [B,F] (and g_kappa [B,S], g_poly [B,S,4], g_n_index [B,W,S+1]); a lens never sees another's rays
+ *   g_kappa [S], g_poly [S,TL_MAX_POLY] : float (aspheric extension: required iff p->surf_kind)
+ *   g_n_index [W,S+1] : float, given together with tl_seeds.g_opd
+ *   g_x_in,g_y_in : [F,W,P] float per-ray input gradients (nullable; used by ray aiming,
+ *                   ray_tracing_lite.py:169-181)
+ */
+typedef struct tl_grads {
+    float *g_c, *g_t, *g_mu, *g_z, *g_cx, *g_cy;
+    float *g_kappa, *g_poly, *g_n_index;
+    float *g_x_in, *g_y_in;
+} tl_grads;
+
+/*
+ * Forward trace: replaces the whole Python loop trace_skew (ray_tracing_lite.py:594-675 =
+ * find_marching_distance_spherical :525-545, update_ray_coordinates :514-522,
+ * reset_bad_rays :574-591, apply_snell_spherical :548-571, image-plane transfer :659-663).
+ * Writes the members of `out` that are not NULL.  A NULL block pointer (here and below) is TL_EINVAL.
+ */
+int tl_trace_fwd(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Backward trace: replaces PyTorch autograd's replay of the recorded graph of trace_skew
  * (SURVEY 3.4).  Recomputes the forward per ray in registers, then sweeps the surfaces in
  * reverse.
- *   gx,gy,gcx,gcy : [F,W,P] upstream gradients of the per-ray outputs (each nullable)
- *   g_opd         : [F,W,P] upstream gradient of the optical path length output (nullable; needs p->n_index and
- *                   g_n_index).  OPD = sum_k n_k d_k + n_S d_image: it enters the adjoint of every marching distance
- *                   and so reaches c, t, mu, z, cx, cy, kappa, poly, x_in, y_in; g_n_index [W,S+1] = d/d n_index
- *   g_moments     : [F,TL_NMOM] double upstream gradient of `moments` (nullable); the per-ray
- *                   seed  gM0 + ok*(gM1 + 2*y*gM2)  (and the x analogue) is formed in-kernel;
- *                   entry 8 seeds the penalty term when p->aggregate
- *   g_c,g_t [S], g_mu [W,S], g_z [1], g_cx,g_cy [F] : float, OVERWRITTEN (not accumulated); summed over the
- *                   rays in fp64 in a fixed order and rounded once.  Lens batch: per lens, [B,S], [B,W,S], [B],
- *                   [B,F] (and g_kappa [B,S], g_poly [B,S,4], g_n_index [B,W,S+1]); a lens never sees another's rays
- *   g_kappa [S], g_poly [S,TL_MAX_POLY] : float, nullable (aspheric extension)
- *   g_x_in,g_y_in : [F,W,P] float per-ray input gradients (nullable; used by ray aiming,
- *                   ray_tracing_lite.py:169-181)
  */
-int tl_trace_bwd(const tl_problem *p,
-                 const float *gx, const float *gy, const float *gcx, const float *gcy,
-                 const double *g_moments, const float *g_opd,
-                 float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy,
-                 float *g_kappa, float *g_poly, float *g_n_index,
-                 float *g_x_in, float *g_y_in,
+int tl_trace_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out,
                  void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Backward trace WITHOUT re-tracing forwards: same gradients as tl_trace_bwd, computed by walking each ray
- * back from the forward kernel's own output (x, y, cx, cy, ok of tl_trace_fwd for this problem) -- undo
- * the refraction at surface k, intersect the incoming line with surface k-1, apply the adjoint step.
+ * back from the forward kernel's own output (`fwd`: x, y, cx, cy, ok, moments as tl_trace_fwd wrote them for this problem;
+ * back, opd, stacks are not read) -- undo the refraction at surface k, intersect the incoming line with surface k-1, apply
+ * the adjoint step.
  * No per-surface state is kept, so the kernel runs at twice the occupancy and needs no bit-exact
  * re-derivation of the forward; the reconstructed states differ from the forward's by rounding only,
  * which perturbs the gradients at the 1e-6 level (tested) -- except for ill-conditioned rays (moment 9 of
  * tl_trace_fwd), where it would reach 1e-4.  The call therefore always enqueues the checkpoint kernel of
  * tl_trace_bwd behind the walk-back kernel; both decide ON THE DEVICE which of them does the work (no host
  * synchronisation; the idle launch retires in microseconds).  The checkpoint kernel takes over when
- *   - `moments_fwd` (the forward's moments, nullable) counts an ill-conditioned live ray -- for exactly those rays when
- *     the forward left their flags in p->cond_flags (read in place of ok_fwd, which may then be NULL; the ok bytes given
+ *   - `fwd->moments` (nullable) counts an ill-conditioned live ray -- for exactly those rays when
+ *     the forward left their flags in p->cond_flags (read in place of fwd->ok, which may then be NULL; the ok bytes given
  *     otherwise must be 0 / 1 as tl_trace_fwd writes them), for the whole launch when it did not -- or
  *   - the walk-back met a non-finite adjoint (it then flags a word at the end of the workspace): the whole launch.
- * Pass `moments_fwd` whenever it is available: without it an ill-conditioned fan is walked back anyway.
- * allow_backward = 1 only, no OPD gradient (TL_EINVAL otherwise: use tl_trace_bwd).  Aspheric rows are walked
- * back too (g_kappa, g_poly as in tl_trace_bwd, required iff p->surf_kind).
+ * Pass `fwd->moments` whenever it is available: without it an ill-conditioned fan is walked back anyway.
+ * allow_backward = 1 only, no OPD gradient (TL_EINVAL for g->g_opd or out->g_n_index: use tl_trace_bwd).  Aspheric rows
+ * are walked back too (g_kappa, g_poly as in tl_trace_bwd, required iff p->surf_kind).
  * Workspace: tl_workspace_bytes(p); its contents need not be initialised.
  * Recorded into a HIP graph, the call is replayed with the same internal token: give the tl_trace_fwd of the same
  * step the SAME workspace with its full tl_workspace_bytes(p) (with or without `moments`) -- it clears the flag word, so
@@ -193,46 +229,8 @@ int tl_trace_bwd(const tl_problem *p,
  * checkpoint kernel in the same call; other lenses are handed to tl_trace_bwd as a whole.  Aspheric rows (ABI 13): with
  * p->asph_hits filled by tl_trace_fwd the hit on an aspheric row is read instead of searched.
  */
-int tl_trace_bwd_from_outputs(const tl_problem *p,
-                              const float *gx, const float *gy, const float *gcx, const float *gcy,
-                              const double *g_moments,
-                              const float *x_fwd, const float *y_fwd, const float *cx_fwd, const float *cy_fwd,
-                              const uint8_t *ok_fwd, const double *moments_fwd,
-                              float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy,
-                              float *g_kappa, float *g_poly,
-                              float *g_x_in, float *g_y_in,
+int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_rays *fwd, const tl_grads *out,
                               void *workspace, size_t workspace_bytes, void *stream);
-
-/*
- * The two backward calls above with a gradient for the per-surface penalty stacks (ABI 14): after `g_stacks` the
- * arguments are exactly theirs, and tl_trace_bwd / tl_trace_bwd_from_outputs are these calls with g_stacks = NULL.
- *   g_stacks : [3][S][F,W,P] float (nullable; [3][S][B,F,W,P] for a lens batch), dense, in the layout of tl_trace_fwd's
- *              `stacks` output: the upstream gradient of z_RELU | theta_norm | theta_prime_norm of every row and ray.
- *              Needs p->aggregate (TL_EINVAL, before any HIP call, otherwise).  Per ray r and row k:
- *                - ray ok after row k: theta and theta' are differentiated through cos^2 with the clamp conventions of
- *                  the fused seed (entry 8 of g_moments), z_RELU passes the gradient where z > 0;
- *                - ray not ok after row k (parked): theta = theta' = 1 carry no gradient, z_RELU = max(-t_k, 0) gives
- *                  d/dt_k only.
- *              It adds to entry 8 of g_moments: a loss may read both the fused sum and the stacks.  The routing is that of
- *              the penalty term (tl_trace_bwd_from_outputs: the walk-back for 3..20 rows, P >= 256, aspheric hits stored;
- *              the checkpoint kernel otherwise).  No host synchronisation: the calls can be recorded into a HIP graph.
- */
-int tl_trace_bwd_stacks(const tl_problem *p, const float *g_stacks,
-                        const float *gx, const float *gy, const float *gcx, const float *gcy,
-                        const double *g_moments, const float *g_opd,
-                        float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy,
-                        float *g_kappa, float *g_poly, float *g_n_index,
-                        float *g_x_in, float *g_y_in,
-                        void *workspace, size_t workspace_bytes, void *stream);
-int tl_trace_bwd_from_outputs_stacks(const tl_problem *p, const float *g_stacks,
-                                     const float *gx, const float *gy, const float *gcx, const float *gcy,
-                                     const double *g_moments,
-                                     const float *x_fwd, const float *y_fwd, const float *cx_fwd, const float *cy_fwd,
-                                     const uint8_t *ok_fwd, const double *moments_fwd,
-                                     float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy,
-                                     float *g_kappa, float *g_poly,
-                                     float *g_x_in, float *g_y_in,
-                                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Spot moments of arbitrary per-ray tensors (same TL_NMOM layout): the reduction inside
@@ -348,16 +346,14 @@ int tl_aim_fan(int32_t device, int32_t B, int32_t F, int32_t W, int32_t P, const
  * untuned kernels (one ray per lane, rolled loops) for reference-quality numbers on the GPU, not for speed.
  * `p` is a tl_problem whose float-typed pointers (x_in, y_in, z, cx, cy, c, t, mu, kappa, poly) POINT AT DOUBLES, same
  * shapes and strides (in elements); mask / surf_kind stay uint8; aggregate must be 0, n_index / asph_hits are ignored.
- * Outputs and gradients as in tl_trace_fwd / tl_trace_bwd with double instead of float (moments [B,F,TL_NMOM] as there,
- * entry 8 = 0).  Workspace: tl_workspace_bytes_f64(p).
+ * The blocks are read the same way: their float-typed members point at doubles (moments [B,F,TL_NMOM] as in tl_trace_fwd,
+ * entry 8 = 0).  Members with no meaning here -- opd, stacks, g_opd, g_stacks, g_n_index -- must be NULL (TL_EINVAL): no
+ * penalty term and no path length in double precision.  Workspace: tl_workspace_bytes_f64(p).
  */
 size_t tl_workspace_bytes_f64(const tl_problem *p);
-int tl_trace_fwd_f64(const tl_problem *p, double *x, double *y, double *cx, double *cy, uint8_t *ok, uint8_t *back,
-                     double *moments, void *workspace, size_t workspace_bytes, void *stream);
-int tl_trace_bwd_f64(const tl_problem *p, const double *gx, const double *gy, const double *gcx, const double *gcy,
-                     const double *g_moments, double *g_c, double *g_t, double *g_mu, double *g_z, double *g_cx, double *g_cy,
-                     double *g_kappa, double *g_poly, double *g_x_in, double *g_y_in, void *workspace, size_t workspace_bytes,
-                     void *stream);
+int tl_trace_fwd_f64(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream);
+int tl_trace_bwd_f64(const tl_problem *p, const tl_seeds *g, const tl_grads *out,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

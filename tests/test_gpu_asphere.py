@@ -258,8 +258,8 @@ def test_opd_gradient_needs_n_index_and_both_pointers(ta):
     g = torch.zeros(F * W * P, device=DEV)
     outs = [torch.zeros(n, device=DEV) for n in (S, S, W * S, 1, F, F)]
     ws = torch.zeros(_lib.lib().tl_workspace_bytes(C.byref(prob)), dtype=torch.uint8, device=DEV)
-    rc = _lib.lib().tl_trace_bwd(C.byref(prob), None, _lib.ptr(g), None, None, None, _lib.ptr(g), *[_lib.ptr(o) for o in outs],
-                                 None, None, None, None, None, _lib.ptr(ws), ws.numel(), None)
+    grads = _lib.grads(g_c=outs[0], g_t=outs[1], g_mu=outs[2], g_z=outs[3], g_cx=outs[4], g_cy=outs[5])
+    rc = _lib.lib().tl_trace_bwd(C.byref(prob), _lib.seeds(gy=g, g_opd=g), grads, _lib.ptr(ws), ws.numel(), None)
     assert rc == _lib.TL_EINVAL if hasattr(_lib, "TL_EINVAL") else rc == -1        # g_opd without g_n_index
 
 

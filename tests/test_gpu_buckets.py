@@ -66,13 +66,14 @@ def test_cabi_error_codes(ta):
     from torchoptics_amd import _lib
     lib = _lib.lib()
     p = _lib.tl_problem()
-    assert lib.tl_trace_fwd(None, *([None] * 9), None, 0, None) == -1
+    none = _lib.rays()                                                              # a block that asks for no output
+    assert lib.tl_trace_fwd(None, none, None, 0, None) == -1
     assert b"NULL" in lib.tl_last_error()
     p.F, p.P, p.W, p.S, p.device = 1, 64, 1, 40, 0
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 9), None, 0, None) == -1
+    assert lib.tl_trace_fwd(C.byref(p), none, None, 0, None) == -1
     assert b"TL_MAX_SURFACES" in lib.tl_last_error()
     p.S = 3
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 9), None, 0, None) == -1       # required pointers are NULL
+    assert lib.tl_trace_fwd(C.byref(p), none, None, 0, None) == -1       # required pointers are NULL
     buf = torch.zeros(64, device=DEV)
     m8 = torch.ones(8, dtype=torch.uint8, device=DEV)
     for f in ("x_in", "y_in", "z", "cx", "cy", "c", "t", "mu"):
@@ -80,17 +81,18 @@ def test_cabi_error_codes(ta):
     p.mask = m8.data_ptr()
     p.xs_p = p.ys_p = 1
     p.mode = 7
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 9), None, 0, None) == -1 and b"mode" in lib.tl_last_error()
+    assert lib.tl_trace_fwd(C.byref(p), none, None, 0, None) == -1 and b"mode" in lib.tl_last_error()
     p.mode = 0
     mom = torch.zeros(1, _lib.TL_NMOM, dtype=torch.float64, device=DEV)
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 8), _lib.ptr(mom), None, 0, None) == -3      # workspace too small
+    assert lib.tl_trace_fwd(C.byref(p), _lib.rays(moments=mom), None, 0, None) == -3             # workspace too small
+    assert lib.tl_trace_fwd(C.byref(p), None, None, 0, None) == -1 and b"NULL" in lib.tl_last_error()   # no block at all
     p.surf_kind = m8.data_ptr()                                                     # kappa / poly missing
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 9), None, 0, None) == -1
+    assert lib.tl_trace_fwd(C.byref(p), none, None, 0, None) == -1
     p.surf_kind = None
     p.B = -1                                                                        # lens batch: B >= 0, B*F*W <= 65535
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 9), None, 0, None) == -1 and b"B must" in lib.tl_last_error()
+    assert lib.tl_trace_fwd(C.byref(p), none, None, 0, None) == -1 and b"B must" in lib.tl_last_error()
     p.B, p.F = 700, 100
-    assert lib.tl_trace_fwd(C.byref(p), *([None] * 9), None, 0, None) == -1 and b"65535" in lib.tl_last_error()
+    assert lib.tl_trace_fwd(C.byref(p), none, None, 0, None) == -1 and b"65535" in lib.tl_last_error()
     p.B, p.F = 0, 1                                                                 # B = 0 is read as one lens
     assert lib.tl_workspace_bytes(C.byref(p)) > 0
     torch.cuda.synchronize()
@@ -269,8 +271,8 @@ def test_forward_without_moments_clears_the_walk_back_flag_word(ta):
     outs = [torch.empty((1, F, W, P), dtype=torch.float32, device=DEV) for _ in range(4)]
     flags = [torch.empty((1, F, W, P), dtype=torch.uint8, device=DEV) for _ in range(2)]
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rc = lib.tl_trace_fwd(C.byref(prob), *[_lib.ptr(o) for o in outs], *[_lib.ptr(f) for f in flags], None, None, None,
-                          _lib.ptr(ws), ws.numel(), st)
+    out = _lib.rays(x=outs[0], y=outs[1], cx=outs[2], cy=outs[3], ok=flags[0], back=flags[1])
+    rc = lib.tl_trace_fwd(C.byref(prob), out, _lib.ptr(ws), ws.numel(), st)
     assert rc == 0, lib.tl_last_error()
     torch.cuda.synchronize()
     word = ws[n - 64:n - 60].cpu().numpy().view(np.uint32)[0]

@@ -127,7 +127,7 @@ def test_split_backward_with_the_penalty_term_and_aspheric_rows(ta, asph):
 
 def test_flag_bytes_and_the_c_abi_with_and_without_them(ta):
     """tl_trace_fwd writes cond_flags = ok + (ill-conditioned ? 1 : 0) per ray; tl_trace_bwd_from_outputs reads them in
-    place of ok_fwd (which may then be NULL).  Without them the whole launch goes to the checkpoint kernel: the bits of
+    place of fwd->ok (which may then be NULL).  Without them the whole launch goes to the checkpoint kernel: the bits of
     tl_trace_bwd.  With them the result differs in the last bits only."""
     from torchoptics_amd import _lib, ops
     ins, mask = _g5()
@@ -151,7 +151,8 @@ def test_flag_bytes_and_the_c_abi_with_and_without_them(ta):
     mom = torch.empty((F, _lib.TL_NMOM), dtype=torch.float64, device=DEV)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     P_ = _lib.ptr
-    rc = lib.tl_trace_fwd(C.byref(prob), *[P_(o) for o in outs], *[P_(f) for f in flags], None, None, P_(mom), P_(ws), ws.numel(), st)
+    out = _lib.rays(x=outs[0], y=outs[1], cx=outs[2], cy=outs[3], ok=flags[0], back=flags[1], moments=mom)
+    rc = lib.tl_trace_fwd(C.byref(prob), out, P_(ws), ws.numel(), st)
     assert rc == 0, lib.tl_last_error()
     n_ill = int(mom[:, 9].sum().item())
     assert n_ill > 0
@@ -162,22 +163,25 @@ def test_flag_bytes_and_the_c_abi_with_and_without_them(ta):
     res = {}
     for tag, pr, okp in (("flags", prob, None), ("flags_and_ok", prob, flags[0]), ("no_flags", prob0, flags[0]), ("bwd", prob0, None)):
         g = [torch.zeros(n, device=DEV) for n in (S, S, W * S, 1, F, F)]
+        seeds = _lib.seeds(g_moments=gmom)
+        grads = _lib.grads(g_c=g[0], g_t=g[1], g_mu=g[2], g_z=g[3], g_cx=g[4], g_cy=g[5])
         if tag == "bwd":
-            rc = lib.tl_trace_bwd(C.byref(pr), None, None, None, None, P_(gmom), None, *[P_(q) for q in g], None, None, None,
-                                  None, None, P_(ws), ws.numel(), st)
+            rc = lib.tl_trace_bwd(C.byref(pr), seeds, grads, P_(ws), ws.numel(), st)
         else:
-            rc = lib.tl_trace_bwd_from_outputs(C.byref(pr), None, None, None, None, P_(gmom), *[P_(o) for o in outs], P_(okp),
-                                               P_(mom), *[P_(q) for q in g], None, None, None, None, P_(ws), ws.numel(), st)
+            fwd = _lib.rays(x=outs[0], y=outs[1], cx=outs[2], cy=outs[3], ok=okp, moments=mom)
+            rc = lib.tl_trace_bwd_from_outputs(C.byref(pr), seeds, fwd, grads, P_(ws), ws.numel(), st)
         assert rc == 0, (tag, lib.tl_last_error())
         res[tag] = torch.cat([q.reshape(-1) for q in g])
     assert torch.equal(res["no_flags"], res["bwd"])
     assert torch.equal(res["flags"], res["flags_and_ok"])
     assert not torch.equal(res["flags"], res["bwd"])                           # the walk-back really took the other rays
     assert rel_l2(res["flags"].cpu().numpy(), res["bwd"].cpu().numpy()) < 1e-5
-    # ok_fwd is only optional when the flags are there
+    # fwd->ok is only optional when the flags are there
     g = [torch.zeros(n, device=DEV) for n in (S, S, W * S, 1, F, F)]
-    rc = lib.tl_trace_bwd_from_outputs(C.byref(prob0), None, None, None, None, P_(gmom), *[P_(o) for o in outs], None,
-                                       P_(mom), *[P_(q) for q in g], None, None, None, None, P_(ws), ws.numel(), st)
+    fwd = _lib.rays(x=outs[0], y=outs[1], cx=outs[2], cy=outs[3], moments=mom)
+    rc = lib.tl_trace_bwd_from_outputs(C.byref(prob0), _lib.seeds(g_moments=gmom), fwd,
+                                       _lib.grads(g_c=g[0], g_t=g[1], g_mu=g[2], g_z=g[3], g_cx=g[4], g_cy=g[5]),
+                                       P_(ws), ws.numel(), st)
     assert rc != 0
 
 

@@ -1,6 +1,6 @@
 """
-Gradients through the per-surface penalty stacks of trace_skew(aggregate=True) (ABI 14: tl_trace_bwd_stacks,
-tl_trace_bwd_from_outputs_stacks).
+Gradients through the per-surface penalty stacks of trace_skew(aggregate=True) (the g_stacks member of the tl_seeds block of
+tl_trace_bwd / tl_trace_bwd_from_outputs).
 
 The lists z_RELU, theta_norm, theta_prime_norm are graph tensors, as in the reference: any function of them
 back-propagates through the backward kernels with one seed per ray, row and term (kPenRay: trace_bwd_inv_unrolled_stk_kernel

@@ -185,6 +185,29 @@ def test_cabi_library_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.tl_problem) == dll.tl_problem_size() == 248
 
 
+def test_pointer_blocks_have_the_members_of_the_header_in_order():
+    """tl_rays / tl_seeds / tl_grads: the member names parsed from include/tl_trace.h, in order, are the _fields_ of the
+    ctypes classes, and every member is one pointer (a swapped pair of members has the same sizeof: this catches it)."""
+    import ctypes
+    from torchoptics_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "tl_trace.h")).read()
+    for name, n_members in (("tl_rays", 9), ("tl_seeds", 7), ("tl_grads", 11)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S)
+        assert body, name
+        members = []
+        for decl in re.sub(r"/\*.*?\*/", "", body.group(1), flags=re.S).split(";"):
+            if not decl.strip():
+                continue
+            m = re.fullmatch(r"\s*(?:const\s+)?(?:float|double|uint8_t)\s+(\*\w+(?:\s*,\s*\*\w+)*)\s*", decl)
+            assert m, (name, decl)                        # pointers only: `T *a, *b`
+            members += [w.strip().lstrip("*") for w in m.group(1).split(",")]
+        cls = getattr(_lib, name)
+        assert len(members) == n_members, (name, members)
+        assert [f for f, _ in cls._fields_] == members, name
+        assert all(ctypes.sizeof(t) == ctypes.sizeof(ctypes.c_void_p) for _, t in cls._fields_), name
+        assert ctypes.sizeof(cls) == n_members * ctypes.sizeof(ctypes.c_void_p), name
+
+
 def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     """tl_unsup_loss / tl_unsup_loss_bwd / tl_aim_fan check their arguments first: TL_EINVAL and a message, no HIP call
     (so this runs without a GPU); the scan map of the penalty walk-back is part of tl_workspace_bytes."""

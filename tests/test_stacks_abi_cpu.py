@@ -1,14 +1,14 @@
 """
-The C-ABI side of the differentiable penalty stacks (ABI 14), without a GPU: the two backward entry points that take a
-gradient of the per-surface stacks are declared and exported, and a stack gradient without the penalty term is refused
-before any device call.
+The C-ABI side of the differentiable penalty stacks, without a GPU: the gradient of the per-surface stacks is a member of
+the tl_seeds block both backward entry points take (ABI 15; ABI 14 had two twin entry points for it), and a stack gradient
+without the penalty term is refused before any device call.
 """
 import ctypes as C
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("tl_trace_bwd_stacks", "tl_trace_bwd_from_outputs_stacks")
+GONE = ("tl_trace_bwd" + "_stacks", "tl_trace_bwd_from_outputs" + "_stacks")     # the twins of ABI 14
 EINVAL = -1                                           # TL_EINVAL (include/tl_trace.h)
 
 
@@ -23,40 +23,41 @@ def _problem(_lib, aggregate):
 
 
 def test_stack_entry_points_are_declared_and_exported():
+    """g_stacks is a member of tl_seeds in the header and in _lib; the ABI-14 twins are neither declared nor exported."""
     from torchoptics_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "tl_trace.h")).read()
     declared = set(re.findall(r"\b(tl_[a-z0-9_]+)\s*\(", hdr))
     dll = _lib.lib()
-    for name in NEW:
-        assert name in declared and name in _lib.EXPORTS, name
-        assert hasattr(dll, name), name
-    # after g_stacks, exactly the argument lists of the existing two calls
-    for name, base in zip(NEW, ("tl_trace_bwd", "tl_trace_bwd_from_outputs")):
-        args, base_args = _lib._SIGNATURES[name][1], _lib._SIGNATURES[base][1]
-        assert [args[0]] + args[2:] == base_args, name
+    body = re.search(r"typedef struct tl_seeds \{(.*?)\} tl_seeds;", hdr, re.S)
+    assert body and re.search(r"\bconst float \*g_stacks;", body.group(1))
+    assert "g_stacks" in [n for n, _ in _lib.tl_seeds._fields_]
+    for name in GONE:
+        assert name not in declared and name not in _lib.EXPORTS, name
+        assert not hasattr(dll, name), name
+    # both backward calls take the block
+    for name in ("tl_trace_bwd", "tl_trace_bwd_from_outputs"):
+        assert name in declared and name in _lib.EXPORTS and hasattr(dll, name), name
+        assert _lib._SIGNATURES[name][1][1] is C.POINTER(_lib.tl_seeds), name
 
 
 def test_abi_version_and_problem_layout():
     from torchoptics_amd import _lib
     dll = _lib.lib()
-    assert dll.tl_version() == _lib.TL_ABI_VERSION == 14
+    assert dll.tl_version() == _lib.TL_ABI_VERSION == 15
     assert dll.tl_problem_size() == C.sizeof(_lib.tl_problem) == 248
 
 
 def test_stack_gradient_without_aggregate_is_refused_before_any_device_call():
     from torchoptics_amd import _lib
     dll = _lib.lib()
-    one = C.c_void_p(8)
     p = _problem(_lib, aggregate=0)
     ws = C.c_void_p(16)
-    # g_stacks, gx, gy, gcx, gcy, g_moments, g_opd, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly, g_n, g_xin, g_yin
-    rc = dll.tl_trace_bwd_stacks(C.byref(p), one, None, None, None, None, one, None, one, one, one, one, one, one,
-                                 None, None, None, None, None, ws, 1 << 30, None)
+    g = _lib.tl_seeds(g_moments=8, g_stacks=8)
+    out = _lib.tl_grads(g_c=8, g_t=8, g_mu=8, g_z=8, g_cx=8, g_cy=8)
+    rc = dll.tl_trace_bwd(C.byref(p), g, out, ws, 1 << 30, None)
     assert rc == EINVAL
     assert b"g_stacks" in dll.tl_last_error()
-    # g_stacks, gx, gy, gcx, gcy, g_moments, x, y, cx, cy, ok, moments_fwd, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa,
-    # g_poly, g_xin, g_yin
-    rc = dll.tl_trace_bwd_from_outputs_stacks(C.byref(p), one, None, None, None, None, one, one, one, one, one, one, None,
-                                              one, one, one, one, one, one, None, None, None, None, ws, 1 << 30, None)
+    fwd = _lib.tl_rays(x=8, y=8, cx=8, cy=8, ok=8)
+    rc = dll.tl_trace_bwd_from_outputs(C.byref(p), g, fwd, out, ws, 1 << 30, None)
     assert rc == EINVAL
     assert b"g_stacks" in dll.tl_last_error()

@@ -90,22 +90,21 @@ def main():
             f.restype, f.argtypes = res, argt
         libs[name] = dll
     P_ = _lib.ptr
-    ak, ap_ = (P_(g_kap), P_(g_pol)) if asph else (None, None)
+    rays = _lib.rays(x=outs[0], y=outs[1], cx=outs[2], cy=outs[3], ok=flags[0], back=flags[1], moments=mom)
+    seeds = _lib.seeds(g_moments=gmom)
+    grads = _lib.grads(g_c=g_c, g_t=g_t, g_mu=g_mu, g_z=g_z, g_cx=g_cx, g_cy=g_cy,
+                       g_kappa=g_kap if asph else None, g_poly=g_pol if asph else None)
 
     def fwd(dll):
-        rc = dll.tl_trace_fwd(C.byref(prob), *[P_(o) for o in outs], *[P_(f) for f in flags], None, None, P_(mom), P_(ws),
-                              ws.numel(), st)
+        rc = dll.tl_trace_fwd(C.byref(prob), rays, P_(ws), ws.numel(), st)
         assert rc == 0, dll.tl_last_error()
 
     def bwd(dll):
-        rc = dll.tl_trace_bwd(C.byref(prob), None, None, None, None, P_(gmom), None, P_(g_c), P_(g_t), P_(g_mu),
-                              P_(g_z), P_(g_cx), P_(g_cy), ak, ap_, None, None, None, P_(ws), ws.numel(), st)
+        rc = dll.tl_trace_bwd(C.byref(prob), seeds, grads, P_(ws), ws.numel(), st)
         assert rc == 0, dll.tl_last_error()
 
     def bwd_inv(dll):
-        rc = dll.tl_trace_bwd_from_outputs(C.byref(prob), None, None, None, None, P_(gmom), P_(outs[0]), P_(outs[1]),
-                                           P_(outs[2]), P_(outs[3]), P_(flags[0]), P_(mom), P_(g_c), P_(g_t), P_(g_mu),
-                                           P_(g_z), P_(g_cx), P_(g_cy), ak, ap_, None, None, P_(ws), ws.numel(), st)
+        rc = dll.tl_trace_bwd_from_outputs(C.byref(prob), seeds, rays, grads, P_(ws), ws.numel(), st)
         assert rc == 0, dll.tl_last_error()
 
     skip = set(a.skip.split(",")) if a.skip else set()

@@ -29,7 +29,8 @@ for wl in ("cfg3a", "cfg3s"):
         mom = torch.empty((F, _lib.TL_NMOM), dtype=torch.float64, device=dev)
         outs = [torch.empty((1, F, W, P), dtype=torch.float32, device=dev) for _ in range(4)]
         fl = [torch.empty((1, F, W, P), dtype=torch.uint8, device=dev) for _ in range(2)]
-        assert dll.tl_trace_fwd(C.byref(prob), *[_lib.ptr(o) for o in outs], *[_lib.ptr(f) for f in fl], None, None, _lib.ptr(mom), _lib.ptr(ws), ws.numel(), st) == 0
+        rays = _lib.rays(x=outs[0], y=outs[1], cx=outs[2], cy=outs[3], ok=fl[0], back=fl[1], moments=mom)
+        assert dll.tl_trace_fwd(C.byref(prob), rays, _lib.ptr(ws), ws.numel(), st) == 0
         torch.cuda.synchronize()
         M = mom[0].cpu(); n = P * W
         m = M[0] / n
@@ -43,7 +44,8 @@ for wl in ("cfg3a", "cfg3s"):
     o64 = [torch.empty((1, F, W, P), dtype=torch.float64, device=dev) for _ in range(4)]
     f64 = [torch.empty((1, F, W, P), dtype=torch.uint8, device=dev) for _ in range(2)]
     lib = _lib.lib()
-    assert lib.tl_trace_fwd_f64(C.byref(prob64), *[_lib.ptr(o) for o in o64], *[_lib.ptr(f) for f in f64], _lib.ptr(mom64), _lib.ptr(ws), ws.numel(), st) == 0
+    rays64 = _lib.rays(x=o64[0], y=o64[1], cx=o64[2], cy=o64[3], ok=f64[0], back=f64[1], moments=mom64)
+    assert lib.tl_trace_fwd_f64(C.byref(prob64), rays64, _lib.ptr(ws), ws.numel(), st) == 0
     torch.cuda.synchronize()
     M = mom64[0].cpu(); m = M[0] / n
     rms64 = float(torch.sqrt((M[2] - 2 * m * M[1] + m * m * M[3]) / n))

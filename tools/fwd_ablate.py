@@ -27,7 +27,8 @@ for rnd in range(8):
     for k, (o, f, m) in variants.items():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        rc = lib.tl_trace_fwd(C.byref(prob), *[P_(t) for t in o], *[P_(t) for t in f], None, None, P_(m), P_(ws), ws.numel(), st)
+        rays = _lib.rays(x=o[0], y=o[1], cx=o[2], cy=o[3], ok=f[0], back=f[1], moments=m)
+        rc = lib.tl_trace_fwd(C.byref(prob), rays, P_(ws), ws.numel(), st)
         e1.record(); torch.cuda.synchronize(); assert rc == 0
         if rnd: res[k].append(e0.elapsed_time(e1))
 for k, v in res.items():

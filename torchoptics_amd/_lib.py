@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TORCHOPTICS_AMD_LIB: another build of the same library (an A/B variant written by build.build_library(tag=...))
 LIB_PATH = os.environ.get("TORCHOPTICS_AMD_LIB") or os.path.join(_HERE, "libtltrace.so")
 
-TL_ABI_VERSION = 14
+TL_ABI_VERSION = 15
 TL_NMOM = 10
 TL_MAX_SURFACES = 32
 TL_MAX_POLY = 4
@@ -38,20 +38,49 @@ class tl_problem(C.Structure):
     ]
 
 
+_VP = C.c_void_p
+
+
+# the trace calls' buffers as blocks of named device pointers (tl_trace.h); member order is the header's
+class tl_rays(C.Structure):
+    _fields_ = [(n, _VP) for n in ("x", "y", "cx", "cy", "ok", "back", "opd", "stacks", "moments")]
+
+
+class tl_seeds(C.Structure):
+    _fields_ = [(n, _VP) for n in ("gx", "gy", "gcx", "gcy", "g_moments", "g_opd", "g_stacks")]
+
+
+class tl_grads(C.Structure):
+    _fields_ = [(n, _VP) for n in ("g_c", "g_t", "g_mu", "g_z", "g_cx", "g_cy", "g_kappa", "g_poly", "g_n_index",
+                                   "g_x_in", "g_y_in")]
+
+
+def _from_tensors(cls):
+    def make(**tensors):
+        """A block whose named members point at the given tensors (None / unnamed -> NULL).  It holds no reference:
+        the caller keeps the tensors alive until the call has returned."""
+        unknown = set(tensors) - {n for n, _ in cls._fields_}
+        if unknown:
+            raise TypeError(f"{cls.__name__} has no member {sorted(unknown)}")
+        return cls(**{n: t.data_ptr() for n, t in tensors.items() if t is not None})
+    return make
+
+
+rays, seeds, grads = _from_tensors(tl_rays), _from_tensors(tl_seeds), _from_tensors(tl_grads)
+
 _lock = threading.Lock()
 _lib = None
 
-_VP = C.c_void_p
+_P, _R, _S, _G = C.POINTER(tl_problem), C.POINTER(tl_rays), C.POINTER(tl_seeds), C.POINTER(tl_grads)
+_WS = [_VP, C.c_size_t, _VP]        # workspace, workspace_bytes, stream
 _SIGNATURES = {
     "tl_version": (C.c_int, []),
     "tl_last_error": (C.c_char_p, []),
     "tl_problem_size": (C.c_size_t, []),
-    "tl_workspace_bytes": (C.c_size_t, [C.POINTER(tl_problem)]),
-    "tl_trace_fwd": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 9 + [_VP, C.c_size_t, _VP]),
-    "tl_trace_bwd": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 17 + [_VP, C.c_size_t, _VP]),
-    "tl_trace_bwd_from_outputs": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 21 + [_VP, C.c_size_t, _VP]),
-    "tl_trace_bwd_stacks": (C.c_int, [C.POINTER(tl_problem), _VP] + [_VP] * 17 + [_VP, C.c_size_t, _VP]),
-    "tl_trace_bwd_from_outputs_stacks": (C.c_int, [C.POINTER(tl_problem), _VP] + [_VP] * 21 + [_VP, C.c_size_t, _VP]),
+    "tl_workspace_bytes": (C.c_size_t, [_P]),
+    "tl_trace_fwd": (C.c_int, [_P, _R] + _WS),
+    "tl_trace_bwd": (C.c_int, [_P, _S, _G] + _WS),
+    "tl_trace_bwd_from_outputs": (C.c_int, [_P, _S, _R, _G] + _WS),
     "tl_spot_moments": (C.c_int, [C.c_int32] * 4 + [_VP] * 3 + [C.c_int64] * 3 + [_VP, _VP, C.c_size_t, _VP]),
     "tl_spot_rms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP, _VP, _VP]),
     "tl_unsup_loss": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP, C.c_double, C.c_float, _VP, _VP, _VP, _VP, _VP]),
@@ -60,9 +89,9 @@ _SIGNATURES = {
     "tl_aim_fan": (C.c_int, [C.c_int32] * 5 + [_VP] * 9),
     "tl_spot_seed": (C.c_int, [C.c_int32] * 4 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] * 4),
     "tl_pupil_position": (C.c_int, [C.c_int32] * 3 + [_VP] * 8 + [C.c_int32, _VP]),
-    "tl_workspace_bytes_f64": (C.c_size_t, [C.POINTER(tl_problem)]),
-    "tl_trace_fwd_f64": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 7 + [_VP, C.c_size_t, _VP]),
-    "tl_trace_bwd_f64": (C.c_int, [C.POINTER(tl_problem)] + [_VP] * 15 + [_VP, C.c_size_t, _VP]),
+    "tl_workspace_bytes_f64": (C.c_size_t, [_P]),
+    "tl_trace_fwd_f64": (C.c_int, [_P, _R] + _WS),
+    "tl_trace_bwd_f64": (C.c_int, [_P, _S, _G] + _WS),
     "tl_selftest_arith": (C.c_int, [C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "tl_ray_aim": (C.c_int, [C.c_int32] * 5 + [_VP] * 12 + [C.c_int32] + [_VP] * 4),
     "tl_ray_aim_iter": (C.c_int, [C.c_int32] * 5 + [_VP] * 12 + [C.c_int32] * 2 + [_VP] * 6),

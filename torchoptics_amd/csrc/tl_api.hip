@@ -726,14 +726,15 @@ size_t tl_workspace_bytes(const tl_problem *p)
     return (a > b + c ? a : b + c) + scan + 256;
 }
 
-int tl_trace_fwd(const tl_problem *p, float *x, float *y, float *cx, float *cy, uint8_t *ok, uint8_t *back,
-                 float *opd, float *stacks, double *moments, void *workspace, size_t workspace_bytes, void *stream)
+int tl_trace_fwd(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream)
 {
     int rc = check_problem(p);
     if (rc) return rc;
-    if (stacks && !p->aggregate) return fail(TL_EINVAL, "the stacks output needs tl_problem.aggregate");
-    if (opd && !p->n_index) return fail(TL_EINVAL, "the opd output needs tl_problem.n_index");
-    if (opd && p->aggregate) return fail(TL_EINVAL, "the opd output and aggregate (penalty term) cannot be combined in one call");
+    if (!out) return fail(TL_EINVAL, "the tl_rays block is NULL");
+    double *const moments = out->moments;
+    if (out->stacks && !p->aggregate) return fail(TL_EINVAL, "the stacks output needs tl_problem.aggregate");
+    if (out->opd && !p->n_index) return fail(TL_EINVAL, "the opd output needs tl_problem.n_index");
+    if (out->opd && p->aggregate) return fail(TL_EINVAL, "the opd output and aggregate (penalty term) cannot be combined in one call");
     if (p->P == 0) {
         if (moments) {
             hipError_t e = hipMemsetAsync(moments, 0, (size_t)lenses(p) * p->F * TL_NMOM * sizeof(double), (hipStream_t)stream);
@@ -752,9 +753,9 @@ int tl_trace_fwd(const tl_problem *p, float *x, float *y, float *cx, float *cy, 
     }
     hipStream_t st = (hipStream_t)stream;
     tl_problem q = *p;
-    if (!opd) q.n_index = nullptr;          // the kernel accumulates the path length only when asked
-    int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_fwd(q, x, y, cx, cy, ok, back, opd, stacks, part, pl.nbx, pl.R, st)
-                                         : tl_strict::api_fwd(q, x, y, cx, cy, ok, back, opd, stacks, part, pl.nbx, pl.R, st);
+    if (!out->opd) q.n_index = nullptr;          // the kernel accumulates the path length only when asked
+    int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_fwd(q, *out, part, pl.nbx, pl.R, st)
+                                         : tl_strict::api_fwd(q, *out, part, pl.nbx, pl.R, st);
     if (herr) return hip_fail(herr, "trace_fwd_kernel launch");
     if (moments) {
         unsigned *clear = (workspace_bytes >= tl_workspace_bytes(p)) ? poison_word(p, workspace) : nullptr;
@@ -769,38 +770,38 @@ int tl_trace_fwd(const tl_problem *p, float *x, float *y, float *cx, float *cy, 
     return TL_OK;
 }
 
-int tl_trace_bwd(const tl_problem *p, const float *gx, const float *gy, const float *gcx, const float *gcy,
-                 const double *g_moments, const float *g_opd, float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx,
-                 float *g_cy, float *g_kappa, float *g_poly, float *g_n_index, float *g_x_in, float *g_y_in, void *workspace,
-                 size_t workspace_bytes, void *stream)
-{
-    return tl_trace_bwd_stacks(p, nullptr, gx, gy, gcx, gcy, g_moments, g_opd, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly,
-                               g_n_index, g_x_in, g_y_in, workspace, workspace_bytes, stream);
-}
-
-int tl_trace_bwd_stacks(const tl_problem *p, const float *g_stacks, const float *gx, const float *gy, const float *gcx,
-                        const float *gcy, const double *g_moments, const float *g_opd, float *g_c, float *g_t, float *g_mu,
-                        float *g_z, float *g_cx, float *g_cy, float *g_kappa, float *g_poly, float *g_n_index, float *g_x_in,
-                        float *g_y_in, void *workspace, size_t workspace_bytes, void *stream)
+// the argument checks both backward entry points share (before any HIP call)
+static int check_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out)
 {
     int rc = check_problem(p);
     if (rc) return rc;
-    if (g_stacks && !p->aggregate) return fail(TL_EINVAL, "g_stacks needs tl_problem.aggregate (the stacks are its outputs)");
-    if ((g_opd != nullptr) != (g_n_index != nullptr)) return fail(TL_EINVAL, "g_opd and g_n_index must be given together");
-    if (g_opd && !p->n_index) return fail(TL_EINVAL, "the gradient of the optical path length needs tl_problem.n_index");
-    if (!g_c || !g_t || !g_mu || !g_z || !g_cx || !g_cy) return fail(TL_EINVAL, "a parameter-gradient output is NULL");
-    if ((g_kappa || g_poly) && !p->surf_kind) return fail(TL_EINVAL, "g_kappa / g_poly need aspheric rows (surf_kind)");
-    if (p->surf_kind && (!g_kappa || !g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
+    if (!g || !out) return fail(TL_EINVAL, "the tl_seeds / tl_grads block is NULL");
+    if (g->g_stacks && !p->aggregate) return fail(TL_EINVAL, "g_stacks needs tl_problem.aggregate (the stacks are its outputs)");
+    if ((g->g_opd != nullptr) != (out->g_n_index != nullptr)) return fail(TL_EINVAL, "g_opd and g_n_index must be given together");
+    if (g->g_opd && !p->n_index) return fail(TL_EINVAL, "the gradient of the optical path length needs tl_problem.n_index");
+    if (!out->g_c || !out->g_t || !out->g_mu || !out->g_z || !out->g_cx || !out->g_cy)
+        return fail(TL_EINVAL, "a parameter-gradient output is NULL");
+    if ((out->g_kappa || out->g_poly) && !p->surf_kind) return fail(TL_EINVAL, "g_kappa / g_poly need aspheric rows (surf_kind)");
+    if (p->surf_kind && (!out->g_kappa || !out->g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
+    return TL_OK;
+}
+
+int tl_trace_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out, void *workspace, size_t workspace_bytes,
+                 void *stream)
+{
+    int rc = check_bwd(p, g, out);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(p->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (p->P == 0) {
         const size_t S = p->S, B = (size_t)lenses(p);
-        if ((e = hipMemsetAsync(g_c, 0, B * S * 4, st)) || (e = hipMemsetAsync(g_t, 0, B * S * 4, st)) ||
-            (e = hipMemsetAsync(g_mu, 0, B * S * p->W * 4, st)) || (e = hipMemsetAsync(g_z, 0, B * 4, st)) ||
-            (e = hipMemsetAsync(g_cx, 0, B * p->F * 4, st)) || (e = hipMemsetAsync(g_cy, 0, B * p->F * 4, st)) ||
-            (g_kappa && (e = hipMemsetAsync(g_kappa, 0, B * S * 4, st))) || (g_poly && (e = hipMemsetAsync(g_poly, 0, B * S * 16, st))) ||
-            (g_n_index && (e = hipMemsetAsync(g_n_index, 0, B * (S + 1) * p->W * 4, st))))
+        if ((e = hipMemsetAsync(out->g_c, 0, B * S * 4, st)) || (e = hipMemsetAsync(out->g_t, 0, B * S * 4, st)) ||
+            (e = hipMemsetAsync(out->g_mu, 0, B * S * p->W * 4, st)) || (e = hipMemsetAsync(out->g_z, 0, B * 4, st)) ||
+            (e = hipMemsetAsync(out->g_cx, 0, B * p->F * 4, st)) || (e = hipMemsetAsync(out->g_cy, 0, B * p->F * 4, st)) ||
+            (out->g_kappa && (e = hipMemsetAsync(out->g_kappa, 0, B * S * 4, st))) ||
+            (out->g_poly && (e = hipMemsetAsync(out->g_poly, 0, B * S * 16, st))) ||
+            (out->g_n_index && (e = hipMemsetAsync(out->g_n_index, 0, B * (S + 1) * p->W * 4, st))))
             return hip_fail(e, "hipMemsetAsync(grads)");
         return TL_OK;
     }
@@ -811,58 +812,38 @@ int tl_trace_bwd_stacks(const tl_problem *p, const float *g_stacks, const float 
     const size_t need = (size_t)rows_bfw(p) * pl.nbx * (size_t)ncol * sizeof(double);
     if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd");
     double *part = (double *)workspace;
-    int herr = (p->mode == TL_MODE_FAST)
-                   ? tl_fast::api_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, part, pl.nbx, pl.R, st, g_opd, g_stacks)
-                   : tl_strict::api_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, part, pl.nbx, pl.R, st, g_opd, g_stacks);
+    int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_bwd(*p, *g, *out, part, pl.nbx, pl.R, st)
+                                         : tl_strict::api_bwd(*p, *g, *out, part, pl.nbx, pl.R, st);
     if (herr) return hip_fail(herr, "trace_bwd_kernel launch");
-    const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0) + (g_opd ? p->W * (p->S + 1) : 0);
-    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, ns, p->F, p->W, p->S, pl.nbx, g_c,
-                       g_t, g_mu, g_z, g_cx, g_cy, ncol, g_kappa, g_poly, (const double *)nullptr, 0,
-                       (const double *)nullptr, (const unsigned *)nullptr, 0u, 0, g_n_index, 0);
+    const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0) + (g->g_opd ? p->W * (p->S + 1) : 0);
+    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, ns, p->F, p->W, p->S, pl.nbx, out->g_c,
+                       out->g_t, out->g_mu, out->g_z, out->g_cx, out->g_cy, ncol, out->g_kappa, out->g_poly,
+                       (const double *)nullptr, 0, (const double *)nullptr, (const unsigned *)nullptr, 0u, 0, out->g_n_index, 0);
     herr = (int)hipGetLastError();
     if (herr) return hip_fail(herr, "reduce_bwd_kernel launch");
     return TL_OK;
 }
 
-int tl_trace_bwd_from_outputs(const tl_problem *p, const float *gx, const float *gy, const float *gcx, const float *gcy,
-                              const double *g_moments, const float *x_fwd, const float *y_fwd, const float *cx_fwd,
-                              const float *cy_fwd, const uint8_t *ok_fwd, const double *moments_fwd, float *g_c,
-                              float *g_t, float *g_mu, float *g_z, float *g_cx, float *g_cy, float *g_kappa,
-                              float *g_poly, float *g_x_in, float *g_y_in, void *workspace, size_t workspace_bytes,
-                              void *stream)
+int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_rays *fwd, const tl_grads *out,
+                              void *workspace, size_t workspace_bytes, void *stream)
 {
-    return tl_trace_bwd_from_outputs_stacks(p, nullptr, gx, gy, gcx, gcy, g_moments, x_fwd, y_fwd, cx_fwd, cy_fwd, ok_fwd,
-                                            moments_fwd, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly, g_x_in, g_y_in,
-                                            workspace, workspace_bytes, stream);
-}
-
-int tl_trace_bwd_from_outputs_stacks(const tl_problem *p, const float *g_stacks, const float *gx, const float *gy,
-                                     const float *gcx, const float *gcy, const double *g_moments, const float *x_fwd,
-                                     const float *y_fwd, const float *cx_fwd, const float *cy_fwd, const uint8_t *ok_fwd,
-                                     const double *moments_fwd, float *g_c, float *g_t, float *g_mu, float *g_z, float *g_cx,
-                                     float *g_cy, float *g_kappa, float *g_poly, float *g_x_in, float *g_y_in, void *workspace,
-                                     size_t workspace_bytes, void *stream)
-{
-    int rc = check_problem(p);
+    int rc = check_bwd(p, g, out);
     if (rc) return rc;
-    if (g_stacks && !p->aggregate) return fail(TL_EINVAL, "g_stacks needs tl_problem.aggregate (the stacks are its outputs)");
-    if (!g_c || !g_t || !g_mu || !g_z || !g_cx || !g_cy) return fail(TL_EINVAL, "a parameter-gradient output is NULL");
-    // p->cond_flags (written by the forward) is the ok bytes with the conditioning flag: it is read instead of ok_fwd
-    if (p->cond_flags) ok_fwd = p->cond_flags;
-    if (p->P > 0 && (!x_fwd || !y_fwd || !cx_fwd || !cy_fwd || !ok_fwd))
+    if (!fwd) return fail(TL_EINVAL, "the tl_rays block of the forward outputs is NULL");
+    if (g->g_opd || out->g_n_index)
+        return fail(TL_EINVAL, "tl_trace_bwd_from_outputs has no path-length gradient (g_opd, g_n_index): use tl_trace_bwd");
+    // p->cond_flags (written by the forward) is the ok bytes with the conditioning flag: it is read instead of fwd->ok
+    tl_rays f = *fwd;
+    if (p->cond_flags) f.ok = p->cond_flags;
+    if (p->P > 0 && (!f.x || !f.y || !f.cx || !f.cy || !f.ok))
         return fail(TL_EINVAL, "the forward outputs x, y, cx, cy, ok are required");
     if (!p->allow_backward)
         return fail(TL_EINVAL, "tl_trace_bwd_from_outputs: allow_backward_rays only");
     const bool hits_ok = p->surf_kind == nullptr || (p->asph_hits != nullptr && p->asph_hit_slots > 0);
     // the penalty term is walked back by the unrolled kernels only (3..20 rows, aspheric rows with stored hits);
-    // other lenses take the checkpoint kernel for every ray
-    if (p->aggregate && !(tl_walk_unrolled(p->S, p->P) && hits_ok))
-        return tl_trace_bwd_stacks(p, g_stacks, gx, gy, gcx, gcy, g_moments, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa,
-                                   g_poly, nullptr, g_x_in, g_y_in, workspace, workspace_bytes, stream);
-    if ((g_kappa || g_poly) && !p->surf_kind) return fail(TL_EINVAL, "g_kappa / g_poly need aspheric rows (surf_kind)");
-    if (p->surf_kind && (!g_kappa || !g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
-    if (p->P == 0) return tl_trace_bwd_stacks(p, g_stacks, gx, gy, gcx, gcy, g_moments, nullptr, g_c, g_t, g_mu, g_z, g_cx, g_cy,
-                                              g_kappa, g_poly, nullptr, g_x_in, g_y_in, workspace, workspace_bytes, stream);
+    // other lenses take the checkpoint kernel for every ray -- and an empty shard its memsets
+    if ((p->aggregate && !(tl_walk_unrolled(p->S, p->P) && hits_ok)) || p->P == 0)
+        return tl_trace_bwd(p, g, out, workspace, workspace_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSetDevice(p->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -884,18 +865,14 @@ int tl_trace_bwd_from_outputs_stacks(const tl_problem *p, const float *g_stacks,
     // (Recorded into a HIP graph the call is replayed with the SAME token every time; the word is cleared by the
     //  forward call of the same step, see reduce_moments_kernel, so a poisoned replay does not stick.)
     int herr = (p->mode == TL_MODE_FAST)
-                   ? tl_fast::api_bwd_inv(*p, gx, gy, gcx, gcy, g_moments, x_fwd, y_fwd, cx_fwd, cy_fwd, ok_fwd,
-                                          moments_fwd, g_x_in, g_y_in, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st,
-                                          g_stacks)
-                   : tl_strict::api_bwd_inv(*p, gx, gy, gcx, gcy, g_moments, x_fwd, y_fwd, cx_fwd, cy_fwd, ok_fwd,
-                                            moments_fwd, g_x_in, g_y_in, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st,
-                                            g_stacks);
+                   ? tl_fast::api_bwd_inv(*p, *g, f, *out, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st)
+                   : tl_strict::api_bwd_inv(*p, *g, f, *out, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st);
     if (herr) return hip_fail(herr, "trace_bwd_inv_kernel launch");
     const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0);
-    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, p->S, p->F, p->W, p->S, pl.nbx, g_c, g_t,
-                       g_mu, g_z, g_cx, g_cy, ncol, g_kappa, g_poly, (const double *)part_ck, ns,
-                       moments_fwd, (const unsigned *)poison, token, pk.nbx, (float *)nullptr,
-                       (p->aggregate ? 1 : 0) | (p->cond_flags ? 2 : 0));
+    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, p->S, p->F, p->W, p->S, pl.nbx, out->g_c,
+                       out->g_t, out->g_mu, out->g_z, out->g_cx, out->g_cy, ncol, out->g_kappa, out->g_poly,
+                       (const double *)part_ck, ns, (const double *)f.moments, (const unsigned *)poison, token, pk.nbx,
+                       (float *)nullptr, (p->aggregate ? 1 : 0) | (p->cond_flags ? 2 : 0));
     herr = (int)hipGetLastError();
     if (herr) return hip_fail(herr, "reduce_bwd_kernel launch");
     return TL_OK;
@@ -1103,45 +1080,47 @@ size_t tl_workspace_bytes_f64(const tl_problem *p)
     return (a > b ? a : b) + 256;
 }
 
-int tl_trace_fwd_f64(const tl_problem *p, double *x, double *y, double *cx, double *cy, uint8_t *ok, uint8_t *back,
-                     double *moments, void *workspace, size_t workspace_bytes, void *stream)
+int tl_trace_fwd_f64(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream)
 {
     int rc = check_f64(p);
     if (rc) return rc;
+    if (!out) return fail(TL_EINVAL, "the tl_rays block is NULL");
+    if (out->opd || out->stacks) return fail(TL_EINVAL, "the double-precision trace has no opd and no stacks output");
     hipError_t e = hipSetDevice(p->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     const Plan pl = plan_fwd(p);
     double *part = nullptr;
-    if (moments) {
+    if (out->moments) {
         const size_t need = (size_t)rows_bfw(p) * pl.nbx * TL_NMOM * sizeof(double);
         if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_fwd_f64");
         part = (double *)workspace;
     }
-    int herr = tl_f64::launch_fwd(*p, x, y, cx, cy, ok, back, part, pl.nbx, (hipStream_t)stream);
+    int herr = tl_f64::launch_fwd(*p, *out, part, pl.nbx, (hipStream_t)stream);
     if (herr) return hip_fail(herr, "tl_f64::fwd_kernel launch");
-    if (moments) {
-        herr = tl_f64::launch_reduce_moments(*p, part, moments, pl.nbx, (hipStream_t)stream);
+    if (out->moments) {
+        herr = tl_f64::launch_reduce_moments(*p, part, out->moments, pl.nbx, (hipStream_t)stream);
         if (herr) return hip_fail(herr, "tl_f64::reduce_moments_kernel launch");
     }
     return TL_OK;
 }
 
-int tl_trace_bwd_f64(const tl_problem *p, const double *gx, const double *gy, const double *gcx, const double *gcy,
-                     const double *g_moments, double *g_c, double *g_t, double *g_mu, double *g_z, double *g_cx, double *g_cy,
-                     double *g_kappa, double *g_poly, double *g_x_in, double *g_y_in, void *workspace, size_t workspace_bytes,
+int tl_trace_bwd_f64(const tl_problem *p, const tl_seeds *g, const tl_grads *out, void *workspace, size_t workspace_bytes,
                      void *stream)
 {
     int rc = check_f64(p);
     if (rc) return rc;
-    if (!g_c || !g_t || !g_mu || !g_z || !g_cx || !g_cy) return fail(TL_EINVAL, "a parameter-gradient output is NULL");
-    if (p->surf_kind && (!g_kappa || !g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
+    if (!g || !out) return fail(TL_EINVAL, "the tl_seeds / tl_grads block is NULL");
+    if (g->g_opd || g->g_stacks || out->g_n_index)
+        return fail(TL_EINVAL, "the double-precision trace has no g_opd, g_stacks and g_n_index");
+    if (!out->g_c || !out->g_t || !out->g_mu || !out->g_z || !out->g_cx || !out->g_cy)
+        return fail(TL_EINVAL, "a parameter-gradient output is NULL");
+    if (p->surf_kind && (!out->g_kappa || !out->g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
     hipError_t e = hipSetDevice(p->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     const Plan pl = plan_bwd(p);
     const size_t need = (size_t)rows_bfw(p) * pl.nbx * (size_t)(8 * p->S + 3) * sizeof(double);
     if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd_f64");
-    const int herr = tl_f64::launch_bwd(*p, gx, gy, gcx, gcy, g_moments, g_x_in, g_y_in, (double *)workspace, pl.nbx, g_c, g_t, g_mu,
-                                        g_z, g_cx, g_cy, g_kappa, g_poly, (hipStream_t)stream);
+    const int herr = tl_f64::launch_bwd(*p, *g, *out, (double *)workspace, pl.nbx, (hipStream_t)stream);
     if (herr) return hip_fail(herr, "tl_f64::bwd_kernel launch");
     return TL_OK;
 }

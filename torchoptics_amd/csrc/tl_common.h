@@ -31,32 +31,35 @@ __host__ __device__ static inline size_t tl_scanmap_bytes(int rows, int64_t nchu
 
 static inline bool tl_walk_unrolled(int S, int P) { return S >= TL_INVU_MIN && S <= TL_INVU_MAX && P >= 256; }
 
-// per-mode launchers (defined in tl_strict.hip / tl_fast.hip); return hipError_t as int
-#define TL_DECLARE_MODE(NS)                                                                          \
-    namespace NS {                                                                                   \
-    int api_fwd(const tl_problem &p, float *x, float *y, float *cx, float *cy, uint8_t *ok,           \
-                uint8_t *back, float *opd, float *stacks, double *part, int nbx, int R,             \
-                hipStream_t st);                                                                     \
-    int api_bwd(const tl_problem &p, const float *gx, const float *gy, const float *gcx,              \
-                const float *gcy, const double *gmom, float *gxin, float *gyin, double *part,         \
-                int nbx, int R, hipStream_t st, const float *gopd, const float *gstk);               \
-    int api_bwd_inv(const tl_problem &p, const float *gx, const float *gy, const float *gcx,          \
-                    const float *gcy, const double *gmom, const float *fx, const float *fy,           \
-                    const float *fcx, const float *fcy, const uint8_t *fok, const double *fmom,       \
-                    float *gxin, float *gyin, double *part_inv, double *part_ck, unsigned *poison,    \
-                    unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st,            \
-                    const float *gstk);                                                              \
-    int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st); \
+// What makes a checkpoint launch (trace_bwd_kernel) the fallback of a walk-back launch in front of it: the forward's moments
+// and the walk-back's poison word / token decide on the device whether it runs; dead_ok = the forward's ok bytes when it also
+// takes single rays (the penalty term's dead rays, flagged ill-conditioned rays).  All zero: an ordinary backward.
+struct tl_fallback {
+    const double *mom;
+    const unsigned *poison;
+    unsigned token;
+    const uint8_t *dead_ok;
+};
+
+// per-mode launchers (defined once, at the end of tl_kernels.inc, for the mode of the including unit); return hipError_t
+// as int.  The blocks are the C entry's, forwarded as they are; `part*`, the plans (nbx, R), poison and token are what the
+// entry point computed.
+#define TL_DECLARE_MODE(NS)                                                                                        \
+    namespace NS {                                                                                                 \
+    int api_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, int R, hipStream_t st);            \
+    int api_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, int R,         \
+                hipStream_t st);                                                                                   \
+    int api_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &fwd, const tl_grads &out,               \
+                    double *part_inv, double *part_ck, unsigned *poison, unsigned token, int nbx, int R,           \
+                    int nbx_ck, int R_ck, hipStream_t st);                                                         \
+    int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st);   \
     }
 TL_DECLARE_MODE(tl_strict)
 TL_DECLARE_MODE(tl_fast)
 
 // double-precision twin (tl_f64.hip): generic, untuned kernels behind tl_trace_fwd_f64 / tl_trace_bwd_f64
 namespace tl_f64 {
-int launch_fwd(const tl_problem &p, double *x, double *y, double *cx, double *cy, uint8_t *ok, uint8_t *back, double *part, int nbx,
-               hipStream_t st);
+int launch_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, hipStream_t st);
 int launch_reduce_moments(const tl_problem &p, const double *part, double *mom, int nbx, hipStream_t st);
-int launch_bwd(const tl_problem &p, const double *gx, const double *gy, const double *gcx, const double *gcy, const double *gmom,
-               double *gxin, double *gyin, double *part, int nbx, double *g_c, double *g_t, double *g_mu, double *g_z, double *g_cx,
-               double *g_cy, double *g_kappa, double *g_poly, hipStream_t st);
+int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, hipStream_t st);
 }

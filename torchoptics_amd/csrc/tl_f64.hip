@@ -474,11 +474,12 @@ __global__ __launch_bounds__(kBlock) void reduce_moments_kernel(const double *__
     if (threadIdx.x == 0) mom[blockIdx.x] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
 }
 
-int launch_fwd(const tl_problem &p, double *x, double *y, double *cx, double *cy, uint8_t *ok, uint8_t *back, double *part, int nbx,
-               hipStream_t st)
+// (the blocks' float-typed members point at doubles here, as tl_problem's do)
+int launch_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, hipStream_t st)
 {
     const int B = p.B > 0 ? p.B : 1;
-    hipLaunchKernelGGL(fwd_kernel, dim3(nbx, B * p.F * p.W), dim3(kBlock), 0, st, p, x, y, cx, cy, ok, back, part);
+    hipLaunchKernelGGL(fwd_kernel, dim3(nbx, B * p.F * p.W), dim3(kBlock), 0, st, p, (double *)out.x, (double *)out.y,
+                       (double *)out.cx, (double *)out.cy, out.ok, out.back, part);
     return (int)hipGetLastError();
 }
 
@@ -489,18 +490,18 @@ int launch_reduce_moments(const tl_problem &p, const double *part, double *mom, 
     return (int)hipGetLastError();
 }
 
-int launch_bwd(const tl_problem &p, const double *gx, const double *gy, const double *gcx, const double *gcy, const double *gmom,
-               double *gxin, double *gyin, double *part, int nbx, double *g_c, double *g_t, double *g_mu, double *g_z, double *g_cx,
-               double *g_cy, double *g_kappa, double *g_poly, hipStream_t st)
+int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, hipStream_t st)
 {
     const int B = p.B > 0 ? p.B : 1;
-    hipLaunchKernelGGL(bwd_kernel, dim3(nbx, B * p.F * p.W), dim3(kBlock), 0, st, p, gx, gy, gcx, gcy, gmom, gxin, gyin, part);
+    hipLaunchKernelGGL(bwd_kernel, dim3(nbx, B * p.F * p.W), dim3(kBlock), 0, st, p, (const double *)g.gx, (const double *)g.gy,
+                       (const double *)g.gcx, (const double *)g.gcy, g.g_moments, (double *)out.g_x_in, (double *)out.g_y_in, part);
     int herr = (int)hipGetLastError();
     if (herr) return herr;
     const int asph = p.surf_kind != nullptr;
     const int nout = 2 * p.S + p.W * p.S + 1 + 2 * p.F + (asph ? 5 * p.S : 0);
     hipLaunchKernelGGL(reduce_kernel, dim3(nout, B), dim3(kBlock), 0, st, (const double *)part, B * p.F * p.W * nbx, 0, p.F, p.W, p.S, nbx,
-                       asph, g_c, g_t, g_mu, g_z, g_cx, g_cy, g_kappa, g_poly);
+                       asph, (double *)out.g_c, (double *)out.g_t, (double *)out.g_mu, (double *)out.g_z, (double *)out.g_cx,
+                       (double *)out.g_cy, (double *)out.g_kappa, (double *)out.g_poly);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // tl_kernels.inc -- device code of the fused sequential ray tracer for gfx950 (CDNA4).
 //
 // Included once per arithmetic mode (tl_strict.hip, tl_fast.hip) with
-//   TL_NS    : namespace name for the mode
+//   TL_NS    : namespace name for the mode; TL_API_NS: namespace of its entry points (tl_common.h, TL_DECLARE_MODE)
 //   TL_FAST  : 0 = strict (TU built with -ffp-contract=off, IEEE sqrt / divide)
 //              1 = fast   (TU built with -ffp-contract=fast, hardware rcp / rsq / sqrt)
 //
@@ -311,7 +311,7 @@ __device__ __forceinline__ float theta_norm(const float cos2) { return theta_fro
 
 // Upstream gradient of the three penalty quantities of one row of one ray: z_RELU, theta_norm, theta_prime_norm.  The
 // fused seed gq (moment 8: the per-ray sum of all three) enters them alike (pen_seed); a per-ray seed from the stacks
-// (PEN == kPenRay, tl_trace_bwd_stacks) adds its own value to each.
+// (PEN == kPenRay, tl_seeds.g_stacks) adds its own value to each.
 struct PenSeed { float z, th, thp; };
 __device__ __forceinline__ PenSeed pen_seed(const float g) { return PenSeed{g, g, g}; }
 
@@ -2336,13 +2336,14 @@ static int launch_selftest_arith(const float *a, const float *b, int64_t n, floa
 }
 
 // ------------------------------------------------------------------ host launchers
-static int launch_fwd(const tl_problem &p, float *x, float *y, float *cx, float *cy, uint8_t *ok,
-                      uint8_t *back, float *opd, float *stacks, double *part, int nbx, int R, hipStream_t st)
+// (the C entry's blocks -- tl_rays, tl_seeds, tl_grads -- come down as they are: a kernel's pointer list is written out
+// once, at its hipLaunchKernelGGL)
+static int launch_fwd(const tl_problem &p, const tl_rays &o, double *part, int nbx, int R, hipStream_t st)
 {
     dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
 #define TL_FWD(PEN_, ASPH_, OPD_) \
-    hipLaunchKernelGGL((trace_fwd_kernel<PEN_, ASPH_, OPD_>), grid, block, 0, st, p, x, y, cx, cy, ok, back, opd, stacks, part, R)
-    const bool asph = p.surf_kind != nullptr, wopd = p.n_index != nullptr && opd != nullptr;
+    hipLaunchKernelGGL((trace_fwd_kernel<PEN_, ASPH_, OPD_>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, o.opd, o.stacks, part, R)
+    const bool asph = p.surf_kind != nullptr, wopd = p.n_index != nullptr && o.opd != nullptr;
     if (p.aggregate && asph) TL_FWD(true, true, false);
     else if (p.aggregate) TL_FWD(true, false, false);
     else if (asph && wopd) TL_FWD(false, true, true);
@@ -2350,7 +2351,7 @@ static int launch_fwd(const tl_problem &p, float *x, float *y, float *cx, float 
     else if (wopd) TL_FWD(false, false, true);
 #if TL_FAST
     // two rays per lane: -10 % in fast mode (latency-bound chains), +4 % in strict mode (issue-bound, fewer waves)
-    else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, x, y, cx, cy, ok, back, part, R);
+    else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, part, R);
 #else
     else TL_FWD(false, false, false);
 #endif
@@ -2359,15 +2360,15 @@ static int launch_fwd(const tl_problem &p, float *x, float *y, float *cx, float 
 }
 
 template <int NS>
-static int launch_bwd_ns(const tl_problem &p, const float *gx, const float *gy, const float *gcx,
-                         const float *gcy, const double *gmom, float *gxin, float *gyin,
-                         double *part, int nbx, int R, hipStream_t st, const double *fb_mom, const unsigned *fb_poison,
-                         unsigned fb_token, const float *gopd, const uint8_t *dead_ok, const float *gstk)
+static int launch_bwd_ns(const tl_problem &p, const tl_seeds &g, const tl_grads &o, double *part, int nbx, int R,
+                         hipStream_t st, const tl_fallback &fb)
 {
     dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
     // (gstk: the per-ray stack seeds, kPenRay; the caller has checked p.aggregate)
+    const float *gstk = g.g_stacks;
 #define TL_BWD(ASPH_, PEN_) \
-    hipLaunchKernelGGL((trace_bwd_kernel<NS, ASPH_, PEN_>), grid, block, 0, st, p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, R, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk)
+    hipLaunchKernelGGL((trace_bwd_kernel<NS, ASPH_, PEN_>), grid, block, 0, st, p, g.gx, g.gy, g.gcx, g.gcy, g.g_moments, \
+                       o.g_x_in, o.g_y_in, part, R, fb.mom, fb.poison, fb.token, g.g_opd, fb.dead_ok, gstk)
     if (p.surf_kind && p.aggregate && gstk) TL_BWD(true, kPenRay);
     else if (p.surf_kind && p.aggregate) TL_BWD(true, kPenUniform);
     else if (p.surf_kind) TL_BWD(true, kPenNone);
@@ -2378,22 +2379,19 @@ static int launch_bwd_ns(const tl_problem &p, const float *gx, const float *gy, 
     return (int)hipGetLastError();
 }
 
-// returns the NS bucket actually used through *ns_used (partials row = 3*NS+3 doubles)
-static int launch_bwd(const tl_problem &p, const float *gx, const float *gy, const float *gcx,
-                      const float *gcy, const double *gmom, float *gxin, float *gyin, double *part,
-                      int nbx, int R, hipStream_t st, const double *fb_mom = nullptr,
-                      const unsigned *fb_poison = nullptr, unsigned fb_token = 0u, const float *gopd = nullptr,
-                      const uint8_t *dead_ok = nullptr, const float *gstk = nullptr)
+// the checkpoint kernel of the row bucket tl_bwd_bucket(p.S) (its partial rows: tl_bwd_row doubles); fb: see tl_fallback
+static int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &o, double *part, int nbx, int R,
+                      hipStream_t st, const tl_fallback &fb = {})
 {
     const int ns = tl_bwd_bucket(p.S);
     switch (ns) {
-    case 4:  return launch_bwd_ns<4>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
-    case 8:  return launch_bwd_ns<8>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
-    case 12: return launch_bwd_ns<12>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
-    case 16: return launch_bwd_ns<16>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
-    case 20: return launch_bwd_ns<20>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
-    case 24: return launch_bwd_ns<24>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
-    case 32: return launch_bwd_ns<32>(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part, nbx, R, st, fb_mom, fb_poison, fb_token, gopd, dead_ok, gstk);
+    case 4:  return launch_bwd_ns<4>(p, g, o, part, nbx, R, st, fb);
+    case 8:  return launch_bwd_ns<8>(p, g, o, part, nbx, R, st, fb);
+    case 12: return launch_bwd_ns<12>(p, g, o, part, nbx, R, st, fb);
+    case 16: return launch_bwd_ns<16>(p, g, o, part, nbx, R, st, fb);
+    case 20: return launch_bwd_ns<20>(p, g, o, part, nbx, R, st, fb);
+    case 24: return launch_bwd_ns<24>(p, g, o, part, nbx, R, st, fb);
+    case 32: return launch_bwd_ns<32>(p, g, o, part, nbx, R, st, fb);
     default: return -1;
     }
 }
@@ -2401,11 +2399,10 @@ static int launch_bwd(const tl_problem &p, const float *gx, const float *gy, con
 // part_inv / part_ck: partial rows of the walk-back kernel (3S+3 columns) and of its checkpoint fallback
 // (3NS+3 columns); exactly one of the two launches does the work, decided on the device (fallback_needed) -- except
 // with the penalty term, where the checkpoint kernel also takes the rays that died on the way (see trace_bwd_kernel).
-static int launch_bwd_inv(const tl_problem &p, const float *gx, const float *gy, const float *gcx, const float *gcy,
-                          const double *gmom, const float *fx, const float *fy, const float *fcx, const float *fcy,
-                          const uint8_t *fok, const double *fmom, float *gxin, float *gyin, double *part_inv,
+// (f.ok: the forward's ok bytes, or p.cond_flags in their place when the forward wrote those)
+static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &f, const tl_grads &o, double *part_inv,
                           double *part_ck, unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck,
-                          hipStream_t st, const float *gstk = nullptr)
+                          hipStream_t st)
 {
     dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
     // TL_INV_LDS_PAD (bytes, development only): extra dynamic LDS per block = fewer resident blocks per CU, to measure how
@@ -2417,7 +2414,9 @@ static int launch_bwd_inv(const tl_problem &p, const float *gx, const float *gy,
     const bool asph = p.surf_kind != nullptr, pen = p.aggregate != 0;
     const bool hits = asph && p.asph_hits != nullptr && p.asph_hit_slots > 0;
     const size_t lds_asph = hits ? (size_t)2 * p.asph_hit_slots * kBlock * sizeof(float) : 0;
-#define TL_INV_ARGS p, gx, gy, gcx, gcy, gmom, fx, fy, fcx, fcy, fok, fmom, gxin, gyin, part_inv, R, poison, token
+    const float *gstk = g.g_stacks;
+#define TL_INV_ARGS p, g.gx, g.gy, g.gcx, g.gcy, g.g_moments, f.x, f.y, f.cx, f.cy, f.ok, f.moments, o.g_x_in, o.g_y_in, \
+                    part_inv, R, poison, token
 #define TL_INVU_V(NS_, ASPH_, PEN_) \
     hipLaunchKernelGGL((trace_bwd_inv_unrolled_kernel<NS_, ASPH_, PEN_>), grid, block, \
                        (NS_ < kInvUnrollPairMin ? 2 : 1) * lds + lds_asph + lds_pad, st, TL_INV_ARGS, gstk)
@@ -2447,8 +2446,20 @@ static int launch_bwd_inv(const tl_problem &p, const float *gx, const float *gy,
 #undef TL_INV_ARGS
     const int herr = (int)hipGetLastError();
     if (herr) return herr;
-    return launch_bwd(p, gx, gy, gcx, gcy, gmom, gxin, gyin, part_ck, nbx_ck, R_ck, st, fmom, poison, token, nullptr,
-                      (pen || p.cond_flags) ? fok : nullptr, gstk);
+    return launch_bwd(p, g, o, part_ck, nbx_ck, R_ck, st, {f.moments, poison, token, (pen || p.cond_flags) ? f.ok : nullptr});
 }
 
 }  // namespace TL_NS
+
+// the per-mode entry points tl_common.h declares (TL_DECLARE_MODE), for the mode this translation unit is built in
+namespace TL_API_NS {
+int api_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, int R, hipStream_t st)
+{ return TL_NS::launch_fwd(p, out, part, nbx, R, st); }
+int api_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, int R, hipStream_t st)
+{ return TL_NS::launch_bwd(p, g, out, part, nbx, R, st); }
+int api_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &fwd, const tl_grads &out, double *part_inv,
+                double *part_ck, unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st)
+{ return TL_NS::launch_bwd_inv(p, g, fwd, out, part_inv, part_ck, poison, token, nbx, R, nbx_ck, R_ck, st); }
+int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st)
+{ return TL_NS::launch_selftest_arith(a, b, n, quot, root, st); }
+}

@@ -125,6 +125,8 @@ struct Norm {                       // trace_skew's arguments brought to the ker
 };
 
 const void *ptr(const Tensor &t) { return t.defined() ? t.data_ptr() : nullptr; }
+// the same, typed for a member of tl_rays / tl_seeds / tl_grads
+template <class T> T *dptr(const Tensor &t) { return t.defined() ? (T *)t.data_ptr() : nullptr; }
 
 tl_problem make_problem(const Norm &n, bool allow_back, int mode, bool aggregate, const Tensor &hits, bool moments_x,
                         bool with_n_index, const Tensor &cond)
@@ -276,10 +278,11 @@ public:
         Tensor moments = at::empty({B * F, TL_NMOM}, fopt.dtype(at::kDouble));
         {
             Timed timed(0, st);
-            check(tl_trace_fwd(&prob, (float *)ptr(fp[0]), (float *)ptr(fp[1]), (float *)ptr(fp[2]), (float *)ptr(fp[3]),
-                               (uint8_t *)ptr(bp[0]), (uint8_t *)ptr(bp[1]), (float *)ptr(opd), (float *)ptr(stacks),
-                               (double *)moments.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), (void *)st),
-                  "tl_trace_fwd");
+            tl_rays o = {};
+            o.x = dptr<float>(fp[0]); o.y = dptr<float>(fp[1]); o.cx = dptr<float>(fp[2]); o.cy = dptr<float>(fp[3]);
+            o.ok = dptr<uint8_t>(bp[0]); o.back = dptr<uint8_t>(bp[1]);
+            o.opd = dptr<float>(opd); o.stacks = dptr<float>(stacks); o.moments = dptr<double>(moments);
+            check(tl_trace_fwd(&prob, &o, ws.data_ptr(), (size_t)ws.numel(), (void *)st), "tl_trace_fwd");
         }
         // kFuseRms: compute_rms2d of these rays (every lens of the batch; n = P W rays per field) as a tenth output of THIS
         // node -- one tl_spot_rms launch here instead of a second extension call and a second autograd node for the loss
@@ -329,7 +332,7 @@ public:
         Tensor opd_out = want_opd ? opd.permute({0, 1, 3, 2}) : at::empty({0}, fopt);
         Tensor stk_out = stacks.defined() ? stacks.permute({0, 1, 2, 3, 5, 4}) : at::empty({0}, fopt);
         Tensor rms_out = rms.defined() ? rms : at::empty({0}, fopt);
-        // the stacks are differentiable (their gradient reaches tl_trace_bwd*_stacks as g_stacks); the placeholders are not
+        // the stacks are differentiable (their gradient reaches the backward calls as tl_seeds.g_stacks); the placeholders are not
         if (want_opd) ctx->mark_non_differentiable({ok, back});
         else ctx->mark_non_differentiable({ok, back, opd_out});
         if (!stacks.defined()) ctx->mark_non_differentiable({stk_out});
@@ -391,24 +394,24 @@ public:
         if (gopdd.defined()) g_n = at::empty({B, W, S + 1}, fopt);
         {
             Timed timed(1, st);
-            if (use_inv)
-                check(tl_trace_bwd_from_outputs_stacks(
-                          &prob, (const float *)ptr(gstk), (const float *)ptr(gxd), (const float *)ptr(gyd), (const float *)ptr(gcxd),
-                          (const float *)ptr(gcyd), (const double *)ptr(gmd), (const float *)ptr(fx), (const float *)ptr(fy),
-                          (const float *)ptr(fcx), (const float *)ptr(fcy), (const uint8_t *)ptr(fok), (const double *)ptr(fmom),
-                          (float *)g_c.data_ptr(), (float *)g_t.data_ptr(), (float *)g_mu.data_ptr(), (float *)g_z.data_ptr(),
-                          (float *)g_cx.data_ptr(), (float *)g_cy.data_ptr(), (float *)ptr(g_kappa), (float *)ptr(g_poly),
-                          (float *)ptr(gxin), (float *)ptr(gyin), ws.data_ptr(), (size_t)ws.numel(), (void *)st),
+            tl_seeds sd = {};
+            sd.gx = dptr<const float>(gxd); sd.gy = dptr<const float>(gyd);
+            sd.gcx = dptr<const float>(gcxd); sd.gcy = dptr<const float>(gcyd);
+            sd.g_moments = dptr<const double>(gmd); sd.g_opd = dptr<const float>(gopdd); sd.g_stacks = dptr<const float>(gstk);
+            tl_grads o = {};
+            o.g_c = dptr<float>(g_c); o.g_t = dptr<float>(g_t); o.g_mu = dptr<float>(g_mu); o.g_z = dptr<float>(g_z);
+            o.g_cx = dptr<float>(g_cx); o.g_cy = dptr<float>(g_cy);
+            o.g_kappa = dptr<float>(g_kappa); o.g_poly = dptr<float>(g_poly); o.g_n_index = dptr<float>(g_n);
+            o.g_x_in = dptr<float>(gxin); o.g_y_in = dptr<float>(gyin);
+            if (use_inv) {
+                tl_rays fwd = {};
+                fwd.x = dptr<float>(fx); fwd.y = dptr<float>(fy); fwd.cx = dptr<float>(fcx); fwd.cy = dptr<float>(fcy);
+                fwd.ok = dptr<uint8_t>(fok); fwd.moments = dptr<double>(fmom);
+                check(tl_trace_bwd_from_outputs(&prob, &sd, &fwd, &o, ws.data_ptr(), (size_t)ws.numel(), (void *)st),
                       "tl_trace_bwd_from_outputs");
-            else
-                check(tl_trace_bwd_stacks(&prob, (const float *)ptr(gstk), (const float *)ptr(gxd), (const float *)ptr(gyd),
-                                   (const float *)ptr(gcxd),
-                                   (const float *)ptr(gcyd), (const double *)ptr(gmd), (const float *)ptr(gopdd),
-                                   (float *)g_c.data_ptr(), (float *)g_t.data_ptr(), (float *)g_mu.data_ptr(),
-                                   (float *)g_z.data_ptr(), (float *)g_cx.data_ptr(), (float *)g_cy.data_ptr(),
-                                   (float *)ptr(g_kappa), (float *)ptr(g_poly), (float *)ptr(g_n), (float *)ptr(gxin),
-                                   (float *)ptr(gyin), ws.data_ptr(), (size_t)ws.numel(), (void *)st),
-                      "tl_trace_bwd");
+            } else {
+                check(tl_trace_bwd(&prob, &sd, &o, ws.data_ptr(), (size_t)ws.numel(), (void *)st), "tl_trace_bwd");
+            }
         }
         auto shape = [&](const char *key) { return ctx->saved_data[key].toIntVector(); };
         // gradients in the callers' shapes: what was broadcast over lenses / fields / wavelengths is summed back

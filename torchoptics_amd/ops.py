@@ -274,9 +274,9 @@ class TraceFunction(torch.autograd.Function):
         stacks = torch.empty((3, S, B, F, W, P), dtype=torch.float32, device=dev) if (aggregate and want_stacks) else None
         moments = torch.empty((B * F, TL_NMOM), dtype=torch.float64, device=dev)
         with _on_device(dev), _Timed("fwd", dev):
-            rc = lib.tl_trace_fwd(C.byref(prob), *[_lib.ptr(b) for b in fp], *[_lib.ptr(b) for b in bp],
-                                  _lib.ptr(opd), _lib.ptr(stacks), _lib.ptr(moments), _lib.ptr(ws), ws.numel(),
-                                  _stream_ptr(dev))
+            out = _lib.rays(x=fp[0], y=fp[1], cx=fp[2], cy=fp[3], ok=bp[0], back=bp[1], opd=opd, stacks=stacks,
+                            moments=moments)
+            rc = lib.tl_trace_fwd(C.byref(prob), out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
         _lib.check(rc, "tl_trace_fwd")
         global _last_use_inv
         _last_use_inv = use_inv
@@ -294,7 +294,7 @@ class TraceFunction(torch.autograd.Function):
             flags = [torch.empty(0, dtype=torch.bool, device=dev) for _ in range(2)]
         opd_out = opd.permute(0, 1, 3, 2) if want_opd else torch.empty(0, device=dev)
         stk_out = stacks.permute(0, 1, 2, 3, 5, 4) if stacks is not None else torch.empty(0, device=dev)
-        # the stacks are differentiable (their gradient reaches tl_trace_bwd*_stacks as g_stacks); the placeholders are not
+        # the stacks are differentiable (their gradient reaches the backward calls as tl_seeds.g_stacks); the placeholders are not
         ctx.mark_non_differentiable(*flags)
         if not want_opd:
             ctx.mark_non_differentiable(opd_out)
@@ -343,23 +343,19 @@ class TraceFunction(torch.autograd.Function):
         # one fp32 tensor per parameter group, written by the reduction kernel (fp64 sums rounded once):
         # autograd can take them as the leaves' .grad without a cast or a clone
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)     # noqa: E731
-        parts = [new(B, S), new(B, S), new(B, W, S), new(B), new(B, F), new(B, F)]
+        g_c, g_t, g_mu, g_z, g_cx, g_cy = new(B, S), new(B, S), new(B, W, S), new(B), new(B, F), new(B, F)
         g_kappa, g_poly = (new(B, S), new(B, S, 4)) if asph else (None, None)
         g_n = new(B, W, S + 1) if gopdd is not None else None
         with _on_device(dev), _Timed("bwd", dev):
+            g = _lib.seeds(gx=gxd, gy=gyd, gcx=gcxd, gcy=gcyd, g_moments=gmd, g_opd=gopdd, g_stacks=gstkd)
+            out = _lib.grads(g_c=g_c, g_t=g_t, g_mu=g_mu, g_z=g_z, g_cx=g_cx, g_cy=g_cy, g_kappa=g_kappa, g_poly=g_poly,
+                             g_n_index=g_n, g_x_in=gxin, g_y_in=gyin)
             if ctx.use_inv:
-                rc = lib.tl_trace_bwd_from_outputs_stacks(
-                    C.byref(prob), _lib.ptr(gstkd), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd), _lib.ptr(gcyd), _lib.ptr(gmd),
-                    _lib.ptr(fx), _lib.ptr(fy), _lib.ptr(fcx), _lib.ptr(fcy), _lib.ptr(fok), _lib.ptr(fmom),
-                    *[_lib.ptr(q) for q in parts[:6]], _lib.ptr(g_kappa), _lib.ptr(g_poly), _lib.ptr(gxin),
-                    _lib.ptr(gyin), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
+                fwd = _lib.rays(x=fx, y=fy, cx=fcx, cy=fcy, ok=fok, moments=fmom)
+                rc = lib.tl_trace_bwd_from_outputs(C.byref(prob), g, fwd, out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
             else:
-                rc = lib.tl_trace_bwd_stacks(C.byref(prob), _lib.ptr(gstkd), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd),
-                                             _lib.ptr(gcyd), _lib.ptr(gmd), _lib.ptr(gopdd), *[_lib.ptr(q) for q in parts[:6]],
-                                             _lib.ptr(g_kappa), _lib.ptr(g_poly), _lib.ptr(g_n), _lib.ptr(gxin), _lib.ptr(gyin),
-                                             _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
+                rc = lib.tl_trace_bwd(C.byref(prob), g, out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
         _lib.check(rc, "tl_trace_bwd")
-        g_c, g_t, g_mu, g_z, g_cx, g_cy = parts
         need = ctx.needs_input_grad
         def fold(g, like):          # [B,F] -> the (possibly broadcast) shape [1|B, 1|F] of cx / cy
             if like.shape[0] == 1 and B > 1:
@@ -401,8 +397,8 @@ class TraceFunctionF64(torch.autograd.Function):
         bp = [new(torch.uint8) for _ in range(2)] if want_rays else [None] * 2
         moments = torch.empty((B * F, TL_NMOM), dtype=torch.float64, device=dev)
         with _on_device(dev):
-            rc = lib.tl_trace_fwd_f64(C.byref(prob), *[_lib.ptr(b) for b in fp], *[_lib.ptr(b) for b in bp], _lib.ptr(moments),
-                                      _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
+            out = _lib.rays(x=fp[0], y=fp[1], cx=fp[2], cy=fp[3], ok=bp[0], back=bp[1], moments=moments)
+            rc = lib.tl_trace_fwd_f64(C.byref(prob), out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
         _lib.check(rc, "tl_trace_fwd_f64")
         ctx.save_for_backward(x_e, y_e, z, cx, cy, c, t, mu, mask_u8, kappa, poly, kind_u8)
         ctx.allow_back = allow_back
@@ -440,10 +436,10 @@ class TraceFunctionF64(torch.autograd.Function):
         g_c, g_t, g_mu, g_z, g_cx, g_cy = new(B, S), new(B, S), new(B, W, S), new(B), new(B, F), new(B, F)
         g_kappa, g_poly = (new(B, S), new(B, S, 4)) if asph else (None, None)
         with _on_device(dev):
-            rc = lib.tl_trace_bwd_f64(C.byref(prob), _lib.ptr(gxd), _lib.ptr(gyd), _lib.ptr(gcxd), _lib.ptr(gcyd), _lib.ptr(gmd),
-                                      _lib.ptr(g_c), _lib.ptr(g_t), _lib.ptr(g_mu), _lib.ptr(g_z), _lib.ptr(g_cx), _lib.ptr(g_cy),
-                                      _lib.ptr(g_kappa), _lib.ptr(g_poly), _lib.ptr(gxin), _lib.ptr(gyin), _lib.ptr(ws), ws.numel(),
-                                      _stream_ptr(dev))
+            g = _lib.seeds(gx=gxd, gy=gyd, gcx=gcxd, gcy=gcyd, g_moments=gmd)
+            out = _lib.grads(g_c=g_c, g_t=g_t, g_mu=g_mu, g_z=g_z, g_cx=g_cx, g_cy=g_cy, g_kappa=g_kappa, g_poly=g_poly,
+                             g_x_in=gxin, g_y_in=gyin)
+            rc = lib.tl_trace_bwd_f64(C.byref(prob), g, out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
         _lib.check(rc, "tl_trace_bwd_f64")
 
         def fold(g, like):
