@@ -356,6 +356,39 @@ int tl_trace_bwd_f64(const tl_problem *p, const tl_seeds *g, const tl_grads *out
                      void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * PSF soft histogram of a ray fan and its adjoint (the contraction inside compute_psf, ray_tracing.py:206-270; additive
+ * entry points, ABI unchanged).  G grids (lens x field), W channels, R rays; ray r of (g, w) is element
+ * g s_g + w s_w + r of x, y (and of weight / ok, gx / gy): rays contiguous, s_g and s_w element strides -- the tracer's
+ * [B,F,W,P] outputs are taken as they are (s_g = W P, s_w = P).  Per grid, in pitch units
+ *     u = x / x_pitch[g],   v = (y - y_centre[g]) / y_pitch[g],
+ *     Gx_j = exp(-2 (u - (x_first + j))^2), j < nxh,    Gy_i = exp(-2 (v - (y_first + i))^2), i < ny
+ * (a Gaussian of sigma = half a pixel at every pixel centre), and
+ *     hist[g,w,i,j] = sum_r wt_r Gy_i(r) Gx_j(r)      the un-mirrored, un-normalised half kernel, float [G,W,ny,nxh].
+ * wt_r = weight[r] (float, nullable), or ok[r] != 0 (the tracer's ray_ok bytes, nullable), or 1; not both (TL_EINVAL).  A ray
+ * of weight 0 adds exactly 0, whatever its coordinates.
+ * Forward: fp32 MFMA tiles in k-ordered FMA chains of <= 1024 rays, one fp32 partial per block in the workspace, summed in a
+ * fixed order in fp64 and rounded once: the same bits on every run, no atomics.
+ * Backward: g_hist [G,W,ny,nxh] -> gx, gy (strided like x, y; OVERWRITTEN; 0 for a ray of weight 0) = d/dx_r, d/dy_r, and,
+ * each nullable, [G] floats reduced in a fixed order in fp64:
+ *     g_x_pitch[g] = -sum_r gx_r x_r / x_pitch,  g_y_pitch[g] = -sum_r gy_r (y_r - y_centre) / y_pitch,  g_y_centre[g] = -sum_r gy_r,
+ * so a grid sized from the data (pitch from the fan's extent, centre from its mean) differentiates through.  The weights carry
+ * no gradient.
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, nxh or ny outside 1..32,
+ * G W > 65535, R < 1, weight and ok both given.  TL_EWORKSPACE: fewer bytes than tl_psf_workspace_bytes asks for (one size
+ * serves both calls; 0 for arguments out of range).  No host synchronisation; caller-owned buffers; re-entrant.
+ */
+size_t tl_psf_workspace_bytes(int32_t G, int32_t W, int64_t R, int32_t nxh, int32_t ny);
+int tl_psf_accumulate(int32_t device, int32_t G, int32_t W, int64_t R, const float *x, const float *y, const float *weight,
+                      const uint8_t *ok, int64_t s_g, int64_t s_w, const float *x_pitch, const float *y_pitch,
+                      const float *y_centre, int32_t nxh, int32_t ny, float x_first, float y_first, float *hist,
+                      void *workspace, size_t workspace_bytes, void *stream);
+int tl_psf_accumulate_bwd(int32_t device, int32_t G, int32_t W, int64_t R, const float *x, const float *y, const float *weight,
+                          const uint8_t *ok, int64_t s_g, int64_t s_w, const float *x_pitch, const float *y_pitch,
+                          const float *y_centre, int32_t nxh, int32_t ny, float x_first, float y_first, const float *g_hist,
+                          float *gx, float *gy, float *g_x_pitch, float *g_y_pitch, float *g_y_centre, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
+/*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of
  * `mode` use.  Strict mode promises the correctly rounded (IEEE) results on the operand ranges of the trace, from shorter
  * instruction sequences than the compiler's general ones: tests/test_gpu_arith.py holds it to that, bit for bit.

@@ -95,6 +95,12 @@ _SIGNATURES = {
     "tl_selftest_arith": (C.c_int, [C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "tl_ray_aim": (C.c_int, [C.c_int32] * 5 + [_VP] * 12 + [C.c_int32] + [_VP] * 4),
     "tl_ray_aim_iter": (C.c_int, [C.c_int32] * 5 + [_VP] * 12 + [C.c_int32] * 2 + [_VP] * 6),
+    "tl_psf_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    # device, G, W, R | x, y, weight, ok | s_g, s_w | x_pitch, y_pitch, y_centre | nxh, ny | x_first, y_first | ...
+    "tl_psf_accumulate": (C.c_int, [C.c_int32] * 3 + [C.c_int64] + [_VP] * 4 + [C.c_int64] * 2 + [_VP] * 3 + [C.c_int32] * 2
+                          + [C.c_float] * 2 + [_VP] + _WS),
+    "tl_psf_accumulate_bwd": (C.c_int, [C.c_int32] * 3 + [C.c_int64] + [_VP] * 4 + [C.c_int64] * 2 + [_VP] * 3 + [C.c_int32] * 2
+                              + [C.c_float] * 2 + [_VP] * 6 + _WS),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -40,6 +40,7 @@ UNITS = {
     "tl_fast.hip": ["-ffp-contract=fast"],
     "tl_api.hip": [],
     "tl_f64.hip": [],          # the double-precision twin (generic, untuned)
+    "tl_psf.hip": [],          # the PSF soft histogram (fp32 MFMA forward, per-ray backward)
 }
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 

@@ -371,6 +371,12 @@ __global__ __launch_bounds__(kBlock) void spot_seed_kernel(int P, int W, const f
 
 }  // namespace
 
+// the calling thread's error message, for the other translation units that hold C-ABI entry points (tl_psf.hip)
+namespace tl_host {
+int fail(int code, const char *msg) { return ::fail(code, "%s", msg); }
+int hip_fail(int herr, const char *where) { return ::hip_fail(herr, where); }
+}
+
 // =================================================================== C ABI
 // Paraxial entrance-pupil position (the `z` argument of the trace): z = B/A of the ordered product
 // M = M_{K-1} ... M_0 of the rows in front of the stop, M_k = [[1 + P t, r t], [P, r]], r = n_k / n_{k+1},

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from . import paraxial
+from . import ops, paraxial
 from .ray_tracing import RayTracer, apply_vignetting
 
 
@@ -78,7 +78,7 @@ def compute_ray_aiming_error(specs, lens, rel_fields, vig_fn=None, n_ray_aiming_
     return ys / rs - y
 
 
-def compute_psf(x, y, n_bins=(21, 21), increment=None, y_target=None, weights=None, y_extent="reference"):
+def compute_psf(x, y, n_bins=(21, 21), increment=None, y_target=None, weights=None, y_extent="reference", fused=False):
     """Soft-histogram PSF of a ray fan on a per-field pixel grid (the reference's TensorFlow
     `compute_psf`, ray_tracing.py:206-270; unreachable in its PyTorch port, PARITY UNPINNED).
 
@@ -101,14 +101,28 @@ def compute_psf(x, y, n_bins=(21, 21), increment=None, y_target=None, weights=No
 
     The double sum over rays and pixels is a contraction over the ray index, so it is evaluated as one batched
     GEMM  G_y [ny, R] @ G_x^T [R, nx]  per (grid, channel) instead of the reference's [.., ny, nx, R] tensor.
+
+    `fused=True` (opt-in; float32 tensors on the GPU only, at most 32 bins per axis): that GEMM and its two operands
+    [g, w, bins, r] -- 128 B per ray at 21 x 21, kept by autograd -- are replaced by one HIP kernel that holds them in
+    registers (ops.PsfAccumulateFunction: fp32 MFMA forward, per-ray backward; differentiable in x, y and through a grid
+    sized from the data; `weights` carry no gradient there and may be bool / uint8: the tracer's ray_ok as it is).  The
+    rest -- y_target, grid sizing, mirroring, normalisation, accounted_ray_proportion -- is the same code below.  The
+    default (`fused=False`) is unchanged: any device, any float dtype.
     """
     nw, nr = x.shape[-2], x.shape[-1]
     n_grids = x.shape[0] * x.shape[1]
     n_x_bins, n_y_bins = n_bins
+    if fused:
+        if n_x_bins > ops.PSF_MAX_BINS or n_y_bins > ops.PSF_MAX_BINS:
+            raise ValueError(f"compute_psf(fused=True) takes at most {ops.PSF_MAX_BINS} bins per axis, got {tuple(n_bins)}")
+        if not (x.is_cuda and y.is_cuda) or x.dtype != torch.float32 or y.dtype != torch.float32:
+            raise RuntimeError(f"compute_psf(fused=True): x is {x.dtype} on {x.device}; the fused PSF runs only as a HIP "
+                               "kernel on float32 tensors on an AMD GPU (there is no CPU fallback): use fused=False")
     x = x.reshape(n_grids, nw, nr)
     y = y.reshape(n_grids, nw, nr)
     if y_target is None:
         y_target = y.reshape(n_grids, -1).mean(dim=1)
+    y_rays = y                                          # the fused kernel centres y itself (y_target's gradient comes from it)
     y = y - y_target[:, None, None]
     if increment is not None:
         x_incr = y_incr = torch.ones(n_grids, dtype=x.dtype, device=x.device) * increment
@@ -126,6 +140,14 @@ def compute_psf(x, y, n_bins=(21, 21), increment=None, y_target=None, weights=No
             raise ValueError("y_extent must be 'reference' or 'centred'")
         x_incr = x_size / n_x_bins
         y_incr = y_size / n_y_bins
+    if fused:
+        # pixel centres x_incr (x_first + j), y_target + y_incr (y_first + i): the grids below, in pitch units
+        nxh, x_first = (n_x_bins // 2 + 1, 0.0) if n_x_bins % 2 == 1 else (n_x_bins // 2, 0.5)
+        wts = None if weights is None else weights.reshape(n_grids, nw, nr)
+        pitch = lambda p: p.to(torch.float32) if torch.is_tensor(p) else torch.full((n_grids,), float(p), dtype=x.dtype, device=x.device)  # noqa: E731
+        kernels = ops.PsfAccumulateFunction.apply(x, y_rays, wts, pitch(x_incr), pitch(y_incr), y_target.to(torch.float32),
+                                                  nxh, n_y_bins, x_first, 0.5 - n_y_bins / 2)
+        return _finish_psf(kernels, n_x_bins, x, y, x_size, y_size, y_target, n_grids)
     rng = lambda n: torch.arange(n, dtype=x.dtype, device=x.device)                 # noqa: E731
     if n_x_bins % 2 == 1:
         gx = rng(n_x_bins // 2 + 1)[None, :] * x_incr[:, None]
@@ -138,6 +160,11 @@ def compute_psf(x, y, n_bins=(21, 21), increment=None, y_target=None, weights=No
     if weights is not None:
         g_y = g_y * weights.reshape(n_grids, nw, 1, nr).to(g_y.dtype)
     kernels = torch.matmul(g_y, g_x.transpose(-1, -2))                               # [g, w, ny, nx_half]
+    return _finish_psf(kernels, n_x_bins, x, y, x_size, y_size, y_target, n_grids)
+
+
+def _finish_psf(kernels, n_x_bins, x, y, x_size, y_size, y_target, n_grids):
+    """Mirror the half kernel [g, w, ny, nx_half] in x, normalise each channel, count the rays inside the grid (y centred)."""
     if n_x_bins % 2 == 1:
         kernels = torch.cat((torch.flip(kernels[..., 1:], dims=(-1,)), kernels), dim=-1)
     else:
@@ -149,11 +176,13 @@ def compute_psf(x, y, n_bins=(21, 21), increment=None, y_target=None, weights=No
     return x_size, y_size, y_target, kernels, accounted.to(x.dtype).mean(dim=(-1, -2))
 
 
-def psf_from_trace(x, y, ray_ok=None, n_bins=(21, 21), increment=None, y_target=None, y_extent="centred"):
+def psf_from_trace(x, y, ray_ok=None, n_bins=(21, 21), increment=None, y_target=None, y_extent="centred", fused=False):
     """compute_psf on the outputs of RayTracer.trace_rays / trace_skew ([1, F, P, W]; their memory is already
     [F, W, P], so the permutation below is free).  With `ray_ok` failed rays are left out of the histogram and of
     the default y_target (the reference counts them as rays at the origin).  An extension with no counterpart in the
-    reference: the automatic grid is sized on the centred spot (`y_extent="centred"`, see compute_psf)."""
+    reference: the automatic grid is sized on the centred spot (`y_extent="centred"`, see compute_psf).
+    `fused=True`: compute_psf's HIP kernel; it reads x, y in the tracer's memory layout and ray_ok as its bytes (no float
+    copy of the flags goes to the kernel; the weighted default y_target is computed as before)."""
     xt, yt = x.permute(0, 1, 3, 2), y.permute(0, 1, 3, 2)
     w = None
     if ray_ok is not None:
@@ -161,4 +190,7 @@ def psf_from_trace(x, y, ray_ok=None, n_bins=(21, 21), increment=None, y_target=
         if y_target is None:
             n_g = yt.shape[0] * yt.shape[1]
             y_target = (yt * w).reshape(n_g, -1).sum(dim=1) / w.reshape(n_g, -1).sum(dim=1).clamp_min(1)
-    return compute_psf(xt, yt, n_bins=n_bins, increment=increment, y_target=y_target, weights=w, y_extent=y_extent)
+    if fused and ray_ok is not None:
+        w = ray_ok.permute(0, 1, 3, 2)
+    return compute_psf(xt, yt, n_bins=n_bins, increment=increment, y_target=y_target, weights=w, y_extent=y_extent,
+                       fused=fused)

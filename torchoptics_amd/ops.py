@@ -531,6 +531,85 @@ class SpotMomentsFunction(torch.autograd.Function):
         return gx, gy, None
 
 
+PSF_MAX_BINS = 32          # rows / columns of the half kernel tl_psf_accumulate takes (one 32x32 MFMA tile)
+
+
+class PsfAccumulateFunction(torch.autograd.Function):
+    """hist [G,W,ny,nxh] = sum_r wt_r Gy_i(r) Gx_j(r): the un-mirrored, un-normalised half kernel of the soft-histogram PSF
+    (tl_psf_accumulate / tl_psf_accumulate_bwd; metrics.compute_psf(fused=True)).
+
+    x, y [G,W,R] float32 on the GPU (rays contiguous; a [F,W,P] view of the tracer's outputs is taken as it is);
+    weight: None, a float tensor (per-ray weights) or a bool / uint8 tensor (the tracer's ray_ok, passed as bytes), same
+    shape; x_pitch, y_pitch, y_centre [G]; the pixel centres are x_pitch (x_first + j), y_centre + y_pitch (y_first + i).
+    Differentiable in x, y, x_pitch, y_pitch and y_centre; the weights carry NO gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, x_pitch, y_pitch, y_centre, nxh, ny, x_first, y_first):
+        for name, ten in (("x", x), ("y", y), ("x_pitch", x_pitch), ("y_pitch", y_pitch), ("y_centre", y_centre)):
+            _require_device(ten, name)
+            if ten.dtype != torch.float32:
+                raise RuntimeError(f"torchoptics_amd: the fused PSF takes float32 tensors; `{name}` is {ten.dtype} "
+                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        if not (1 <= nxh <= PSF_MAX_BINS and 1 <= ny <= PSF_MAX_BINS):
+            raise ValueError(f"the fused PSF takes 1..{PSF_MAX_BINS} bins per axis of the half kernel (got {ny} x {nxh})")
+        dev = x.device
+        G, W, R = x.shape
+        if x.stride(2) != 1 or any(s == 0 for s in x.stride()[:2]):
+            x = x.contiguous()
+        if y.stride() != x.stride():
+            y = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev).copy_(y)
+        wf = wb = None
+        if weight is not None:
+            _require_device(weight, "weight")
+            if weight.dtype in (torch.bool, torch.uint8):
+                wb = weight.view(torch.uint8) if weight.dtype == torch.bool else weight
+            else:
+                wf = weight.detach().to(torch.float32)
+            wt = wb if wb is not None else wf
+            if wt.shape != x.shape:
+                raise ValueError("the fused PSF: weights must have the shape of x")
+            if wt.stride() != x.stride():
+                wt = torch.empty_strided(x.shape, x.stride(), dtype=wt.dtype, device=dev).copy_(wt)
+            wf, wb = (None, wt) if wb is not None else (wt, None)
+        xp, yp, yc = (a.detach().reshape(G).contiguous() for a in (x_pitch, y_pitch, y_centre))
+        lib = _lib.lib()
+        nbytes = lib.tl_psf_workspace_bytes(G, W, R, nxh, ny)
+        ws = _workspace(nbytes, dev)
+        hist = torch.empty((G, W, ny, nxh), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            rc = lib.tl_psf_accumulate(dev.index, G, W, R, _lib.ptr(x), _lib.ptr(y), _lib.ptr(wf), _lib.ptr(wb),
+                                       x.stride(0), x.stride(1), _lib.ptr(xp), _lib.ptr(yp), _lib.ptr(yc), nxh, ny,
+                                       float(x_first), float(y_first), _lib.ptr(hist), _lib.ptr(ws), ws.numel(),
+                                       _stream_ptr(dev))
+        _lib.check(rc, "tl_psf_accumulate")
+        ctx.save_for_backward(x, y, wf, wb, xp, yp, yc)
+        ctx.geom = (nxh, ny, float(x_first), float(y_first), nbytes)
+        ctx.shapes = (x_pitch.shape, y_pitch.shape, y_centre.shape)
+        return hist
+
+    @staticmethod
+    def backward(ctx, g_hist):
+        x, y, wf, wb, xp, yp, yc = ctx.saved_tensors
+        nxh, ny, x_first, y_first, nbytes = ctx.geom
+        dev = x.device
+        G, W, R = x.shape
+        lib = _lib.lib()
+        gh = g_hist.to(torch.float32).contiguous()
+        gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
+        gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        g_xp, g_yp, g_yc = (torch.empty(G, dtype=torch.float32, device=dev) if need[k] else None for k in (3, 4, 5))
+        ws = _workspace(nbytes, dev)
+        with _on_device(dev):
+            rc = lib.tl_psf_accumulate_bwd(dev.index, G, W, R, _lib.ptr(x), _lib.ptr(y), _lib.ptr(wf), _lib.ptr(wb),
+                                           x.stride(0), x.stride(1), _lib.ptr(xp), _lib.ptr(yp), _lib.ptr(yc), nxh, ny,
+                                           x_first, y_first, _lib.ptr(gh), _lib.ptr(gx), _lib.ptr(gy), _lib.ptr(g_xp),
+                                           _lib.ptr(g_yp), _lib.ptr(g_yc), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
+        _lib.check(rc, "tl_psf_accumulate_bwd")
+        g_xp, g_yp, g_yc = (g if g is None else g.reshape(s) for g, s in zip((g_xp, g_yp, g_yc), ctx.shapes))
+        return (gx if need[0] else None, gy if need[1] else None, None, g_xp, g_yp, g_yc, None, None, None, None)
+
+
 class PupilPositionFunction(torch.autograd.Function):
     """z [B] = paraxial entrance-pupil position from the rows in front of the stop: c, t [B,K], n [B,K+1]
     (tl_pupil_position: one tiny kernel forward, one backward, one thread per lens; mode 'strict': the value is the
