@@ -70,6 +70,10 @@ Plan plan_fwd(const tl_problem *p)
     return make_plan(p->P, rows_bfw(p), cap, rmax, few, rwant);
 }
 
+// the checkpoint launch queued behind a walk-back (tl_trace_bwd_from_outputs): it normally retires at once, and a quarter of
+// the blocks keeps that idle launch cheap
+Plan plan_bwd_fallback(const tl_problem *p) { return make_plan(p->P, rows_bfw(p), 1024, 256); }
+
 Plan plan_bwd(const tl_problem *p)
 {
     // 16 rays per lane once there is work for >= 4096 such blocks (8 per lane and 2048 blocks in the forward): the
@@ -721,11 +725,12 @@ static unsigned *poison_word(const tl_problem *p, void *workspace)
 size_t tl_workspace_bytes(const tl_problem *p)
 {
     if (!p || p->F < 1 || p->W < 1 || p->S < 1 || p->P < 0) return 0;
-    const Plan pf = plan_fwd(p), pb = plan_bwd(p);
+    const Plan pf = plan_fwd(p), pb = plan_bwd(p), pk = plan_bwd_fallback(p);
     const int ns = tl_bwd_bucket(p->S);
     const size_t fw = (size_t)rows_bfw(p);
     const size_t a = fw * pf.nbx * TL_NMOM * sizeof(double);
-    const size_t b = fw * pb.nbx * (size_t)tl_bwd_row(ns < 0 ? TL_MAX_SURFACES : ns, p->surf_kind != nullptr) * sizeof(double);
+    // (the fallback's grid is the smaller one under the default plan; TL_PLAN_FEW / TL_PLAN_R can make it the larger)
+    const size_t b = fw * (pb.nbx > pk.nbx ? pb.nbx : pk.nbx) * (size_t)tl_bwd_row(ns < 0 ? TL_MAX_SURFACES : ns, p->surf_kind != nullptr) * sizeof(double);
     const size_t c = fw * pb.nbx * (size_t)((p->surf_kind ? 8 : 3) * p->S + 3) * sizeof(double);   // walk-back kernel next to its fallback
     // + the penalty walk-back's scan map, right below the 256-byte slack at the end (the poison word lives in that slack)
     const size_t scan = tl_scanmap_bytes(rows_bfw(p), ((int64_t)p->P + kBlock - 1) / kBlock);
@@ -854,8 +859,7 @@ int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_r
     hipError_t e = hipSetDevice(p->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     const Plan pl = plan_bwd(p);
-    // the fallback is launched too and normally retires at once: a quarter of the blocks keeps that idle launch cheap
-    const Plan pk = make_plan(p->P, rows_bfw(p), 1024, 256);
+    const Plan pk = plan_bwd_fallback(p);              // the fallback is launched too
     const bool asph = p->surf_kind != nullptr;
     const int ncol = (asph ? 8 : 3) * p->S + 3, ns = tl_bwd_bucket(p->S), ncol_ck = tl_bwd_row(ns, asph);
     const size_t rows = (size_t)rows_bfw(p) * pl.nbx, rows_ck = (size_t)rows_bfw(p) * pk.nbx;

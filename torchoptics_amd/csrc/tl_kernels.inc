@@ -73,6 +73,10 @@ __device__ __forceinline__ float uload(const float *__restrict__ q, const int i)
 {
     return ((const __attribute__((address_space(4))) float *)(unsigned long long)q)[i];
 }
+__device__ __forceinline__ double uload64(const double *__restrict__ q, const int i)
+{
+    return ((const __attribute__((address_space(4))) double *)(unsigned long long)q)[i];
+}
 
 // ------------------------------------------------------------------ math policy
 // STRICT (TL_FAST = 0, TU built with -ffp-contract=off) promises the reference's fp32 operation order for the
@@ -916,6 +920,13 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
     float *__restrict__ hits = ASPH ? p.asph_hits : nullptr;
     const int hit_slots = ASPH ? p.asph_hit_slots : 0;
     const size_t n_rays_all = (size_t)gridDim.y * p.P;
+    // ASPH: which optional outputs are there, as bits of ONE scalar that is made opaque per ray below.  As plain pointer
+    // tests they are hoisted out of the ray loop as nine wave-uniform booleans of two SGPRs each, and with the aspheric
+    // rows' pointers that is more than the scalar file holds (13 spills to VGPR lanes, re-read per ray).  What is still
+    // spilled with PEN or OPD is written before the ray loop and read after it.
+    const unsigned out_bits_all = !ASPH ? 0u : (unsigned)__builtin_amdgcn_readfirstlane((int)(
+        (ox ? 1u : 0u) | (oy ? 2u : 0u) | (ocx ? 4u : 0u) | (ocy ? 8u : 0u) | (ook ? 16u : 0u) | (oback ? 32u : 0u) |
+        (p.cond_flags ? 64u : 0u) | (part ? 128u : 0u) | (want_x ? 256u : 0u) | (oopd ? 512u : 0u)));
 
     // per-lane sums: the value moments in fp64, the three counts (ok, back, ill-conditioned) as integers
     double m[TL_NMOM];
@@ -937,6 +948,9 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
     for (int r = 0; r < R; ++r) {
         const int64_t ip = (c0 + r) * kBlock + threadIdx.x;
         const bool valid = ip < p.P;
+        unsigned out_bits = out_bits_all;
+        if (ASPH) asm("" : "+s"(out_bits) : "s"(r));
+        auto has = [&](const unsigned bit, const bool there) { return ASPH ? (out_bits & bit) != 0 : there; };
         Ray ray;
         ray.x = x_nxt;
         ray.y = y_nxt;
@@ -1019,21 +1033,21 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
         }
         if (valid) {
             const int64_t o = (int64_t)fw * p.P + ip;
-            if (ox) ox[o] = xo;
-            if (oy) oy[o] = yo;
-            if (ocx) ocx[o] = ray.cx;
-            if (ocy) ocy[o] = ray.cy;
-            if (ook) ook[o] = ok ? 1 : 0;
-            if (oback) oback[o] = back ? 1 : 0;
-            if (p.cond_flags) p.cond_flags[o] = alive ? (min_cos2 < kCondThr ? 2 : 1) : 0;  // 2: the rays moment 9 counts
-            if (OPD && oopd) oopd[o] = alive ? opd + uload(n_w, S) * dist : 0.0f;
-            if (part) {
+            if (has(1u, ox != nullptr)) ox[o] = xo;
+            if (has(2u, oy != nullptr)) oy[o] = yo;
+            if (has(4u, ocx != nullptr)) ocx[o] = ray.cx;
+            if (has(8u, ocy != nullptr)) ocy[o] = ray.cy;
+            if (has(16u, ook != nullptr)) ook[o] = ok ? 1 : 0;
+            if (has(32u, oback != nullptr)) oback[o] = back ? 1 : 0;
+            if (has(64u, p.cond_flags != nullptr)) p.cond_flags[o] = alive ? (min_cos2 < kCondThr ? 2 : 1) : 0;  // 2: the rays moment 9 counts
+            if (OPD && has(512u, oopd != nullptr)) oopd[o] = alive ? opd + uload(n_w, S) * dist : 0.0f;
+            if (has(128u, part != nullptr)) {
                 // (ok differs from alive only where backward rays are not allowed; the squares are exact in fp64)
                 const double yd = (double)yo, ykd = (double)(ok ? yo : 0.0f);
                 m[0] += yd; m[1] += ykd; m[2] = __builtin_fma(ykd, ykd, m[2]);
                 n_ok += ok ? 1 : 0; n_back += back ? 1 : 0;
                 n_ill += (alive && min_cos2 < kCondThr) ? 1 : 0;
-                if (want_x) {           // compute_rms2d reads y only (:684-701); the 2-D spot radius asks for these
+                if (has(256u, want_x)) {           // compute_rms2d reads y only (:684-701); the 2-D spot radius asks for these
                     const double xd = (double)xo, xkd = (double)(ok ? xo : 0.0f);
                     m[4] += xd; m[5] += xkd; m[6] = __builtin_fma(xkd, xkd, m[6]);
                 }
@@ -1846,12 +1860,16 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
 // 7-row Cooke triplet; from ~13 rows up the 2 NS KB of LDS per block cost more waves than the unrolling wins
 // (20 rows: equal; hence the pair-shared slots from 13 rows on, below); launch_bwd_inv uses it for
 // kInvUnrollMin <= S <= kInvUnrollMax and the rolled kernel otherwise.
-// Three compiler habits the code below works around, each measured on this kernel:
+// Four compiler habits the code below works around, each measured on this kernel:
 //  * a `#pragma unroll` loop promotes the per-row arrays to <NS x float> VECTORS before it unrolls, and vector-typed
 //    registers with their tuple copies cost 8-20 VGPRs per row: hence static_for_down with a std::integral_constant;
 //  * whatever depends on the row alone (mu^2, 2c ...; uniform, but computed by the VALU, so a VGPR each) is hoisted
 //    out of the ray loop, +5 VGPRs per row: hence the LDS index laundered through an empty asm that "reads" the
 //    carried state (NOT volatile: that would be a memory clobber and turn the scalar loads into vector loads);
+//  * (ASPH) whatever is affine in the ray index or invariant in the ray loop gets a register of its own across the loop:
+//    a running pointer per array and plane, a lane mask per row-kind test, base + lane per array in a VGPR pair; on an
+//    aspheric lens that was 116 SGPRs spilled to VGPR lanes and read back per ray and row: hence the chunk offset, the
+//    row bits and the lane's byte offset laundered once per ray (at the top of the ray loop);
 //  * g_c, g_t, g_mu feed nothing but the sums, so they are sunk to the END of the ray together with the ~20
 //    intermediates each row needs for them (scratch spills from NS = 3 on; __builtin_amdgcn_sched_barrier is no
 //    help, the order is lost before the machine scheduler): hence the empty volatile asm at the end of a row that
@@ -1939,11 +1957,11 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
     const int tid = threadIdx.x;
     TL_LENS_ROW(pa);
     TL_BLOCK_CHUNKS(p.P);
-    const unsigned kbits = ASPH ? row_bits(p.surf_kind, NS) : 0u;
+    const unsigned kbits_all = ASPH ? row_bits(p.surf_kind, NS) : 0u;
     const int hit_slots = ASPH ? p.asph_hit_slots : 0;
     const float *__restrict__ hits = ASPH ? p.asph_hits : nullptr;
     const size_t n_rays_all = (size_t)gridDim.y * p.P;
-    if (ASPH && (hits == nullptr || __popc(kbits) > hit_slots)) {      // (block-uniform) not enough hit slots for this lens
+    if (ASPH && (hits == nullptr || __popc(kbits_all) > hit_slots)) {      // (block-uniform) not enough hit slots for this lens
         if (tid == 0) *poison = token;
         return;
     }
@@ -1952,12 +1970,15 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
     const float cz0 = tl_sqrt_any((1.0f - cx0 * cx0) - cy0 * cy0);
     const float *__restrict__ mu_w = p.mu + (size_t)w * NS;
     const int64_t xoff = f * p.xs_f + w * p.xs_w, yoff = f * p.ys_f + w * p.ys_w;
+    // the six fp64 seed factors of this field.  ASPH: re-read per ray through the scalar cache instead (uload64 below):
+    // held across the row code they are 12 SGPRs which the aspheric rows need
+    const double *const gm_f = gmom ? gmom + (size_t)gf * TL_NMOM : nullptr;
     double gm0 = 0, gm1 = 0, gm2 = 0, gm4 = 0, gm5 = 0, gm6 = 0;
-    if (gmom) {
-        const double *q = gmom + (size_t)gf * TL_NMOM;
-        gm0 = q[0]; gm1 = q[1]; gm2 = q[2]; gm4 = q[4]; gm5 = q[5]; gm6 = q[6];
-    }
+    if (!ASPH && gmom) { gm0 = gm_f[0]; gm1 = gm_f[1]; gm2 = gm_f[2]; gm4 = gm_f[4]; gm5 = gm_f[5]; gm6 = gm_f[6]; }
     const float gq = (PEN && gmom) ? (float)gmom[(size_t)gf * TL_NMOM + 8] : 0.0f;
+    // which of the optional per-ray seed arrays are there (none on the moment-seeded path), as bits of one scalar
+    const unsigned seed_bits = !ASPH ? 0u : (unsigned)__builtin_amdgcn_readfirstlane(
+        (int)((gx ? 1u : 0u) | (gy ? 2u : 0u) | (gcx ? 4u : 0u) | (gcy ? 8u : 0u)));
     float r_c[NS];                                              // the g_c sums of this lane
 #pragma unroll
     for (int j = 0; j < NS; ++j) r_c[j] = 0.0f;
@@ -1992,18 +2013,37 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
         const unsigned rem = left < (int64_t)kBlock ? (unsigned)left : (unsigned)kBlock;
         const unsigned ut = (unsigned)tid;
         const bool valid = ut < rem;
-        const int64_t ob = (int64_t)fw * p.P + chunk;
+        // `ob`, the element offset of this chunk in every [B,F,W][P] array, is the ONE quantity that advances per ray: each
+        // address below is formed from it where it is used (base + ob [+ a uniform plane offset], scalar adds).  The empty
+        // asm hides how it depends on r: otherwise loop strength reduction keeps a running 64-bit pointer per array and
+        // plane, 32 of them on an aspheric lens, advanced in the latch and spilled to VGPR lanes.  The row bits, the plane
+        // stride, the seed-factor pointer and the seed bits go through it too, so that what depends on them alone (the
+        // per-row kind tests, k * stride, the factors) is evaluated where it is used, on the scalar unit, and not hoisted
+        // out of the ray loop into SGPRs held across it (a wave-uniform bool held there is a lane mask: two SGPRs each).
+        // (NOT volatile: see the header.)  The all-spherical variants keep their code to the instruction.
+        int64_t ob = (int64_t)fw * p.P + chunk;
+        unsigned kbits = kbits_all;
+        const double *gm = gm_f;
+        size_t nra = n_rays_all;
+        unsigned sbits = seed_bits;
+        if (ASPH) asm("" : "+s"(ob), "+s"(kbits), "+s"(gm), "+s"(nra), "+s"(sbits));
+        // this lane's element of a [P] row at a wave-uniform address.  ASPH: the lane part as a 32-bit BYTE offset, which
+        // selects the `saddr` form of the load (uniform base in SGPRs + one VGPR); indexed by element, the lane part is
+        // widened first and every load forms a 64-bit address in a VGPR pair
+        unsigned ut4 = ut * 4u;
+        if (ASPH) asm("" : "+v"(ut4) : "s"(r));       // (or base + lane is kept per array across the ray loop, a VGPR pair each)
+        auto LD = [&](const float *q) { return ASPH ? *(const float *)((const char *)q + ut4) : q[ut]; };
         bool alive = false;
         float xi = 0.0f, yi = 0.0f, dx = 0.0f, dy = 0.0f;       // position at the image plane, direction leaving row S-1
         float sx = 0.0f, sy = 0.0f, scx = 0.0f, scy = 0.0f;     // seeds (same as trace_bwd_kernel; the forward's own x, y)
         if (valid) {
             alive = ((fok + ob)[ut] & 1) != 0;                          // (2: ill-conditioned, the checkpoint pass takes it.  `& 1`,
                                                                         //  not `== 1`: that form costs 2 VGPRs and 32 B of scratch at NS = 11)
-            xi = (fx + ob)[ut]; yi = (fy + ob)[ut]; dx = (fcx + ob)[ut]; dy = (fcy + ob)[ut];
-            if (gx) sx = (gx + ob)[ut];
-            if (gy) sy = (gy + ob)[ut];
-            if (gcx) scx = (gcx + ob)[ut];
-            if (gcy) scy = (gcy + ob)[ut];
+            xi = LD(fx + ob); yi = LD(fy + ob); dx = LD(fcx + ob); dy = LD(fcy + ob);
+            if (ASPH ? (sbits & 1u) != 0 : gx != nullptr) sx = LD(gx + ob);
+            if (ASPH ? (sbits & 2u) != 0 : gy != nullptr) sy = LD(gy + ob);
+            if (ASPH ? (sbits & 4u) != 0 : gcx != nullptr) scx = LD(gcx + ob);
+            if (ASPH ? (sbits & 8u) != 0 : gcy != nullptr) scy = LD(gcy + ob);
         }
         // dead lanes: a harmless axial ray with zero seeds; its terms are exact zeros.  No wave-level skip here: a
         // second path through the loop makes the allocator keep two copies of every register sum and shuffle them
@@ -2017,6 +2057,10 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
         const float gq_l = (PEN && alive) ? gq : 0.0f;          // PEN: rays that died on the way belong to the checkpoint pass
         float dz = tl_sqrt_hw(1.0f - (dx * dx + dy * dy));
         if (gmom) {
+            if (ASPH) {
+                gm0 = uload64(gm, 0); gm1 = uload64(gm, 1); gm2 = uload64(gm, 2);
+                gm4 = uload64(gm, 4); gm5 = uload64(gm, 5); gm6 = uload64(gm, 6);
+            }
             sy += alive ? (float)(gm0 + (gm1 + 2.0 * (double)yi * gm2)) : 0.0f;
             sx += alive ? (float)(gm4 + (gm5 + 2.0 * (double)xi * gm6)) : 0.0f;
         }
@@ -2036,9 +2080,9 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
         // the stored hit of this lane's ray on the aspheric row with `below_` aspheric rows before it
 #define TL_LOAD_HIT(below_, PX, PY)                                                      \
         {                                                                                \
-            const float *hp_ = hits + ((size_t)(2 * (below_)) * n_rays_all + (size_t)ob); \
+            const float *hp_ = hits + ((size_t)(2 * (below_)) * nra + (size_t)ob);       \
             PX = 0.0f; PY = 0.0f;                                                        \
-            if (valid) { PX = hp_[ut]; PY = (hp_ + n_rays_all)[ut]; }                    \
+            if (valid) { PX = LD(hp_); PY = LD(hp_ + nra); }                             \
             PX = alive ? PX : 0.0f; PY = alive ? PY : 0.0f;                              \
         }
         Adj a;
@@ -2098,9 +2142,9 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
             const bool zpos = PEN && (hz - t_k) > 0.0f;                      // zRELU of this row is active
             PenSeed sk = pen_seed(gq_l);                                     // this row's seeds of zRELU, theta, theta'
             if (STK) {                                                       // (kPenRay) + the stacks' seeds of this ray
-                const float *sq_ = gstk + ((size_t)k * n_rays_all + (size_t)ob);
+                const float *sq_ = gstk + ((size_t)k * nra + (size_t)ob);
                 float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-                if (valid) { s0 = sq_[ut]; s1 = (sq_ + (size_t)NS * n_rays_all)[ut]; s2 = (sq_ + (size_t)(2 * NS) * n_rays_all)[ut]; }
+                if (valid) { s0 = LD(sq_); s1 = LD(sq_ + (size_t)NS * nra); s2 = LD(sq_ + (size_t)(2 * NS) * nra); }
                 sk.z += alive ? s0 : 0.0f; sk.th += alive ? s1 : 0.0f; sk.thp += alive ? s2 : 0.0f;
             }
             StepVals v;
@@ -2293,13 +2337,13 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
     if (ASPH) {
         // g_kappa[k] -> column 3NS+3+k ; g_poly[k][j] -> column 4NS+3+4k+j.  Slot j holds this lens' j-th aspheric row:
         // lanes = 0, 1, 2 (mod 4) of the even slot row hold kappa, a4, a6, lanes = 0, 1 of the odd one a8, a10.
-        if (tid < NS && !((kbits >> tid) & 1u)) {                  // spherical rows: zeros
+        if (tid < NS && !((kbits_all >> tid) & 1u)) {                  // spherical rows: zeros
             row[(size_t)(3 * NS + 3 + tid) * nrows_] = 0.0;
             for (int j = 0; j < 4; ++j) row[(size_t)(4 * NS + 3 + 4 * tid + j) * nrows_] = 0.0;
         }
         int j = 0;
         for (int k = 0; k < NS; ++k) {
-            if (!((kbits >> k) & 1u)) continue;                    // wave-uniform
+            if (!((kbits_all >> k) & 1u)) continue;                    // wave-uniform
             if ((j & (kWaves - 1)) == wv) {
                 const float *qa = sasph_dyn + (size_t)(2 * j) * kBlock, *qb = qa + kBlock;
                 double va = (double)qa[lane] + (double)qa[lane + 64];
