@@ -110,6 +110,17 @@ def test_double_precision_with_ray_aiming_and_a_lens_batch(ta):
     assert per_lens.shape == (2,) and per_lens.dtype == torch.float64
     per_lens.sum().backward()
     assert torch.isfinite(leaves["c"].grad).all() and leaves["c"].grad[:7].abs().max() > 0 and leaves["c"].grad[7:].abs().max() > 0
+    # each lens of the batch = the same lens traced alone in double precision (the same kernel on the same rays): 1e-12
+    g_batch = leaves["c"].grad.double().cpu()
+    for b, (name, rows) in enumerate((("cooke", slice(0, 7)), ("doublet", slice(7, 12)))):
+        l1, s1, lv1 = L.build(name, DEV)
+        o1 = tr.trace_rays(s1, l1)
+        r1 = ta.compute_rms2d(o1[0], o1[1], o1[4])
+        assert r1.dtype == torch.float64
+        assert abs(per_lens[b].item() - r1.item()) <= 1e-12 * r1.item(), (name, per_lens[b].item(), r1.item())
+        r1.backward()
+        e = rel_l2(g_batch[rows].numpy(), lv1["c"].grad.double().cpu().numpy())
+        assert e <= 1e-12, f"d/dc of {name} in the batch vs alone: {e:.2e}"
 
 
 def test_double_precision_refuses_what_it_does_not_have(ta):

@@ -8,6 +8,8 @@
 // spherical rows, Newton to convergence from the closed-form conic hit for aspheric rows (the oracle's definition), adjoint
 // = the same chain rule as step_vals / step_adjoint / asph_vals / asph_adjoint of the fp32 kernels.  No penalty term, no
 // optical path length here (the C entry points refuse them).
+// Identity padding rows (c = 0, t = 0, mu = 1, mask 0: a shorter lens in a padded batch) are passed through: flags and
+// gradients as the oracle's, the ray state untouched, so that a padded lens equals the un-padded one bit for bit.
 #include "tl_common.h"
 
 namespace tl_f64 {
@@ -64,8 +66,11 @@ __device__ __forceinline__ void sag_terms(const Asph &A, const double rho, doubl
     dsag = A.c / (2.0 * q) + rho * (2.0 * A.a0 + rho * (3.0 * A.a1 + rho * (4.0 * A.a2 + rho * (5.0 * A.a3))));
 }
 
+// `ident`: an identity padding row (is_identity below).  Its tests run like any row's (the flags are the oracle's), but the
+// ray is left where it is instead of being moved to the row's vertex plane: the rows behind it then see the state they see
+// in the un-padded lens, and a lens padded to a batch's row count gives the un-padded lens's outputs bit for bit.
 __device__ void step_fwd(Ray &r, bool &ok, bool &back, const double c, const double t, const double mu, const bool asph,
-                         const Asph &A, const bool chk, const bool allow_back, double &min_cos2)
+                         const Asph &A, const bool chk, const bool allow_back, double &min_cos2, const bool ident = false)
 {
     double X, Y, Z, dz, cos_i, nx, ny, nz;
     bool miss;
@@ -123,8 +128,23 @@ __device__ void step_fwd(Ray &r, bool &ok, bool &back, const double c, const dou
         ok = ok && !(hit && !allow_back);
     }
     ok = ok && !fail;
+    if (ident) return;
     r.x = X; r.y = Y; r.z = Z - t;
     r.cx = cx3; r.cy = cy3; r.cz = sqrt(fail ? 1.0 : czsq);
+}
+
+// a padding row of a batch of lenses of different length: flat, no gap, no index step, not part of the sequence
+__device__ __forceinline__ bool is_identity(const View &v, const double *mu_w, const int k)
+{
+    return !(v.kind && v.kind[k]) && v.c[k] == 0.0 && v.t[k] == 0.0 && mu_w[k] == 1.0 && !v.mask[k];
+}
+
+// marching distance of a ray to the vertex plane of a flat row (step_fwd with c = 0)
+__device__ __forceinline__ double flat_march(const Ray &r)
+{
+    const double e = -((r.x * r.cx + r.y * r.cy) + r.z * r.cz);
+    const double mz = r.z + e * r.cz;
+    return e + (-2.0 * mz) / (r.cz + sqrt(r.cz * r.cz));
 }
 
 __device__ __forceinline__ Asph load_asph(const View &v, const int k)
@@ -177,7 +197,8 @@ __global__ __launch_bounds__(kBlock) void fwd_kernel(const tl_problem p, double 
         double min_cos2 = 1.0;
         for (int k = 0; k < S; ++k) {
             const bool asph = v.kind && v.kind[k];
-            step_fwd(ray, ok, back, v.c[k], v.t[k], mu_w[k], asph, load_asph(v, k), k > 0 && v.mask[k - 1], allow_back, min_cos2);
+            step_fwd(ray, ok, back, v.c[k], v.t[k], mu_w[k], asph, load_asph(v, k), k > 0 && v.mask[k - 1], allow_back, min_cos2,
+                     is_identity(v, mu_w, k));
         }
         const double dz = -ray.z, dist = dz / ray.cz;
         const bool alive = ok;
@@ -373,7 +394,8 @@ __global__ __launch_bounds__(kBlock) void bwd_kernel(const tl_problem p, const d
         Ray ck[TL_MAX_SURFACES];
         for (int k = 0; k < S; ++k) {
             ck[k] = ray;
-            step_fwd(ray, ok, back, v.c[k], v.t[k], mu_w[k], v.kind && v.kind[k], load_asph(v, k), k > 0 && v.mask[k - 1], allow_back, mc);
+            step_fwd(ray, ok, back, v.c[k], v.t[k], mu_w[k], v.kind && v.kind[k], load_asph(v, k), k > 0 && v.mask[k - 1], allow_back, mc,
+                     is_identity(v, mu_w, k));
         }
         const int64_t o = (int64_t)fw * p.P + ip;
         const bool alive = ok;
@@ -402,6 +424,18 @@ __global__ __launch_bounds__(kBlock) void bwd_kernel(const tl_problem p, const d
         for (int k = S - 1; k >= 0; --k) {
             const double zout = (k + 1 < S) ? ck[k + 1].z : z_last;
             double g_c, g_t, g_mu, g5[5];
+            if (is_identity(v, mu_w, k)) {
+                // The forward left the ray where it was, so `a` is the adjoint of the state ENTERING the row already and
+                // stays.  d/dt and d/dmu of the row are those of the row as the oracle traces it (the ray moved by d to the
+                // vertex plane): step_bwd on the adjoint carried to that point, a_dir - d a_pos.  d/dc of a flat row that
+                // bends nothing is zero.
+                const double d = flat_march(ck[k]);
+                Adj m = a;
+                m.cx -= d * a.x; m.cy -= d * a.y; m.cz -= d * a.z;
+                step_bwd(ck[k], zout, v.c[k], v.t[k], mu_w[k], false, load_asph(v, k), m, g_c, g_t, g_mu, g5);
+                a_t[k] += g_t; a_mu[k] += g_mu;
+                continue;
+            }
             step_bwd(ck[k], zout, v.c[k], v.t[k], mu_w[k], v.kind && v.kind[k], load_asph(v, k), a, g_c, g_t, g_mu, g5);
             a_c[k] += g_c; a_t[k] += g_t; a_mu[k] += g_mu;
             a_k[k] += g5[0];
