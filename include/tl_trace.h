@@ -389,6 +389,54 @@ int tl_psf_accumulate_bwd(int32_t device, int32_t G, int32_t W, int64_t R, const
                           size_t workspace_bytes, void *stream);
 
 /*
+ * Spatially varying overlap-add PSF convolution of an image and its adjoints (imaging.svola_convolution(fused=True);
+ * additive entry points, ABI unchanged).  The image [B,H,W,C] is cut into a gh x gw grid of overlapping patches of
+ * ph = H/gh + 2 oh rows and pw = W/gw + 2 ow columns in the frame of Ih = H + 2 oh rows and Iw = W + 2 ow columns (the image
+ * plus the overlap margin); patch n = i gw + j owns frame rows [r0[i], r1[i]) and columns [c0[j], c1[j]).  With P the image
+ * extended by symmetric reflection (-1-i -> i, H+i -> H-1-i) and a = kh/2, b = kw/2,
+ *     out[b,y,x,c] = sum_n w_n(y + oh, x + ow) sum_{i<kh, j<kw} psfs[b,n,i,j,c] P[b, y + a - i, x + b - j, c],
+ *     w_n(r, q)    = wr[i][r] wc[j][q]
+ * where wr [gh][Ih] and wc [gw][Iw] are DEVICE tables of doubles: the window of patch row i (column j) at frame row r
+ * (column q), 0 outside the patch, already divided by the sum over the patches of that axis (the window is separable, so
+ * the 2-D normalisation is the product of the two).  r0, r1, c0, c1 are HOST arrays of gh / gw ints, non-decreasing; every
+ * row and column of the central H x W must lie inside a patch.  Element strides address image (b, y, x, c), psfs and g_psfs
+ * (b, n, i, j, c); psf_batch is B or 1 (PSFs shared by the batch: g_psfs is then the sum over b).  out, g_out and g_image
+ * are contiguous [B,H,W,C] floats.
+ *   tl_svola_fwd        out.  One block per tile of <= 32 x 32 pixels that no patch edge crosses, so the covering patches
+ *                       are block-uniform: the tile plus halo is staged in LDS with the reflection resolved in the index,
+ *                       the taps come through the scalar cache.  No workspace.
+ *   tl_svola_bwd_psf    g_psfs = d/d psfs of sum(g_out out).  Per-tile partials in the workspace, summed in a fixed order
+ *                       in fp64 and rounded once: the same bits on every run, no atomics.
+ *   tl_svola_bwd_image  g_image = d/d image: the correlation of w_n g_out with the PSFs on the extended frame (workspace),
+ *                       then each pixel gathers its own value and those of its mirror images.  No atomics.
+ * TL_EINVAL before any HIP call, with the function's name and the argument in the message: a required pointer NULL, kh or
+ * kw even or > 31, oh + kh/2 > H or ow + kw/2 > W, gh or gw outside 1..128, psf_batch not 1 or B, patch bounds that are not
+ * ph (pw) long, decreasing or outside the frame, an uncovered row or column.  TL_EWORKSPACE: fewer bytes than
+ * tl_svola_workspace_bytes asks for (one size serves both backward calls; 0 for arguments out of range).  No host
+ * synchronisation; caller-owned buffers; the launches go on `stream`.
+ */
+typedef struct tl_svola_geom {
+    int32_t device;
+    int32_t B, H, W, C;               /* image [B,H,W,C] */
+    int32_t psf_batch;                /* B, or 1: PSFs shared by the batch */
+    int32_t gh, gw, kh, kw, oh, ow;
+    int64_t image_stride[4];          /* elements: b, y, x, c */
+    int64_t psfs_stride[5];           /* elements: b, n, i, j, c */
+    int64_t g_psfs_stride[5];         /* elements: b, n, i, j, c (tl_svola_bwd_psf) */
+} tl_svola_geom;
+
+size_t tl_svola_workspace_bytes(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, const int32_t *c0,
+                                const int32_t *c1);
+int tl_svola_fwd(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, const int32_t *c0, const int32_t *c1,
+                 const double *wr, const double *wc, const float *image, const float *psfs, float *out, void *stream);
+int tl_svola_bwd_psf(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, const int32_t *c0, const int32_t *c1,
+                     const double *wr, const double *wc, const float *image, const float *g_out, float *g_psfs,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int tl_svola_bwd_image(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, const int32_t *c0, const int32_t *c1,
+                       const double *wr, const double *wc, const float *psfs, const float *g_out, float *g_image,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of
  * `mode` use.  Strict mode promises the correctly rounded (IEEE) results on the operand ranges of the trace, from shorter
  * instruction sequences than the compiler's general ones: tests/test_gpu_arith.py holds it to that, bit for bit.

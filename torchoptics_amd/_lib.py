@@ -68,11 +68,19 @@ def _from_tensors(cls):
 
 rays, seeds, grads = _from_tensors(tl_rays), _from_tensors(tl_seeds), _from_tensors(tl_grads)
 
+class tl_svola_geom(C.Structure):
+    _fields_ = [("device", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("psf_batch", C.c_int32), ("gh", C.c_int32), ("gw", C.c_int32), ("kh", C.c_int32), ("kw", C.c_int32),
+                ("oh", C.c_int32), ("ow", C.c_int32),
+                ("image_stride", C.c_int64 * 4), ("psfs_stride", C.c_int64 * 5), ("g_psfs_stride", C.c_int64 * 5)]
+
+
 _lock = threading.Lock()
 _lib = None
 
 _P, _R, _S, _G = C.POINTER(tl_problem), C.POINTER(tl_rays), C.POINTER(tl_seeds), C.POINTER(tl_grads)
 _WS = [_VP, C.c_size_t, _VP]        # workspace, workspace_bytes, stream
+_SV = C.POINTER(tl_svola_geom)
 _SIGNATURES = {
     "tl_version": (C.c_int, []),
     "tl_last_error": (C.c_char_p, []),
@@ -101,6 +109,11 @@ _SIGNATURES = {
                           + [C.c_float] * 2 + [_VP] + _WS),
     "tl_psf_accumulate_bwd": (C.c_int, [C.c_int32] * 3 + [C.c_int64] + [_VP] * 4 + [C.c_int64] * 2 + [_VP] * 3 + [C.c_int32] * 2
                               + [C.c_float] * 2 + [_VP] * 6 + _WS),
+    # geom, r0, r1, c0, c1 (host ints) | wr, wc (device doubles) | ...
+    "tl_svola_workspace_bytes": (C.c_size_t, [_SV] + [_VP] * 4),
+    "tl_svola_fwd": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + [_VP]),
+    "tl_svola_bwd_psf": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + _WS),
+    "tl_svola_bwd_image": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + _WS),
 }
 EXPORTS = tuple(_SIGNATURES)
 

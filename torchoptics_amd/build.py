@@ -41,6 +41,7 @@ UNITS = {
     "tl_api.hip": [],
     "tl_f64.hip": [],          # the double-precision twin (generic, untuned)
     "tl_psf.hip": [],          # the PSF soft histogram (fp32 MFMA forward, per-ray backward)
+    "tl_svola.hip": [],        # the spatially varying PSF convolution of an image and its adjoints
 }
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 

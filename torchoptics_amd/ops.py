@@ -610,6 +610,92 @@ class PsfAccumulateFunction(torch.autograd.Function):
         return (gx if need[0] else None, gy if need[1] else None, None, g_xp, g_yp, g_yc, None, None, None, None)
 
 
+SVOLA_MAX_TAPS = 31       # rows / columns of a PSF the tl_svola_* kernels take (tile plus halo in LDS)
+SVOLA_MAX_GRID = 128      # patches per axis
+
+# C-ABI calls of SvolaFunction since import (tests: the image backward runs only when the image needs a gradient), and the
+# psfs pointer the last forward handed to the kernel (a strided view goes through as it is: no copy)
+_svola_calls = {"fwd": 0, "bwd_psf": 0, "bwd_image": 0, "psfs_ptr": None}
+
+
+def svola_counts() -> dict:
+    """{'fwd': n, 'bwd_psf': n, 'bwd_image': n, 'psfs_ptr': data pointer of the last forward's psfs}."""
+    return dict(_svola_calls)
+
+
+class SvolaFunction(torch.autograd.Function):
+    """out [B,H,W,C] = the spatially varying overlap-add convolution of image [B,H,W,C] with psfs [B or 1,N,kh,kw,C]
+    (tl_svola_fwd / tl_svola_bwd_psf / tl_svola_bwd_image; imaging.svola_convolution(fused=True), which checks the arguments).
+
+    float32 on one GPU; both tensors are taken with the strides they have.  `geo` is imaging.svola_geometry(...): the patch
+    bounds as host ints and the normalised per-axis window tables, uploaded once per device as doubles.  Differentiable in
+    image and psfs; the image backward is launched only when the image needs a gradient."""
+
+    @staticmethod
+    def _geom(geo, image, psfs, g_psfs=None):
+        B, H, W, Cc = image.shape
+        q = _lib.tl_svola_geom(device=image.device.index, B=B, H=H, W=W, C=Cc, psf_batch=psfs.shape[0], gh=geo.gh, gw=geo.gw,
+                               kh=psfs.shape[2], kw=psfs.shape[3], oh=geo.oh, ow=geo.ow)
+        q.image_stride[:] = image.stride()
+        q.psfs_stride[:] = psfs.stride()
+        q.g_psfs_stride[:] = (g_psfs if g_psfs is not None else psfs).stride()
+        return q
+
+    @staticmethod
+    def _tables(geo, dev):
+        tabs = geo.device_tables.get(dev)
+        if tabs is None:
+            tabs = geo.device_tables[dev] = (torch.from_numpy(geo.tab_r).to(dev), torch.from_numpy(geo.tab_c).to(dev))
+        return tabs
+
+    @staticmethod
+    def forward(ctx, image, psfs, geo):
+        ctx.set_materialize_grads(False)
+        dev = image.device
+        wr, wc = SvolaFunction._tables(geo, dev)
+        out = torch.empty(image.shape, dtype=torch.float32, device=dev)
+        q = SvolaFunction._geom(geo, image, psfs)
+        with _on_device(dev):
+            rc = _lib.lib().tl_svola_fwd(C.byref(q), *geo.bounds, _lib.ptr(wr), _lib.ptr(wc), _lib.ptr(image), _lib.ptr(psfs),
+                                         _lib.ptr(out), _stream_ptr(dev))
+        _lib.check(rc, "tl_svola_fwd")
+        _svola_calls["fwd"] += 1
+        _svola_calls["psfs_ptr"] = psfs.data_ptr()
+        ctx.save_for_backward(image, psfs)
+        ctx.geo = geo
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need_image, need_psfs = ctx.needs_input_grad[:2]
+        if g_out is None or not (need_image or need_psfs):
+            return None, None, None
+        image, psfs = ctx.saved_tensors
+        geo, dev = ctx.geo, image.device
+        wr, wc = SvolaFunction._tables(geo, dev)
+        lib = _lib.lib()
+        g_out = g_out.to(torch.float32).contiguous()
+        g_image = g_psfs = None
+        if need_psfs:
+            g_psfs = torch.empty(psfs.shape, dtype=torch.float32, device=dev)
+        q = SvolaFunction._geom(geo, image, psfs, g_psfs)
+        nbytes = lib.tl_svola_workspace_bytes(C.byref(q), *geo.bounds)
+        ws = _workspace(nbytes, dev)
+        with _on_device(dev):
+            if need_psfs:
+                rc = lib.tl_svola_bwd_psf(C.byref(q), *geo.bounds, _lib.ptr(wr), _lib.ptr(wc), _lib.ptr(image), _lib.ptr(g_out),
+                                          _lib.ptr(g_psfs), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
+                _lib.check(rc, "tl_svola_bwd_psf")
+                _svola_calls["bwd_psf"] += 1
+            if need_image:
+                g_image = torch.empty(image.shape, dtype=torch.float32, device=dev)
+                rc = lib.tl_svola_bwd_image(C.byref(q), *geo.bounds, _lib.ptr(wr), _lib.ptr(wc), _lib.ptr(psfs), _lib.ptr(g_out),
+                                            _lib.ptr(g_image), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
+                _lib.check(rc, "tl_svola_bwd_image")
+                _svola_calls["bwd_image"] += 1
+        return g_image, g_psfs, None
+
+
 class PupilPositionFunction(torch.autograd.Function):
     """z [B] = paraxial entrance-pupil position from the rows in front of the stop: c, t [B,K], n [B,K+1]
     (tl_pupil_position: one tiny kernel forward, one backward, one thread per lens; mode 'strict': the value is the
