@@ -11,20 +11,13 @@ import pytest
 import torch
 
 from conftest import ROOT
+import svola_cases as sc
 import svola_ref as ref
 
 from torchoptics_amd import _lib, imaging
 
-# B, H, W, C, grid, PSF, overlap, window, psf_batch -- the shapes of tests/test_gpu_svola.py
-SHAPES = {
-    "odd-boxcar": (2, 23, 29, 2, (2, 3), (5, 3), (2, 3), "boxcar", None),
-    "odd-hann": (2, 23, 29, 2, (2, 3), (5, 3), (2, 3), "hann", None),
-    "taps31": (1, 40, 40, 1, (1, 2), (31, 31), (0, 4), "boxcar", None),
-    "tiles-hann": (1, 70, 131, 3, (3, 4), (7, 7), (5, 5), "hann", None),
-    "cover3": (1, 24, 24, 1, (4, 4), (3, 3), (5, 5), "boxcar", None),
-    "shared-psfs": (3, 23, 29, 2, (2, 3), (5, 3), (2, 3), "hann", 1),
-    "degenerate": (1, 8, 8, 1, (1, 1), (1, 1), (0, 0), "boxcar", None),
-}
+# The shared table (tests/svola_cases.py); this file has always named the shapes without their number.
+SHAPES = {name.split("-", 1)[1]: case for name, case in sc.CASES.items()}
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -163,7 +156,8 @@ def _calls(dll, q, bounds, ptrs=None, ws=ONE, ws_bytes=1 << 30):
 
 BAD_GEOM = [(dict(kh=4), b"kh"), (dict(kw=2), b"kw"), (dict(kh=33), b"kh"), (dict(kw=33), b"kw"),      # even or > 31
             (dict(oh=22), b"oh"), (dict(ow=29), b"ow"),                                                 # the padding rule
-            (dict(gh=0), b"gh"), (dict(gw=129), b"gw"), (dict(pb=3), b"psf_batch"), (dict(B=0), b"B"), (dict(Cc=0), b"C")]
+            (dict(gh=0), b"gh"), (dict(gw=129), b"gw"), (dict(pb=3), b"psf_batch"), (dict(B=0), b"B"), (dict(Cc=0), b"C"),
+            (dict(Cc=65536), b"C <= 65535")]                                   # one more than a launch's grid z
 
 
 @pytest.mark.parametrize("bad,word", BAD_GEOM, ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) if isinstance(v, dict) else "")
@@ -225,8 +219,42 @@ def test_workspace_grows_with_the_batch_and_every_test_shape_plans():
         b = _bounds(H, W, grid[0], grid[1], ov[0], ov[1])
         one = dll.tl_svola_workspace_bytes(C.byref(q), *b)
         assert one >= B * Cc * (H + k[0] - 1) * (W + k[1] - 1) * 4, name
+        assert one == sc.workspace_bytes(B, H, W, Cc, grid, k, ov), name        # the planner's tiles under every patch
         q8 = _geom(8 * B, H, W, Cc, 8 * B if pb is None else 1, grid[0], grid[1], k[0], k[1], ov[0], ov[1])
         assert dll.tl_svola_workspace_bytes(C.byref(q8), *b) > one, name
+        assert dll.tl_svola_workspace_bytes(C.byref(q8), *b) == sc.workspace_bytes(8 * B, H, W, Cc, grid, k, ov), name
+
+
+def test_the_chunked_shapes_have_more_tiles_than_one_launch_takes():
+    """The tile counts that make shapes 8 to 12 run more than one chunk on the GPU, from the Python statement of the tile
+    cutting that test_workspace_... holds the planner to; and that statement on an axis small enough to do by hand."""
+    # 70 rows, 3 patches of 33 at 0, 24, 47 of an 80-row frame, centre [5, 75): cells [5,24) [24,33) [33,47) [47,57) [57,75)
+    assert sc.cut_tiles(70, 3, 5) == (5, [2, 3, 2])
+    # 100 rows, one patch: four tiles of 25
+    assert sc.cut_tiles(100, 1, 0) == (4, [4])
+    for name, (rows, cols) in sc.TILE_COUNTS.items():
+        B, H, W, Cc, grid, k, ov, win, pb = sc.CASES[name]
+        assert (sc.cut_tiles(H, grid[0], ov[0])[0], sc.cut_tiles(W, grid[1], ov[1])[0]) == (rows, cols), name
+        assert max(rows, cols) > sc.MAX_SEG, name
+    rows, cols = sc.TILE_COUNTS["12-both-chunked"]
+    assert rows > sc.MAX_SEG and cols > sc.MAX_SEG
+    tiles, under = sc.cut_tiles(384, 128, 1)
+    assert tiles - under[-1] > 2 * sc.MAX_SEG                 # the last patch starts in the third chunk (first_c > 192)
+
+
+def test_the_torch_path_is_the_reference_on_the_fuzz_geometries():
+    """The seeded draws of the GPU fuzz test through fused=False in float64: uneven geometries, both windows."""
+    kept, skipped = sc.fuzz_survivors(imaging.svola_geometry)
+    assert skipped <= sc.FUZZ_MAX_SKIPPED and len(kept) + skipped == sc.FUZZ_DRAWS, skipped
+    for t, (B, H, W, Cc, grid, k, ov, win) in kept:
+        image, psfs, g_out = ref.make_case(B, H, W, Cc, grid, k, seed=t)
+        want = ref.ref_with_grads(image, ov, psfs, grid, win, g_out)
+        im, ps = image.clone().requires_grad_(True), psfs.clone().requires_grad_(True)
+        out = imaging.svola_convolution(im, ov, ps, grid, win, fused=False)
+        (out * g_out).sum().backward()
+        for what, got, exp in zip(("out", "g_image", "g_psfs"), (out.detach(), im.grad, ps.grad), want):
+            err = ((got - exp).abs().max() / exp.abs().max()).item()
+            assert err <= 1e-12, (t, (B, H, W, Cc, grid, k, ov, win), what, err)
 
 
 # ------------------------------------------------------------------------------------------------------- Python layer
