@@ -129,3 +129,35 @@ def test_double_precision_refuses_what_it_does_not_have(ta):
     mask = torch.from_numpy(g["in_mask"]).to(DEV)
     with pytest.raises(NotImplementedError):
         ta.trace_skew(*ins, mask, True, True)
+
+
+@pytest.mark.parametrize("aspheric", [False, True])
+def test_fp64_backward_under_saved_tensor_hooks(ta, aspheric):
+    """The fp64 sibling of test_gpu_parity.test_backward_under_saved_tensor_hooks: the backward reuses the tl_problem
+    filled in forward, and under saved-tensor hooks the unpacked tensors live in OTHER storage, so the problem must be
+    rebuilt from them.  One step under torch.autograd.graph.save_on_cpu() gives the gradients of the plain step, bit for
+    bit (same kernel, same inputs, same launch shape: nothing may differ)."""
+    g = load_golden("G2_cooke_16x16")
+    ins = [torch.from_numpy(g[n]).double() for n in IN]
+    mask = torch.from_numpy(g["in_mask"]).to(DEV)
+    allow = bool(g.get("allow_backward_rays", True))
+    kap0, pol0, _kind = asphere_params(ins[5].shape[-1], torch.float64)
+    gen = torch.Generator().manual_seed(5)
+    seed = (torch.randn(g["x"].shape, generator=gen, dtype=torch.float64) * 1e-3).to(DEV)
+    res = []
+    for hooks in (False, True):
+        lv = [ins[i].to(DEV).clone().requires_grad_(True) for i in (2, 4, 5, 6, 7)]            # z, cy, c, t, mu
+        kw = {}
+        if aspheric:
+            lv += [kap0.to(DEV).clone().requires_grad_(True), pol0.to(DEV).clone().requires_grad_(True)]
+            kw = dict(kappa=lv[5], poly=lv[6])
+        xin = ins[0].to(DEV).clone().requires_grad_(True)
+        with (torch.autograd.graph.save_on_cpu() if hooks else torch.enable_grad()):
+            o = ta.trace_skew(xin, ins[1].to(DEV), lv[0], ins[3].to(DEV), lv[1], lv[2], lv[3], lv[4], mask, False, allow, **kw)
+            assert o[0].dtype == torch.float64
+            loss = ta.compute_rms2d(o[0], o[1], o[4]) + (o[0] * seed).sum()
+        loss.backward()
+        res.append([q.grad.clone() for q in lv + [xin]])
+    assert len(res[0]) == (8 if aspheric else 6)
+    for a, b in zip(*res):
+        assert a.abs().max().item() > 0 and torch.equal(a, b)

@@ -286,3 +286,71 @@ def test_memo_key_tells_aliasing_views_and_fields_apart():
     cc, tt = torch.full((8,), 2.0), torch.full((8,), 3.0)
     lens = lm.Lens(st, cc, tt, nd, v)
     assert (lens.c[0] == 2.0).all() and (lens.t[0] == 3.0).all() and lens.c[1, 3:].eq(0).all()
+
+
+def test_call_helper_marshals_arguments_checks_the_code_and_times(monkeypatch):
+    """ops._call, the one place that talks to a launching C-ABI entry, against a stub library (no GPU): tensors arrive
+    as c_void_p of their data_ptr(), None as None, an empty tensor as NULL, ints / floats / byref structs unchanged, the
+    stream last; a non-zero code raises '<entry> failed (code N): <last error>'; timed='fwd' records one pair while
+    timing is on, timed=None none."""
+    import ctypes as C
+    from torchoptics_amd import _lib, ops
+
+    class Stub:
+        def __init__(self):
+            self.seen, self.rc = [], 0
+
+        def tl_fake_entry(self, *args):
+            self.seen.append(args)
+            return self.rc
+
+        def tl_last_error(self):
+            return b"the stub says no"
+
+    class FakeEvent:
+        """Stands for torch.cuda.Event, so that the real ops._Timed runs without a GPU."""
+        def __init__(self, enable_timing=False):
+            self.on = None
+
+        def record(self, on):
+            self.on = on
+
+    stub, dev, stream = Stub(), torch.device("cuda", 0), C.c_void_p(0x5EED)
+    entered = []
+
+    class Guard:
+        def __enter__(self):
+            entered.append("in")
+
+        def __exit__(self, *exc):
+            entered.append("out")
+    monkeypatch.setattr(_lib, "lib", lambda: stub)
+    monkeypatch.setattr(ops, "_on_device", lambda d: Guard())
+    monkeypatch.setattr(ops, "_stream_ptr", lambda d: stream)
+    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda d=None: "the stream of %s" % d)
+    monkeypatch.setattr(ops, "_timing", None)
+
+    t, empty, prob = torch.arange(4.0), torch.empty(0), _lib.tl_problem()
+    ref = C.byref(prob)
+    ops._call("tl_fake_entry", dev, ref, 7, 2.5, t, None, empty)
+    (got,) = stub.seen
+    assert entered == ["in", "out"]
+    assert got[0] is ref and got[1] == 7 and type(got[1]) is int and got[2] == 2.5 and type(got[2]) is float
+    assert isinstance(got[3], C.c_void_p) and got[3].value == t.data_ptr() != 0
+    assert got[4] is None
+    assert isinstance(got[5], C.c_void_p) and got[5].value is None              # NULL
+    assert got[6] is stream and len(got) == 7
+
+    stub.rc = -3
+    with pytest.raises(RuntimeError, match=r"^tl_fake_entry failed \(code -3\): the stub says no$"):
+        ops._call("tl_fake_entry", dev, t)
+
+    stub.rc = 0
+    monkeypatch.setattr(ops, "_timing", {"fwd": [], "bwd": []})
+    ops._call("tl_fake_entry", dev, t, timed="fwd")
+    assert {k: len(v) for k, v in ops._timing.items()} == {"fwd": 1, "bwd": 0}
+    start, stop = ops._timing["fwd"][0]
+    assert start is not stop and start.on == stop.on == "the stream of cuda:0"   # both recorded, on the launch stream
+    ops._call("tl_fake_entry", dev, t, timed=None)
+    assert {k: len(v) for k, v in ops._timing.items()} == {"fwd": 1, "bwd": 0}

@@ -3,8 +3,15 @@ autograd.Function wrappers around the C ABI (include/tl_trace.h).
 
 `TraceFunction` stands where PyTorch autograd's recorded graph of the reference's
 `trace_skew` stood (ray_tracing_lite.py:594-675): forward = one fused HIP kernel,
-backward = one recompute-and-reverse HIP kernel.  `SpotMomentsFunction` is the reduction of
-`compute_rms2d` (ray_tracing_lite.py:678-702) for tensors that did not come from the trace.
+backward = one recompute-and-reverse HIP kernel.  It is the one trace node of both precisions:
+float64 rays select the `_f64` entry points and element type through a `_Precision` record.
+`SpotMomentsFunction` is the reduction of `compute_rms2d` (ray_tracing_lite.py:678-702) for
+tensors that did not come from the trace.
+
+Every launching entry point of the C ABI is reached through `_call`: device guard, optional
+timing events, tensors -> device pointers, the current stream as the last argument, the return
+code checked under the entry point's own name.  Only the sizing entries (`tl_*workspace_bytes*`:
+no stream, no return code) are called directly.
 
 Per-ray buffers are allocated [B, F, W, P] (pupil index contiguous) and handed
 out as [B, F, P, W] permuted views, which is the reference's logical shape.  A batch of B padded
@@ -12,6 +19,7 @@ lenses is ONE launch (tl_problem.B); B = 1 is the reference's callers' case.
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -168,6 +176,17 @@ def _on_device(dev):
     return _NO_CTX if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
+def _call(name, dev, *args, timed=None):
+    """Call the launching C-ABI entry `name` on the current stream of `dev`: tensors go as their device pointers (None ->
+    NULL), everything else (ints, floats, byref structs, pointer blocks) as it is, the stream last.  `timed`: 'fwd' /
+    'bwd' records the call for timing_ms() while enable_timing() is on.  A non-zero return code raises."""
+    with _on_device(dev), (_Timed(timed, dev) if timed is not None else _NO_CTX):
+        rc = getattr(_lib.lib(), name)(*[_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in args],
+                                       _stream_ptr(dev))
+    if rc != 0:
+        _lib.check(rc, name)
+
+
 def _workspace(nbytes: int, device) -> torch.Tensor:
     """Per-(device, stream) scratch for the block partials; grows monotonically."""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
@@ -229,29 +248,48 @@ def _fwp(t):
     return t.permute(0, 1, 3, 2).contiguous()
 
 
+class _Precision(NamedTuple):
+    """What the trace node takes from the element type of its rays."""
+    dtype: torch.dtype        # every float allocation, and the cast of the backward's seeds
+    ws_bytes: str             # the C-ABI entries: workspace size, forward, checkpoint backward
+    fwd: str
+    bwd: str
+    walk_back: bool           # tl_trace_bwd_from_outputs (with its hit-point and conditioning buffers) exists
+    timed: bool               # the calls are recorded by enable_timing()
+
+
+_F32 = _Precision(torch.float32, "tl_workspace_bytes", "tl_trace_fwd", "tl_trace_bwd", True, True)
+# RayTracer(double_precision=True): generic, untuned fp64 kernels, checkpoint backward; no penalty term, no optical path length
+_F64 = _Precision(torch.float64, "tl_workspace_bytes_f64", "tl_trace_fwd_f64", "tl_trace_bwd_f64", False, False)
+
+
 class TraceFunction(torch.autograd.Function):
-    """(x, y, cx, cy, ok, back, moments, opd) = trace(x_in, y_in, z, cx, cy, c, t, mu[, kappa, poly]).
+    """(x, y, cx, cy, ok, back, moments, opd, stacks) = trace(x_in, y_in, z, cx, cy, c, t, mu[, kappa, poly]).
 
     Shapes: x_in, y_in [B,F,P,W] (expanded views welcome), z [B], cx, cy [1|B, 1|F], c, t [B,S], mu [B,W,S],
     mask_u8 [B,S]; kappa [B,S], poly [B,S,4], kind_u8 [B,S] are None for an all-spherical lens (the reference's
-    case); n_index [B,W,S+1] is only needed for the optical path length output (`want_opd`).  moments [B*F, TL_NMOM]."""
+    case); n_index [B,W,S+1] is only needed for the optical path length output (`want_opd`).  moments [B*F, TL_NMOM].
+    float64 rays run the double-precision kernels: every float argument float64, mode 'strict', no `want_opd`, no
+    `aggregate` (trace_skew refuses them), and the x-moments are always filled."""
 
     @staticmethod
     def forward(ctx, x_e, y_e, z, cx, cy, c, t, mu, kappa, poly, mask_u8, kind_u8, n_index, allow_back, mode,
                 want_rays, want_opd, aggregate, want_stacks, moments_x=False):
+        prec = _F64 if x_e.dtype == torch.float64 else _F32
         for name, ten in (("x", x_e), ("y", y_e), ("z", z), ("cx", cx), ("cy", cy), ("c", c), ("t", t),
                           ("mu", mu), ("mask", mask_u8)):
             _require_device(ten, name)
+            if prec is _F64 and name != "mask" and ten.dtype != torch.float64:
+                raise TypeError(f"double-precision trace: `{name}` is {ten.dtype}")
         dev = x_e.device
         B, F, P, W = x_e.shape
         S = c.shape[-1]
         if S > _lib.TL_MAX_SURFACES:
             raise RuntimeError(f"lens has {S} rows; this build supports at most {_lib.TL_MAX_SURFACES}")
-        lib = _lib.lib()
         # per-ray input gradients (ray aiming: a handful of rays) keep the checkpoint algorithm: extreme rays
         # amplify the reconstruction rounding of the walk-back to ~1e-4 in d/dx_in, d/dy_in
         # ... and so does the gradient through the optical path length (only the checkpoint kernel carries it)
-        use_inv = (_bwd_algo == "inverse" and want_rays and allow_back and not want_opd
+        use_inv = (prec.walk_back and _bwd_algo == "inverse" and want_rays and allow_back and not want_opd
                    and not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
         # aspheric rows: the forward leaves their hit points for the walk-back (8 B per ray and slot actually used)
         hits = None
@@ -263,21 +301,18 @@ class TraceFunction(torch.autograd.Function):
                 if use_inv and any(ctx.needs_input_grad[2:10]) else None)
         prob = _problem(x_e, y_e, z, cx, cy, c, t, mu, mask_u8, allow_back, mode, kappa, poly, kind_u8, n_index, aggregate,
                         hits, moments_x, cond)
-        nbytes = lib.tl_workspace_bytes(C.byref(prob))
+        nbytes = getattr(_lib.lib(), prec.ws_bytes)(C.byref(prob))
         ws = _workspace(nbytes, dev)
         if want_rays:
-            fp = [torch.empty((B, F, W, P), dtype=torch.float32, device=dev) for _ in range(4)]
+            fp = [torch.empty((B, F, W, P), dtype=prec.dtype, device=dev) for _ in range(4)]
             bp = [torch.empty((B, F, W, P), dtype=torch.uint8, device=dev) for _ in range(2)]
         else:
             fp, bp = [None] * 4, [None] * 2
-        opd = torch.empty((B, F, W, P), dtype=torch.float32, device=dev) if want_opd else None
-        stacks = torch.empty((3, S, B, F, W, P), dtype=torch.float32, device=dev) if (aggregate and want_stacks) else None
+        opd = torch.empty((B, F, W, P), dtype=prec.dtype, device=dev) if want_opd else None
+        stacks = torch.empty((3, S, B, F, W, P), dtype=prec.dtype, device=dev) if (aggregate and want_stacks) else None
         moments = torch.empty((B * F, TL_NMOM), dtype=torch.float64, device=dev)
-        with _on_device(dev), _Timed("fwd", dev):
-            out = _lib.rays(x=fp[0], y=fp[1], cx=fp[2], cy=fp[3], ok=bp[0], back=bp[1], opd=opd, stacks=stacks,
-                            moments=moments)
-            rc = lib.tl_trace_fwd(C.byref(prob), out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "tl_trace_fwd")
+        out = _lib.rays(x=fp[0], y=fp[1], cx=fp[2], cy=fp[3], ok=bp[0], back=bp[1], opd=opd, stacks=stacks, moments=moments)
+        _call(prec.fwd, dev, C.byref(prob), out, ws, ws.numel(), timed="fwd" if prec.timed else None)
         global _last_use_inv
         _last_use_inv = use_inv
         fwd_out = (fp[0], fp[1], fp[2], fp[3], bp[0], moments) if use_inv else (None,) * 6
@@ -290,10 +325,10 @@ class TraceFunction(torch.autograd.Function):
             outs = [b.permute(0, 1, 3, 2) for b in fp]
             flags = [b.view(torch.bool).permute(0, 1, 3, 2) for b in bp]
         else:
-            outs = [torch.empty(0, device=dev) for _ in range(4)]
+            outs = [torch.empty(0, dtype=prec.dtype, device=dev) for _ in range(4)]
             flags = [torch.empty(0, dtype=torch.bool, device=dev) for _ in range(2)]
-        opd_out = opd.permute(0, 1, 3, 2) if want_opd else torch.empty(0, device=dev)
-        stk_out = stacks.permute(0, 1, 2, 3, 5, 4) if stacks is not None else torch.empty(0, device=dev)
+        opd_out = opd.permute(0, 1, 3, 2) if want_opd else torch.empty(0, dtype=prec.dtype, device=dev)
+        stk_out = stacks.permute(0, 1, 2, 3, 5, 4) if stacks is not None else torch.empty(0, dtype=prec.dtype, device=dev)
         # the stacks are differentiable (their gradient reaches the backward calls as tl_seeds.g_stacks); the placeholders are not
         ctx.mark_non_differentiable(*flags)
         if not want_opd:
@@ -309,18 +344,17 @@ class TraceFunction(torch.autograd.Function):
         dev = x_e.device
         B, F, P, W = x_e.shape
         S = c.shape[-1]
-        n_in = 20
+        prec = _F64 if x_e.dtype == torch.float64 else _F32
         if gopd is not None and (n_index is None or gopd.numel() == 0):
             gopd = None
         # gradient of the per-surface stacks [3,S,B,F,P,W] -> g_stacks [3][S][B,F,W,P], the layout of the forward's output
         gstkd = None
         if ctx.aggregate and gstk is not None and gstk.numel() > 0:
-            gstkd = gstk.to(torch.float32).permute(0, 1, 2, 3, 5, 4).contiguous()
+            gstkd = gstk.to(prec.dtype).permute(0, 1, 2, 3, 5, 4).contiguous()
         if (gx is None and gy is None and gcx is None and gcy is None and gmom is None and gopd is None
                 and gstkd is None):
-            return (None,) * n_in
+            return (None,) * 20
         asph = kind_u8 is not None
-        lib = _lib.lib()
         prob = ctx.prob
         # saved-tensor hooks (save_on_cpu, checkpointing) hand back tensors in other storage than the forward saw
         if (prob.x_in != (x_e.data_ptr() or None) or prob.c != c.data_ptr() or prob.mu != mu.data_ptr()
@@ -334,125 +368,41 @@ class TraceFunction(torch.autograd.Function):
         def dense(g):
             if g is None or g.numel() == 0:
                 return None
-            return _fwp(g.to(torch.float32))
+            return _fwp(g.to(prec.dtype))
         gxd, gyd, gcxd, gcyd, gopdd = dense(gx), dense(gy), dense(gcx), dense(gcy), dense(gopd)
         gmd = None if gmom is None else gmom.to(torch.float64).contiguous()
-        need_xin, need_yin = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gxin = torch.empty((B, F, W, P), dtype=torch.float32, device=dev) if need_xin else None
-        gyin = torch.empty((B, F, W, P), dtype=torch.float32, device=dev) if need_yin else None
-        # one fp32 tensor per parameter group, written by the reduction kernel (fp64 sums rounded once):
-        # autograd can take them as the leaves' .grad without a cast or a clone
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)     # noqa: E731
-        g_c, g_t, g_mu, g_z, g_cx, g_cy = new(B, S), new(B, S), new(B, W, S), new(B), new(B, F), new(B, F)
-        g_kappa, g_poly = (new(B, S), new(B, S, 4)) if asph else (None, None)
-        g_n = new(B, W, S + 1) if gopdd is not None else None
-        with _on_device(dev), _Timed("bwd", dev):
-            g = _lib.seeds(gx=gxd, gy=gyd, gcx=gcxd, gcy=gcyd, g_moments=gmd, g_opd=gopdd, g_stacks=gstkd)
-            out = _lib.grads(g_c=g_c, g_t=g_t, g_mu=g_mu, g_z=g_z, g_cx=g_cx, g_cy=g_cy, g_kappa=g_kappa, g_poly=g_poly,
-                             g_n_index=g_n, g_x_in=gxin, g_y_in=gyin)
-            if ctx.use_inv:
-                fwd = _lib.rays(x=fx, y=fy, cx=fcx, cy=fcy, ok=fok, moments=fmom)
-                rc = lib.tl_trace_bwd_from_outputs(C.byref(prob), g, fwd, out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-            else:
-                rc = lib.tl_trace_bwd(C.byref(prob), g, out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "tl_trace_bwd")
         need = ctx.needs_input_grad
-        def fold(g, like):          # [B,F] -> the (possibly broadcast) shape [1|B, 1|F] of cx / cy
-            if like.shape[0] == 1 and B > 1:
-                g = g.sum(dim=0, keepdim=True)
-            if like.shape[1] == 1 and F > 1:
-                g = g.sum(dim=1, keepdim=True)
-            return g
-        g_cx = fold(g_cx, cx) if need[3] else None
-        g_cy = fold(g_cy, cy) if need[4] else None
-        return (gxin.permute(0, 1, 3, 2) if need_xin else None,
-                gyin.permute(0, 1, 3, 2) if need_yin else None,
-                g_z.reshape(z.shape) if need[2] else None, g_cx.reshape(cx.shape) if need[3] else None,
-                g_cy.reshape(cy.shape) if need[4] else None,
-                g_c.reshape(c.shape), g_t.reshape(t.shape), g_mu.reshape(mu.shape),
-                g_kappa.reshape(kappa.shape) if asph else None, g_poly.reshape(poly.shape) if asph else None,
-                None, None, g_n.reshape(n_index.shape) if g_n is not None else None, None, None, None, None, None, None,
-                None)
-
-
-class TraceFunctionF64(torch.autograd.Function):
-    """The trace in double precision (RayTracer(double_precision=True); tl_trace_fwd_f64 / tl_trace_bwd_f64: generic,
-    untuned fp64 kernels, checkpoint backward).  Same argument shapes as TraceFunction with float64 tensors; no penalty
-    term, no optical path length.  Returns (x, y, cx, cy, ok, back, moments)."""
-
-    @staticmethod
-    def forward(ctx, x_e, y_e, z, cx, cy, c, t, mu, kappa, poly, mask_u8, kind_u8, allow_back, want_rays):
-        for name, ten in (("x", x_e), ("y", y_e), ("z", z), ("cx", cx), ("cy", cy), ("c", c), ("t", t), ("mu", mu)):
-            _require_device(ten, name)
-            if ten.dtype != torch.float64:
-                raise TypeError(f"double-precision trace: `{name}` is {ten.dtype}")
-        dev = x_e.device
-        B, F, P, W = x_e.shape
-        lib = _lib.lib()
-        prob = _problem(x_e, y_e, z, cx, cy, c, t, mu, mask_u8, allow_back, "strict", kappa, poly, kind_u8)
-        nbytes = lib.tl_workspace_bytes_f64(C.byref(prob))
-        ws = _workspace(nbytes, dev)
-        new = lambda dt: torch.empty((B, F, W, P), dtype=dt, device=dev)      # noqa: E731
-        fp = [new(torch.float64) for _ in range(4)] if want_rays else [None] * 4
-        bp = [new(torch.uint8) for _ in range(2)] if want_rays else [None] * 2
-        moments = torch.empty((B * F, TL_NMOM), dtype=torch.float64, device=dev)
-        with _on_device(dev):
-            out = _lib.rays(x=fp[0], y=fp[1], cx=fp[2], cy=fp[3], ok=bp[0], back=bp[1], moments=moments)
-            rc = lib.tl_trace_fwd_f64(C.byref(prob), out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "tl_trace_fwd_f64")
-        ctx.save_for_backward(x_e, y_e, z, cx, cy, c, t, mu, mask_u8, kappa, poly, kind_u8)
-        ctx.allow_back = allow_back
-        ctx.set_materialize_grads(False)
-        if want_rays:
-            outs = [b.permute(0, 1, 3, 2) for b in fp]
-            flags = [b.view(torch.bool).permute(0, 1, 3, 2) for b in bp]
-        else:
-            outs = [torch.empty(0, dtype=torch.float64, device=dev) for _ in range(4)]
-            flags = [torch.empty(0, dtype=torch.bool, device=dev) for _ in range(2)]
-        ctx.mark_non_differentiable(*flags)
-        return (*outs, *flags, moments)
-
-    @staticmethod
-    def backward(ctx, gx, gy, gcx, gcy, _gok, _gback, gmom):
-        x_e, y_e, z, cx, cy, c, t, mu, mask_u8, kappa, poly, kind_u8 = ctx.saved_tensors
-        if gx is None and gy is None and gcx is None and gcy is None and gmom is None:
-            return (None,) * 14
-        dev = x_e.device
-        B, F, P, W = x_e.shape
-        S = c.shape[-1]
-        asph = kind_u8 is not None
-        lib = _lib.lib()
-        prob = _problem(x_e, y_e, z, cx, cy, c, t, mu, mask_u8, ctx.allow_back, "strict", kappa, poly, kind_u8)
-        ws = _workspace(lib.tl_workspace_bytes_f64(C.byref(prob)), dev)
-
-        def dense(g):
-            return None if g is None or g.numel() == 0 else _fwp(g.to(torch.float64))
-        gxd, gyd, gcxd, gcyd = dense(gx), dense(gy), dense(gcx), dense(gcy)
-        gmd = None if gmom is None else gmom.to(torch.float64).contiguous()
-        need = ctx.needs_input_grad
-        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)     # noqa: E731
+        # one tensor per parameter group in the rays' element type, written by the reduction kernel (fp64 sums rounded
+        # once): autograd can take them as the leaves' .grad without a cast or a clone
+        new = lambda *shape: torch.empty(shape, dtype=prec.dtype, device=dev)     # noqa: E731
         gxin = new(B, F, W, P) if need[0] else None
         gyin = new(B, F, W, P) if need[1] else None
         g_c, g_t, g_mu, g_z, g_cx, g_cy = new(B, S), new(B, S), new(B, W, S), new(B), new(B, F), new(B, F)
         g_kappa, g_poly = (new(B, S), new(B, S, 4)) if asph else (None, None)
-        with _on_device(dev):
-            g = _lib.seeds(gx=gxd, gy=gyd, gcx=gcxd, gcy=gcyd, g_moments=gmd)
-            out = _lib.grads(g_c=g_c, g_t=g_t, g_mu=g_mu, g_z=g_z, g_cx=g_cx, g_cy=g_cy, g_kappa=g_kappa, g_poly=g_poly,
-                             g_x_in=gxin, g_y_in=gyin)
-            rc = lib.tl_trace_bwd_f64(C.byref(prob), g, out, _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "tl_trace_bwd_f64")
+        g_n = new(B, W, S + 1) if gopdd is not None else None
+        g = _lib.seeds(gx=gxd, gy=gyd, gcx=gcxd, gcy=gcyd, g_moments=gmd, g_opd=gopdd, g_stacks=gstkd)
+        out = _lib.grads(g_c=g_c, g_t=g_t, g_mu=g_mu, g_z=g_z, g_cx=g_cx, g_cy=g_cy, g_kappa=g_kappa, g_poly=g_poly,
+                         g_n_index=g_n, g_x_in=gxin, g_y_in=gyin)
+        timed = "bwd" if prec.timed else None
+        if ctx.use_inv:
+            fwd = _lib.rays(x=fx, y=fy, cx=fcx, cy=fcy, ok=fok, moments=fmom)
+            _call("tl_trace_bwd_from_outputs", dev, C.byref(prob), g, fwd, out, ws, ws.numel(), timed=timed)
+        else:
+            _call(prec.bwd, dev, C.byref(prob), g, out, ws, ws.numel(), timed=timed)
 
-        def fold(g, like):
+        def fold(g, like):          # [B,F] -> the (possibly broadcast) shape [1|B, 1|F] of cx / cy
             if like.shape[0] == 1 and B > 1:
                 g = g.sum(dim=0, keepdim=True)
             if like.shape[1] == 1 and F > 1:
                 g = g.sum(dim=1, keepdim=True)
             return g.reshape(like.shape)
         return (gxin.permute(0, 1, 3, 2) if need[0] else None, gyin.permute(0, 1, 3, 2) if need[1] else None,
-                g_z.reshape(z.shape) if need[2] else None, fold(g_cx, cx) if need[3] else None, fold(g_cy, cy) if need[4] else None,
+                g_z.reshape(z.shape) if need[2] else None, fold(g_cx, cx) if need[3] else None,
+                fold(g_cy, cy) if need[4] else None,
                 g_c.reshape(c.shape), g_t.reshape(t.shape), g_mu.reshape(mu.shape),
                 g_kappa.reshape(kappa.shape) if asph else None, g_poly.reshape(poly.shape) if asph else None,
-                None, None, None, None)
+                None, None, g_n.reshape(n_index.shape) if g_n is not None else None, None, None, None, None, None, None,
+                None)
 
 
 class SpotRmsFunction(torch.autograd.Function):
@@ -467,10 +417,7 @@ class SpotRmsFunction(torch.autograd.Function):
         m = moments.to(torch.float64).contiguous()
         rms = torch.empty(() if n_lens == 1 else (n_lens,), dtype=torch.float32, device=dev)
         dm = torch.empty_like(m)
-        with _on_device(dev):
-            rc = _lib.lib().tl_spot_rms(dev.index, n_lens, m.shape[0] // n_lens, float(n_per_field), _lib.ptr(m),
-                                        _lib.ptr(rms), _lib.ptr(dm), _stream_ptr(dev))
-        _lib.check(rc, "tl_spot_rms")
+        _call("tl_spot_rms", dev, dev.index, n_lens, m.shape[0] // n_lens, float(n_per_field), m, rms, dm)
         ctx.save_for_backward(dm)
         ctx.n_lens = n_lens
         return rms
@@ -501,14 +448,10 @@ class SpotMomentsFunction(torch.autograd.Function):
         oks = ok.view(torch.uint8) if ok.dtype == torch.bool else ok.to(torch.uint8)
         if oks.stride() != y.stride():
             oks = torch.empty_strided(y.shape, y.stride(), dtype=torch.uint8, device=dev).copy_(oks)
-        lib = _lib.lib()
         moments = torch.empty((F, TL_NMOM), dtype=torch.float64, device=dev)
         ws = _workspace(F * W * ((P + 255) // 256) * TL_NMOM * 8 + 256, dev)
-        with _on_device(dev):
-            rc = lib.tl_spot_moments(dev.index, F, P, W, _lib.ptr(xs), _lib.ptr(y), _lib.ptr(oks),
-                                     y.stride(1), y.stride(2), y.stride(3), _lib.ptr(moments),
-                                     _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "tl_spot_moments")
+        _call("tl_spot_moments", dev, dev.index, F, P, W, xs, y, oks, y.stride(1), y.stride(2), y.stride(3), moments,
+              ws, ws.numel())
         ctx.save_for_backward(xs if xs is not None else y, y, oks)
         ctx.has_x = xs is not None
         return moments
@@ -518,16 +461,12 @@ class SpotMomentsFunction(torch.autograd.Function):
         xs, y, oks = ctx.saved_tensors
         dev = y.device
         _, F, P, W = y.shape
-        lib = _lib.lib()
         gm = gmom.to(torch.float64).contiguous()
         gy = torch.empty_strided(y.shape, y.stride(), dtype=torch.float32, device=dev)
         need_x = ctx.has_x and ctx.needs_input_grad[0]
         gx = torch.empty_strided(y.shape, y.stride(), dtype=torch.float32, device=dev) if need_x else None
-        with _on_device(dev):
-            rc = lib.tl_spot_seed(dev.index, F, P, W, _lib.ptr(xs) if ctx.has_x else None, _lib.ptr(y),
-                                  _lib.ptr(oks), y.stride(1), y.stride(2), y.stride(3), _lib.ptr(gm),
-                                  _lib.ptr(gx), _lib.ptr(gy), _stream_ptr(dev))
-        _lib.check(rc, "tl_spot_seed")
+        _call("tl_spot_seed", dev, dev.index, F, P, W, xs if ctx.has_x else None, y, oks, y.stride(1), y.stride(2),
+              y.stride(3), gm, gx, gy)
         return gx, gy, None
 
 
@@ -572,16 +511,11 @@ class PsfAccumulateFunction(torch.autograd.Function):
                 wt = torch.empty_strided(x.shape, x.stride(), dtype=wt.dtype, device=dev).copy_(wt)
             wf, wb = (None, wt) if wb is not None else (wt, None)
         xp, yp, yc = (a.detach().reshape(G).contiguous() for a in (x_pitch, y_pitch, y_centre))
-        lib = _lib.lib()
-        nbytes = lib.tl_psf_workspace_bytes(G, W, R, nxh, ny)
+        nbytes = _lib.lib().tl_psf_workspace_bytes(G, W, R, nxh, ny)
         ws = _workspace(nbytes, dev)
         hist = torch.empty((G, W, ny, nxh), dtype=torch.float32, device=dev)
-        with _on_device(dev):
-            rc = lib.tl_psf_accumulate(dev.index, G, W, R, _lib.ptr(x), _lib.ptr(y), _lib.ptr(wf), _lib.ptr(wb),
-                                       x.stride(0), x.stride(1), _lib.ptr(xp), _lib.ptr(yp), _lib.ptr(yc), nxh, ny,
-                                       float(x_first), float(y_first), _lib.ptr(hist), _lib.ptr(ws), ws.numel(),
-                                       _stream_ptr(dev))
-        _lib.check(rc, "tl_psf_accumulate")
+        _call("tl_psf_accumulate", dev, dev.index, G, W, R, x, y, wf, wb, x.stride(0), x.stride(1), xp, yp, yc, nxh, ny,
+              float(x_first), float(y_first), hist, ws, ws.numel())
         ctx.save_for_backward(x, y, wf, wb, xp, yp, yc)
         ctx.geom = (nxh, ny, float(x_first), float(y_first), nbytes)
         ctx.shapes = (x_pitch.shape, y_pitch.shape, y_centre.shape)
@@ -593,19 +527,14 @@ class PsfAccumulateFunction(torch.autograd.Function):
         nxh, ny, x_first, y_first, nbytes = ctx.geom
         dev = x.device
         G, W, R = x.shape
-        lib = _lib.lib()
         gh = g_hist.to(torch.float32).contiguous()
         gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
         gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
         need = ctx.needs_input_grad
         g_xp, g_yp, g_yc = (torch.empty(G, dtype=torch.float32, device=dev) if need[k] else None for k in (3, 4, 5))
         ws = _workspace(nbytes, dev)
-        with _on_device(dev):
-            rc = lib.tl_psf_accumulate_bwd(dev.index, G, W, R, _lib.ptr(x), _lib.ptr(y), _lib.ptr(wf), _lib.ptr(wb),
-                                           x.stride(0), x.stride(1), _lib.ptr(xp), _lib.ptr(yp), _lib.ptr(yc), nxh, ny,
-                                           x_first, y_first, _lib.ptr(gh), _lib.ptr(gx), _lib.ptr(gy), _lib.ptr(g_xp),
-                                           _lib.ptr(g_yp), _lib.ptr(g_yc), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "tl_psf_accumulate_bwd")
+        _call("tl_psf_accumulate_bwd", dev, dev.index, G, W, R, x, y, wf, wb, x.stride(0), x.stride(1), xp, yp, yc, nxh, ny,
+              x_first, y_first, gh, gx, gy, g_xp, g_yp, g_yc, ws, ws.numel())
         g_xp, g_yp, g_yc = (g if g is None else g.reshape(s) for g, s in zip((g_xp, g_yp, g_yc), ctx.shapes))
         return (gx if need[0] else None, gy if need[1] else None, None, g_xp, g_yp, g_yc, None, None, None, None)
 
@@ -655,10 +584,7 @@ class SvolaFunction(torch.autograd.Function):
         wr, wc = SvolaFunction._tables(geo, dev)
         out = torch.empty(image.shape, dtype=torch.float32, device=dev)
         q = SvolaFunction._geom(geo, image, psfs)
-        with _on_device(dev):
-            rc = _lib.lib().tl_svola_fwd(C.byref(q), *geo.bounds, _lib.ptr(wr), _lib.ptr(wc), _lib.ptr(image), _lib.ptr(psfs),
-                                         _lib.ptr(out), _stream_ptr(dev))
-        _lib.check(rc, "tl_svola_fwd")
+        _call("tl_svola_fwd", dev, C.byref(q), *geo.bounds, wr, wc, image, psfs, out)
         _svola_calls["fwd"] += 1
         _svola_calls["psfs_ptr"] = psfs.data_ptr()
         ctx.save_for_backward(image, psfs)
@@ -673,26 +599,20 @@ class SvolaFunction(torch.autograd.Function):
         image, psfs = ctx.saved_tensors
         geo, dev = ctx.geo, image.device
         wr, wc = SvolaFunction._tables(geo, dev)
-        lib = _lib.lib()
         g_out = g_out.to(torch.float32).contiguous()
         g_image = g_psfs = None
         if need_psfs:
             g_psfs = torch.empty(psfs.shape, dtype=torch.float32, device=dev)
         q = SvolaFunction._geom(geo, image, psfs, g_psfs)
-        nbytes = lib.tl_svola_workspace_bytes(C.byref(q), *geo.bounds)
+        nbytes = _lib.lib().tl_svola_workspace_bytes(C.byref(q), *geo.bounds)
         ws = _workspace(nbytes, dev)
-        with _on_device(dev):
-            if need_psfs:
-                rc = lib.tl_svola_bwd_psf(C.byref(q), *geo.bounds, _lib.ptr(wr), _lib.ptr(wc), _lib.ptr(image), _lib.ptr(g_out),
-                                          _lib.ptr(g_psfs), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-                _lib.check(rc, "tl_svola_bwd_psf")
-                _svola_calls["bwd_psf"] += 1
-            if need_image:
-                g_image = torch.empty(image.shape, dtype=torch.float32, device=dev)
-                rc = lib.tl_svola_bwd_image(C.byref(q), *geo.bounds, _lib.ptr(wr), _lib.ptr(wc), _lib.ptr(psfs), _lib.ptr(g_out),
-                                            _lib.ptr(g_image), _lib.ptr(ws), ws.numel(), _stream_ptr(dev))
-                _lib.check(rc, "tl_svola_bwd_image")
-                _svola_calls["bwd_image"] += 1
+        if need_psfs:
+            _call("tl_svola_bwd_psf", dev, C.byref(q), *geo.bounds, wr, wc, image, g_out, g_psfs, ws, ws.numel())
+            _svola_calls["bwd_psf"] += 1
+        if need_image:
+            g_image = torch.empty(image.shape, dtype=torch.float32, device=dev)
+            _call("tl_svola_bwd_image", dev, C.byref(q), *geo.bounds, wr, wc, psfs, g_out, g_image, ws, ws.numel())
+            _svola_calls["bwd_image"] += 1
         return g_image, g_psfs, None
 
 
@@ -711,10 +631,7 @@ class PupilPositionFunction(torch.autograd.Function):
         if t.shape != (B, K) or n.shape != (B, K + 1):
             raise ValueError("pupil position: c, t must hold [B,K] rows and n [B,K+1] indices")
         z = torch.empty(B, dtype=torch.float32, device=c.device)
-        with _on_device(c.device):
-            rc = _lib.lib().tl_pupil_position(c.device.index, B, K, _lib.ptr(c), _lib.ptr(t), _lib.ptr(n), _lib.ptr(z),
-                                              None, None, None, None, ctx.mode, _stream_ptr(c.device))
-        _lib.check(rc, "tl_pupil_position")
+        _call("tl_pupil_position", c.device, c.device.index, B, K, c, t, n, z, None, None, None, None, ctx.mode)
         ctx.save_for_backward(c, t, n)
         return z
 
@@ -724,11 +641,7 @@ class PupilPositionFunction(torch.autograd.Function):
         B, K = c.shape
         g_z = g_z.to(torch.float32).reshape(B).contiguous()
         g_c, g_t, g_n = torch.empty_like(c), torch.empty_like(t), torch.empty_like(n)
-        with _on_device(c.device):
-            rc = _lib.lib().tl_pupil_position(c.device.index, B, K, _lib.ptr(c), _lib.ptr(t), _lib.ptr(n), None,
-                                              _lib.ptr(g_z), _lib.ptr(g_c), _lib.ptr(g_t), _lib.ptr(g_n), ctx.mode,
-                                              _stream_ptr(c.device))
-        _lib.check(rc, "tl_pupil_position (backward)")
+        _call("tl_pupil_position", c.device, c.device.index, B, K, c, t, n, None, g_z, g_c, g_t, g_n, ctx.mode)
         return g_c, g_t, g_n, None
 
 

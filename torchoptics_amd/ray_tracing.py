@@ -11,7 +11,7 @@ Tensor dims, as in the reference: [lens (=1), field, pupil, wavelength(, surface
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -260,18 +260,20 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
     f64 = any(torch.is_tensor(a) and a.dtype == torch.float64 for a in (x, y, z, cy, c, t, mu))
     if f64 and (aggregate or want_opd):
         raise NotImplementedError("the double-precision trace has no penalty term and no optical path length")
+    # aspheric rows: an absent kappa / poly is zero, and the rows traced by Newton iteration default to those where
+    # either is non-zero (per lens [B,S] / [B,S,4], or one set [S] / [S,4] shared by every lens of the batch)
+    S = c.shape[-1]
+    kap = pol = kind = None
+    if kappa is not None or poly is not None:
+        kap = kappa if kappa is not None else torch.zeros(1, S, device=c.device)
+        pol = poly if poly is not None else torch.zeros(1, S, 4, device=c.device)
+        kind = surf_kind
+        if kind is None:
+            kind = (kap.detach().reshape(-1, S) != 0) | (pol.detach().reshape(-1, S, 4) != 0).any(dim=-1)
+        kind = torch.as_tensor(kind, device=c.device)
     ext = None if f64 else ops._ext()
     if ext is not None:
         # the C++ host chain: shapes are normalised, outputs allocated and the autograd node built in csrc/tl_torch.cpp
-        S = c.shape[-1]
-        kap = pol = kind = None
-        if kappa is not None or poly is not None:
-            kap = kappa if kappa is not None else torch.zeros(1, S, device=c.device)
-            pol = poly if poly is not None else torch.zeros(1, S, 4, device=c.device)
-            kind = surf_kind
-            if kind is None:
-                kind = (kap.detach().reshape(-1, S) != 0) | (pol.detach().reshape(-1, S, 4) != 0).any(dim=-1)
-            kind = torch.as_tensor(kind, device=c.device)
         out, use_inv = ops.trace_cpp(ext, x, y, z, cx, cy, c, t, mu, mask, kap, pol, kind, n_index if want_opd else None,
                                      bool(allow_backward_rays), mode or ops.get_default_mode(), want_rays, bool(want_opd),
                                      bool(aggregate), bool(aggregate is True and want_rays), bool(x_moments))
@@ -285,7 +287,6 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
             raise ValueError(f"{n} must be 4-D with 1 or {B} lenses in dim 0, got {tuple(a.shape)}")
     if c.dim() != 5 or t.dim() != 5 or mu.dim() != 5 or any(a.shape[0] not in (1, B) for a in (c, t, mu)):
         raise ValueError("c, t, mu must be 5-D [1|B,1,1,1|W,S]")
-    S = c.shape[-1]
     F = max(x.shape[1], y.shape[1], cx.shape[1], cy.shape[1])
     P = max(x.shape[2], y.shape[2])
     W = max(x.shape[3], y.shape[3], mu.shape[3])
@@ -303,16 +304,11 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
     mask_u8 = mask.reshape(-1, S)
     mask_u8 = mask_u8.view(torch.uint8) if mask_u8.dtype == torch.bool else mask_u8.to(torch.uint8)   # bool: no copy
     mask_u8 = mask_u8.expand(B, S).contiguous()
-    kap = pol = kind_u8 = None
-    if kappa is not None or poly is not None:
-        # per lens [B,S] / [B,S,4], or one set [S] / [S,4] shared by every lens of the batch
-        kap = (cast(kappa, 'kappa').reshape(-1, S) if kappa is not None
-               else torch.zeros(1, S, device=c.device, dtype=c.dtype)).expand(B, S).contiguous()
-        pol = (cast(poly, 'poly').reshape(-1, S, 4) if poly is not None
-               else torch.zeros(1, S, 4, device=c.device, dtype=c.dtype)).expand(B, S, 4).contiguous()
-        if surf_kind is None:
-            surf_kind = (kap.detach() != 0) | (pol.detach() != 0).any(dim=-1)
-        kind_u8 = torch.as_tensor(surf_kind, device=c.device).reshape(-1, S).to(torch.uint8).expand(B, S).contiguous()
+    kind_u8 = None
+    if kind is not None:
+        kap = cast(kap, 'kappa').reshape(-1, S).expand(B, S).contiguous()
+        pol = cast(pol, 'poly').reshape(-1, S, 4).expand(B, S, 4).contiguous()
+        kind_u8 = kind.reshape(-1, S).to(torch.uint8).expand(B, S).contiguous()
     nidx = None
     if want_opd:
         if n_index is None:
@@ -320,13 +316,45 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
         nidx = cast(n_index, 'n_index')
         nidx = nidx.reshape(nidx.shape[0] if nidx.dim() == 5 else 1, -1, S + 1).expand(B, W, S + 1).contiguous()
     if f64:
-        out = ops.TraceFunctionF64.apply(x_e, y_e, zv, cx2, cy2, c2, t2, mu3, kap, pol, mask_u8, kind_u8,
-                                         bool(allow_backward_rays), want_rays)
-        return _trace_result((*out, None, None), False, want_rays, False, False, True, P * W, B)
+        # the fp64 kernels: 'strict' arithmetic only, no walk-back, and the x-moments always filled (nothing to ask for)
+        out = ops.TraceFunction.apply(x_e, y_e, zv, cx2, cy2, c2, t2, mu3, kap, pol, mask_u8, kind_u8, None,
+                                      bool(allow_backward_rays), "strict", want_rays, False, False, False, False)
+        return _trace_result(out, False, want_rays, False, False, True, P * W, B)
     out = ops.TraceFunction.apply(x_e, y_e, zv, cx2, cy2, c2, t2, mu3, kap, pol, mask_u8, kind_u8, nidx,
                                   bool(allow_backward_rays), mode or ops.get_default_mode(), want_rays, bool(want_opd),
                                   bool(aggregate), bool(aggregate is True and want_rays), bool(x_moments))
     return _trace_result(out, ops._last_use_inv, want_rays, want_opd, aggregate, x_moments, P * W, B)
+
+
+class _SpotTag(NamedTuple):
+    """What trace_skew leaves on its `y` (as `y._tl_spot`) so that the spot metrics cost no second pass over the rays."""
+    moments: torch.Tensor                   # [B*F, TL_NMOM], lens-major
+    ok: torch.Tensor                        # the ray_ok returned with y
+    version: int                            # y._version when the tag was set
+    n_pw: int                               # rays per field: P * W
+    has_x: bool                             # the x-moments were filled (x_moments=True)
+    rms: Optional[torch.Tensor] = None      # the spot metric, when the trace node computed it already (C++ host chain)
+
+
+def _spot_tag(y, ray_ok) -> Optional[_SpotTag]:
+    """The tag of `y` if it still describes (y, ray_ok): same ray_ok (identity), y not modified since.  Else None."""
+    tag = getattr(y, "_tl_spot", None)
+    return tag if tag is not None and tag.ok is ray_ok and tag.version == y._version else None
+
+
+def _spot_moments(tag, x, y, ray_ok, group=None, n_per_field=None):
+    """(moments, rays per field) of a spot: the trace's fused moments when `tag` is given, else one reduction over the
+    rays; summed over the process group that shards the pupil, if any."""
+    if tag is not None:
+        moments, n_local = tag.moments, tag.n_pw
+    else:
+        moments, n_local = ops.SpotMomentsFunction.apply(x, y, ray_ok), y.shape[2] * y.shape[3]
+    if group is not None:
+        from . import dist as tl_dist
+        moments = tl_dist.all_reduce_sum(moments, group)
+        if n_per_field is None:
+            n_per_field = n_local * torch.distributed.get_world_size(group)
+    return moments, n_per_field or n_local
 
 
 def _trace_result(out, use_inv, want_rays, want_opd, aggregate, x_moments, n_pw, B):
@@ -336,7 +364,7 @@ def _trace_result(out, use_inv, want_rays, want_opd, aggregate, x_moments, n_pw,
     if want_rays:
         # remember which moments belong to these rays (checked by identity + version in compute_rms2d):
         # [B*F, TL_NMOM], lens-major; and their spot metric when the trace node computed it already
-        yo._tl_spot = (moments, ok, yo._version, n_pw, bool(x_moments), rms)
+        yo._tl_spot = _SpotTag(moments, ok, yo._version, n_pw, bool(x_moments), rms)
         xo._tl_use_inv = bool(use_inv)                 # which backward algorithm this trace will take (ops.used_walk_back)
         res = (xo, yo, cxo, cyo, ok, back)
         if want_opd:
@@ -372,8 +400,8 @@ def _trace_skew_in_lens_chunks(nb, B, x, y, z, cx, cy, c, t, mu, mask, aggregate
         return torch.cat(outs, dim=0)                      # moments [B*F, TL_NMOM], lens-major
     n_ray = 6 + (1 if want_opd else 0)
     res = [torch.cat([o[i] for o in outs], dim=0) for i in range(n_ray)]
-    moments = torch.cat([o[1]._tl_spot[0] for o in outs], dim=0)
-    res[1]._tl_spot = (moments, res[4], res[1]._version, outs[0][1]._tl_spot[3], bool(x_moments))
+    moments = torch.cat([o[1]._tl_spot.moments for o in outs], dim=0)
+    res[1]._tl_spot = _SpotTag(moments, res[4], res[1]._version, outs[0][1]._tl_spot.n_pw, bool(x_moments))
     if aggregate:
         stk = None
         if aggregate is True:
@@ -433,14 +461,13 @@ def unsupervised_loss(rt_outputs, n_sequence: int, penalty_rate: float):
 def _fused_unsup_loss(y, ray_ok, stacks, n_sequence, penalty_rate, n_lens):
     """The loss_dict in ONE launch (tl_unsup_loss, C++ host chain) when everything it needs is the fused moments of an
     aggregate trace of fp32 tensors on the GPU; None otherwise (the callers compose it from tensor ops: same values)."""
-    tag = getattr(y, "_tl_spot", None)
-    if (not isinstance(stacks, PenaltyStacks) or tag is None or tag[1] is not ray_ok or tag[2] != y._version
-            or stacks._moments is not tag[0] or y.dtype != torch.float32 or not isinstance(penalty_rate, (int, float))):
+    tag = _spot_tag(y, ray_ok)
+    if (not isinstance(stacks, PenaltyStacks) or tag is None or stacks._moments is not tag.moments
+            or y.dtype != torch.float32 or not isinstance(penalty_rate, (int, float))):
         return None
-    moments = tag[0]
     if n_lens == 1 and y.shape[0] > 1:
         return None                     # compute_rms2d reads sample 0 of a batch, the penalty sums all of it: not this kernel
-    out = ops.unsup_loss(moments, tag[3], n_lens, n_sequence, penalty_rate)
+    out = ops.unsup_loss(tag.moments, tag.n_pw, n_lens, n_sequence, penalty_rate)
     if out is None:
         return None
     return {'loss_unsup': out[0], 'rms': out[1], 'penalty': out[2]}
@@ -485,26 +512,18 @@ def compute_rms2d(x, y, ray_ok, group=None, n_per_field: Optional[int] = None):
     `n_per_field`: P*W of the WHOLE (unsharded) pupil; defaults to this shard's P*W times the
     group size.
     """
-    tag = getattr(y, "_tl_spot", None)
-    if tag is not None and tag[1] is ray_ok and tag[2] == y._version:
-        moments, n_local = tag[0], tag[3]
-        if group is None and len(tag) > 5 and tag[5] is not None and n_per_field in (None, n_local) and y.dtype == torch.float32:
-            return tag[5] if y.shape[0] == 1 else tag[5][0]        # computed by the trace node itself (one launch, one node)
+    tag = _spot_tag(y, ray_ok)
+    if tag is not None:
+        if group is None and tag.rms is not None and n_per_field in (None, tag.n_pw) and y.dtype == torch.float32:
+            return tag.rms if y.shape[0] == 1 else tag.rms[0]      # computed by the trace node itself (one launch, one node)
         if y.shape[0] > 1:                       # the reference reads sample 0 only (:695,699)
-            moments = moments[: y.shape[1]]
-    else:
-        if y.shape[0] > 1:
-            x, y, ray_ok = (None if x is None else x[:1]), y[:1], ray_ok[:1]
-        moments = ops.SpotMomentsFunction.apply(x, y, ray_ok)
-        n_local = y.shape[2] * y.shape[3]
-    if group is not None:
-        from . import dist as tl_dist
-        moments = tl_dist.all_reduce_sum(moments, group)
-        if n_per_field is None:
-            n_per_field = n_local * torch.distributed.get_world_size(group)
+            tag = tag._replace(moments=tag.moments[: y.shape[1]])
+    elif y.shape[0] > 1:
+        x, y, ray_ok = (None if x is None else x[:1]), y[:1], ray_ok[:1]
+    moments, n = _spot_moments(tag, x, y, ray_ok, group, n_per_field)
     if moments.is_cuda and y.dtype != torch.float64:
-        return ops.spot_rms(moments, n_per_field or n_local).to(y.dtype)
-    return rms_from_moments(moments, n_per_field or n_local).to(y.dtype)        # fp64 callers: the closed form in fp64
+        return ops.spot_rms(moments, n).to(y.dtype)
+    return rms_from_moments(moments, n).to(y.dtype)        # fp64 callers: the closed form in fp64
 
 
 def compute_rms2d_batch(x, y, ray_ok):
@@ -512,15 +531,12 @@ def compute_rms2d_batch(x, y, ray_ok):
     its callers loop over lenses, optical_loss.py:96-110).  Same closed form per lens on the moments fused into the
     one batched trace launch; differentiable through the one batched backward launch."""
     B, F = y.shape[0], y.shape[1]
-    tag = getattr(y, "_tl_spot", None)
-    if tag is not None and tag[1] is ray_ok and tag[2] == y._version:
-        moments, n_local = tag[0], tag[3]
-        if len(tag) > 5 and tag[5] is not None and y.dtype == torch.float32:
-            return tag[5].reshape(B)                               # computed by the trace node itself
-    else:
-        fold = lambda a: None if a is None else a.reshape(1, B * F, a.shape[2], a.shape[3])      # noqa: E731
-        moments = ops.SpotMomentsFunction.apply(fold(x), fold(y), fold(ray_ok))
-        n_local = y.shape[2] * y.shape[3]
+    tag = _spot_tag(y, ray_ok)
+    if tag is not None and tag.rms is not None and y.dtype == torch.float32:
+        return tag.rms.reshape(B)                                  # computed by the trace node itself
+    if tag is None:                 # the fields of every lens as one list of B * F fields
+        x, y, ray_ok = (None if a is None else a.reshape(1, B * F, a.shape[2], a.shape[3]) for a in (x, y, ray_ok))
+    moments, n_local = _spot_moments(tag, x, y, ray_ok)
     if moments.is_cuda and y.dtype != torch.float64:
         return ops.spot_rms(moments, n_local, B).reshape(B).to(y.dtype)
     m = moments.view(B, F, -1)
@@ -534,18 +550,10 @@ def compute_rms_spot_xy(x, y, ray_ok, group=None, n_per_field: Optional[int] = N
     spot radius sqrt(<(x - x_c)^2 + (y - y_c)^2>) with the same conventions as compute_rms2d (centroid over
     all rays, failed rays at the origin, denominator P*W).  Uses the x- and y-moments fused into the trace
     kernel; differentiable through the same backward kernel."""
-    tag = getattr(y, "_tl_spot", None)
-    if tag is not None and tag[1] is ray_ok and tag[2] == y._version and tag[4]:      # traced with x_moments=True
-        moments, n_local = tag[0], tag[3]
-    else:
-        moments = ops.SpotMomentsFunction.apply(x, y, ray_ok)
-        n_local = y.shape[2] * y.shape[3]
-    if group is not None:
-        from . import dist as tl_dist
-        moments = tl_dist.all_reduce_sum(moments, group)
-        if n_per_field is None:
-            n_per_field = n_local * torch.distributed.get_world_size(group)
-    n = n_per_field or n_local
+    tag = _spot_tag(y, ray_ok)
+    if tag is not None and not tag.has_x:           # traced without x_moments=True: one reduction over the rays instead
+        tag = None
+    moments, n = _spot_moments(tag, x, y, ray_ok, group, n_per_field)
     my, mx = moments[:, 0] / n, moments[:, 4] / n
     var = ((moments[:, 2] - 2 * my * moments[:, 1] + my * my * moments[:, 3])
            + (moments[:, 6] - 2 * mx * moments[:, 5] + mx * mx * moments[:, 3])) / n
@@ -674,8 +682,6 @@ class RayTracer:
         instead of two eager traces, an autograd pass and ~60 tensor ops per step (1.1 ms of host time per call for a
         256-lens minibatch, 0.1 ms now).  tee_ref [B,F,3] (vignetted tee points), rs [B] (stop radius): None = the
         kernel's defaults (pupil (0,-1), (0,1), (1,0); the marginal ray)."""
-        import ctypes as C
-        from . import _lib
         from .lens_modeling import const_tensor
         dev = lens2stop.c.device
         B, K = lens2stop.c.shape
@@ -694,13 +700,8 @@ class RayTracer:
         fields = const_tensor(list(self.rel_fields), torch.float32, dev)
         hfov, epd = _dense(specs2stop.hfov.detach().float()), _dense(specs2stop.epd.detach().float())
         out = torch.empty((3, B, F, 1, W), dtype=torch.float32, device=dev)
-        with ops._on_device(dev):
-            rc = _lib.lib().tl_ray_aim_iter(dev.index, B, F, W, K, _lib.ptr(c), _lib.ptr(t), _lib.ptr(n), _lib.ptr(n_d),
-                                            _lib.ptr(mask), _lib.ptr(kap), _lib.ptr(pol), _lib.ptr(kind), _lib.ptr(z), _lib.ptr(hfov),
-                                            _lib.ptr(fields), _lib.ptr(epd), 1 if self.allow_backward_rays else 0,
-                                            int(self.n_ray_aiming_iter), _lib.ptr(tee_ref), _lib.ptr(rs), _lib.ptr(out[0]),
-                                            _lib.ptr(out[1]), _lib.ptr(out[2]), ops._stream_ptr(dev))
-        _lib.check(rc, "tl_ray_aim_iter")
+        ops._call("tl_ray_aim_iter", dev, dev.index, B, F, W, K, c, t, n, n_d, mask, kap, pol, kind, z, hfov, fields, epd,
+                  1 if self.allow_backward_rays else 0, int(self.n_ray_aiming_iter), tee_ref, rs, out[0], out[1], out[2])
         x_scale, y_scale, y_offset = out[0], out[1], out[2]
 
         def remap(xp_rel, yp_rel):
@@ -716,10 +717,7 @@ class RayTracer:
                 return None
             xp, yp, e = _dense(xp_rel.detach()), _dense(yp_rel.detach()), _dense(epd_full.detach().float())
             xy = torch.empty((2, B, F, W, P), dtype=torch.float32, device=dev)
-            with ops._on_device(dev):
-                rc2 = _lib.lib().tl_aim_fan(dev.index, B, F, W, P, _lib.ptr(xp), _lib.ptr(yp), _lib.ptr(x_scale), _lib.ptr(y_scale),
-                                            _lib.ptr(y_offset), _lib.ptr(e), _lib.ptr(xy[0]), _lib.ptr(xy[1]), ops._stream_ptr(dev))
-            _lib.check(rc2, "tl_aim_fan")
+            ops._call("tl_aim_fan", dev, dev.index, B, F, W, P, xp, yp, x_scale, y_scale, y_offset, e, xy[0], xy[1])
             return xy[0].permute(0, 1, 3, 2), xy[1].permute(0, 1, 3, 2)
         remap.fan = fan
         return remap
