@@ -227,6 +227,9 @@ __global__ __launch_bounds__(kBlock) void reduce_bwd_kernel(const double *__rest
 
 // rms = mean_f sqrt((M2 - 2 m M1 + m^2 M3)/n), m = M0/n  (compute_rms2d on the moments)
 // and d rms / d moments, in one block: replaces ~25 tiny elementwise kernels of the autograd graph.
+// A field with var <= 0 contributes rms 0 and derivative 0: an all-dead field (var = 0: sqrt' is infinite there), or live rays
+// that coincide -- the closed form then cancels to rounding noise of either sign, and the root of a negative one would make
+// the lens' whole rms NaN.  Every field with var > 0 is evaluated exactly as before.
 // One block per lens (blockIdx.x): rms[b] from the moments rows [b F, (b + 1) F).
 __global__ __launch_bounds__(64) void spot_rms_kernel(const double *__restrict__ mom, int F, double n,
                                                       float *__restrict__ rms, double *__restrict__ dmom)
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(64) void spot_rms_kernel(const double *__restrict__
         const double *M = mom + (size_t)f * TL_NMOM;
         const double m = M[0] / n;
         const double var = (M[2] - 2.0 * m * M[1] + m * m * M[3]) / n;
-        const double sd = sqrt(var);
+        const double sd = var > 0.0 ? sqrt(var) : 0.0;      // (see above: var <= 0 is a spot of no extent)
         acc += sd;
         const double k = var > 0.0 ? 1.0 / (2.0 * (double)F * n * sd) : 0.0;
         double *D = dmom + (size_t)f * TL_NMOM;
@@ -270,7 +273,7 @@ __global__ __launch_bounds__(64) void unsup_loss_kernel(const double *__restrict
         const double *M = mom + (size_t)f * TL_NMOM;
         const double m = M[0] / n;
         const double var = (M[2] - 2.0 * m * M[1] + m * m * M[3]) / n;
-        const double sd = sqrt(var);
+        const double sd = var > 0.0 ? sqrt(var) : 0.0;      // (see above: var <= 0 is a spot of no extent)
         acc += sd;
         q += M[8];
         const double k = var > 0.0 ? 1.0 / (2.0 * (double)F * n * sd) : 0.0;

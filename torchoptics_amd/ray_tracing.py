@@ -347,6 +347,8 @@ def _spot_moments(tag, x, y, ray_ok, group=None, n_per_field=None):
     rays; summed over the process group that shards the pupil, if any."""
     if tag is not None:
         moments, n_local = tag.moments, tag.n_pw
+    elif y.dtype == torch.float64:
+        moments, n_local = _moments_f64(x, y, ray_ok), y.shape[2] * y.shape[3]
     else:
         moments, n_local = ops.SpotMomentsFunction.apply(x, y, ray_ok), y.shape[2] * y.shape[3]
     if group is not None:
@@ -355,6 +357,22 @@ def _spot_moments(tag, x, y, ray_ok, group=None, n_per_field=None):
         if n_per_field is None:
             n_per_field = n_local * torch.distributed.get_world_size(group)
     return moments, n_per_field or n_local
+
+
+def _moments_f64(x, y, ray_ok):
+    """The [F, TL_NMOM] moments of fp64 rays [1,F,P,W] that carry no tag, as differentiable fp64 sums (tl_spot_moments reads
+    fp32: it would round x and y before summing and return fp32 seeds, and a double_precision=True caller who applies any op to
+    y would silently get fp32-input accuracy).  Plain tensor ops, on whatever device the rays live; the fp32 path does not
+    come here.  The caller decides by y's type alone: an fp32 x next to an fp64 y is widened here, an fp64 x next to an fp32 y
+    still goes through tl_spot_moments and is rounded to fp32."""
+    okd = ray_ok.to(torch.float64)
+    cols = [y.sum(dim=(2, 3)), (okd * y).sum(dim=(2, 3)), (okd * y * y).sum(dim=(2, 3)), okd.sum(dim=(2, 3))]
+    if x is not None:
+        xd = x.to(torch.float64)
+        cols += [xd.sum(dim=(2, 3)), (okd * xd).sum(dim=(2, 3)), (okd * xd * xd).sum(dim=(2, 3))]
+    zero = torch.zeros_like(cols[0])
+    cols += [zero] * (ops.TL_NMOM - len(cols))
+    return torch.stack(cols, dim=-1)[0]
 
 
 def _trace_result(out, use_inv, want_rays, want_opd, aggregate, x_moments, n_pw, B):
@@ -501,7 +519,15 @@ def rms_from_moments(moments: torch.Tensor, n_per_field: int) -> torch.Tensor:
     centroid and in the denominator, exactly like the reference (quirk B8)."""
     m = moments[:, 0] / n_per_field
     var = (moments[:, 2] - 2 * m * moments[:, 1] + m * m * moments[:, 3]) / n_per_field
-    return torch.sqrt(var).mean()
+    return _root_of_variance(var).mean()
+
+
+def _root_of_variance(var: torch.Tensor) -> torch.Tensor:
+    """sqrt(var) where var > 0, else 0 with derivative 0 (the rule of spot_rms_kernel): an all-dead field has var = 0, and
+    live rays that coincide cancel the closed form to rounding noise of either sign -- sqrt of a negative one is NaN, and
+    sqrt'(0) = inf must not enter the graph (inf * 0 = NaN in the backward).  Where var > 0 nothing changes by a bit."""
+    pos = var > 0
+    return torch.where(pos, torch.sqrt(torch.where(pos, var, torch.ones_like(var))), torch.zeros_like(var))
 
 
 def compute_rms2d(x, y, ray_ok, group=None, n_per_field: Optional[int] = None):
@@ -542,7 +568,7 @@ def compute_rms2d_batch(x, y, ray_ok):
     m = moments.view(B, F, -1)
     mean = m[..., 0] / n_local
     var = (m[..., 2] - 2 * mean * m[..., 1] + mean * mean * m[..., 3]) / n_local
-    return torch.sqrt(var).mean(dim=1).to(y.dtype)
+    return _root_of_variance(var).mean(dim=1).to(y.dtype)
 
 
 def compute_rms_spot_xy(x, y, ray_ok, group=None, n_per_field: Optional[int] = None):
@@ -557,7 +583,7 @@ def compute_rms_spot_xy(x, y, ray_ok, group=None, n_per_field: Optional[int] = N
     my, mx = moments[:, 0] / n, moments[:, 4] / n
     var = ((moments[:, 2] - 2 * my * moments[:, 1] + my * my * moments[:, 3])
            + (moments[:, 6] - 2 * mx * moments[:, 5] + mx * mx * moments[:, 3])) / n
-    return torch.sqrt(var).mean().to(y.dtype)
+    return _root_of_variance(var).mean().to(y.dtype)
 
 
 # ---------------------------------------------------------------------------- RayTracer
