@@ -4,7 +4,9 @@
  * The reference (OceanT-shirt/TorchOptics) has no FFI: its hot path is a chain of
  * in-process Python calls.  Each entry point below states which reference function it
  * stands in for (file:line under torchlens/); the Python host in torchoptics_amd/
- * mirrors the reference signatures on top of these.
+ * mirrors the reference signatures on top of these.  The image side (image_ops.py) is here
+ * too: tl_svola_* blurs an image with the lens's PSFs, tl_warp_* resamples it through the
+ * distortion map and multiplies the relative illumination in.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless marked "host";
@@ -435,6 +437,53 @@ int tl_svola_bwd_psf(const tl_svola_geom *g, const int32_t *r0, const int32_t *r
 int tl_svola_bwd_image(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, const int32_t *c0, const int32_t *c1,
                        const double *wr, const double *wc, const float *psfs, const float *g_out, float *g_image,
                        void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Bicubic resampling of an image at per-pixel source coordinates, with gradients to the coordinates and to a gain
+ * (imaging.warp_bicubic(fused=True); additive entry points, ABI unchanged): distortion and relative illumination of a rendered
+ * image.  image [B,H,W,C]; x, y [coord_batch,Ho,Wo], normalised source coordinates, -1 at the centre of the first column (row)
+ * and +1 at the centre of the last; gain [gain_batch,Ho,Wo,gain_channels] or NULL (then gain_batch and gain_channels are not
+ * read).  Per output pixel
+ *     xc = clamp(x, -1, 1),  u = (xc + 1) / 2 (W - 1),  j0 = floor(u),  t = u - j0,
+ *     columns j0 - 1, j0, j0 + 1, j0 + 2, each clipped into [0, W - 1] (replicate padding); rows likewise from y and H;
+ *     w(-1) = a(t^3 - 2t^2 + t), w(0) = (a+2)t^3 - (a+3)t^2 + 1, w(1) = -(a+2)t^3 + (2a+3)t^2 - at, w(2) = a(t^2 - t^3), a = -0.75;
+ *     out[b,yo,xo,c] = gain sum_i sum_j wy_i wx_j image[b, row_i, col_j, c].
+ * Element strides address image and gain (b, y, x, c), x, y (b, y, x) and the gradient outputs, which have the shapes of x, y
+ * and gain.  out and g_out are contiguous [B,Ho,Wo,C] floats.
+ *   tl_warp_fwd   out.  One lane per output pixel, the channels looped in the lane; no LDS, no workspace.
+ *   tl_warp_bwd   g_x, g_y = d/dx, d/dy of sum(g_out out) (both or neither: NULL for none) and g_gain (NULL for none; needs
+ *                 gain), in one launch that recomputes the taps; the forward output is not needed.  d/dx is the derivative
+ *                 weights times (W - 1)/2 where -1 <= x <= 1 and 0 outside; at an integer u it is taken in the cell with
+ *                 t = 0 (the interpolant is C1, so both cells agree).  Whatever is shared (coord_batch or gain_batch 1 with
+ *                 B > 1, gain_channels 1 with C > 1) receives the sum over what shares it, taken inside one lane in a fixed
+ *                 order (b outer, c inner): no atomics, no workspace, the same bits on every run.
+ * Only clipped integer indices form addresses, so no coordinate value can read outside the image; a NaN coordinate gives NaN
+ * in that pixel's output and gradients and nowhere else.  The gradient to the image (a scatter) is not provided.
+ * TL_EINVAL before any HIP call, with the function's name and the argument in the message: a required pointer NULL, a size
+ * below 1 (or H, W, Ho, Wo above 2^20), coord_batch or gain_batch neither 1 nor B, gain_channels neither 1 nor C.  C is not a
+ * grid dimension and has no upper limit; B is cut into launches of 65535 lenses.  No host synchronisation, no allocation;
+ * the launches go on `stream`.
+ */
+typedef struct tl_warp_geom {
+    int32_t device;
+    int32_t B, H, W, C;               /* image [B,H,W,C] */
+    int32_t Ho, Wo;                   /* output [B,Ho,Wo,C] */
+    int32_t coord_batch;              /* B, or 1: coordinates shared by the batch */
+    int32_t gain_batch;               /* B, or 1: gain shared by the batch */
+    int32_t gain_channels;            /* C, or 1: gain shared by the channels */
+    int64_t image_stride[4];          /* elements: b, y, x, c */
+    int64_t x_stride[3];              /* elements: b, y, x */
+    int64_t y_stride[3];
+    int64_t gain_stride[4];           /* elements: b, y, x, c */
+    int64_t g_x_stride[3];            /* tl_warp_bwd */
+    int64_t g_y_stride[3];
+    int64_t g_gain_stride[4];
+} tl_warp_geom;
+
+int tl_warp_fwd(const tl_warp_geom *g, const float *image, const float *x, const float *y, const float *gain, float *out,
+                void *stream);
+int tl_warp_bwd(const tl_warp_geom *g, const float *image, const float *x, const float *y, const float *gain, const float *g_out,
+                float *g_x, float *g_y, float *g_gain, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

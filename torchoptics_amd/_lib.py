@@ -75,6 +75,15 @@ class tl_svola_geom(C.Structure):
                 ("image_stride", C.c_int64 * 4), ("psfs_stride", C.c_int64 * 5), ("g_psfs_stride", C.c_int64 * 5)]
 
 
+class tl_warp_geom(C.Structure):
+    _fields_ = [("device", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("Ho", C.c_int32), ("Wo", C.c_int32), ("coord_batch", C.c_int32), ("gain_batch", C.c_int32),
+                ("gain_channels", C.c_int32),
+                ("image_stride", C.c_int64 * 4), ("x_stride", C.c_int64 * 3), ("y_stride", C.c_int64 * 3),
+                ("gain_stride", C.c_int64 * 4), ("g_x_stride", C.c_int64 * 3), ("g_y_stride", C.c_int64 * 3),
+                ("g_gain_stride", C.c_int64 * 4)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -114,6 +123,9 @@ _SIGNATURES = {
     "tl_svola_fwd": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + [_VP]),
     "tl_svola_bwd_psf": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + _WS),
     "tl_svola_bwd_image": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + _WS),
+    # geom | image, x, y, gain | out | stream          and          geom | image, x, y, gain | g_out | g_x, g_y, g_gain | stream
+    "tl_warp_fwd": (C.c_int, [C.POINTER(tl_warp_geom)] + [_VP] * 4 + [_VP] + [_VP]),
+    "tl_warp_bwd": (C.c_int, [C.POINTER(tl_warp_geom)] + [_VP] * 4 + [_VP] + [_VP] * 3 + [_VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -42,6 +42,7 @@ UNITS = {
     "tl_f64.hip": [],          # the double-precision twin (generic, untuned)
     "tl_psf.hip": [],          # the PSF soft histogram (fp32 MFMA forward, per-ray backward)
     "tl_svola.hip": [],        # the spatially varying PSF convolution of an image and its adjoints
+    "tl_warp.hip": [],         # the bicubic image warp (distortion, relative illumination) and its coordinate / gain gradients
 }
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 

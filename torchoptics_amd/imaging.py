@@ -1,5 +1,5 @@
 """
-Rendering an image through the lens: the spatially varying overlap-add convolution of an image with a grid of PSFs (the
+Rendering an image through the lens.  First, the spatially varying overlap-add convolution of an image with a grid of PSFs (the
 reference's `svola_convolution`, image_ops.py:6-98, which cannot run as written: `fft` is undefined, `F.pad(mode='symmetric')`
 and `torch.nn.functional.resize_with_crop_or_pad` do not exist in torch, and it transforms over (C, H) instead of (H, W)).
 
@@ -169,3 +169,155 @@ def psf_grid_from_fields(kernels, grid_shape, index_map=None):
     elif kernels.shape[0] != gh * gw:
         raise ValueError(f"psf_grid_from_fields: {kernels.shape[0]} fields do not fill a {gh} x {gw} grid (give an index_map)")
     return kernels.permute(0, 2, 3, 1).unsqueeze(0)
+
+
+WARP_ALPHA = -0.75        # the cubic convolution parameter of the reference's matrix (image_ops.py:150-153)
+
+
+def _warp_axis(x, n):
+    """One axis of warp_bicubic in plain torch ops: the four clipped tap indices and the four weights, in the arithmetic of
+    the kernel (csrc/tl_warp.hip: axis_taps).  The clamp is written with comparisons, so that x = +-1 exactly passes the
+    gradient and a NaN coordinate stays NaN (torch.clamp's backward would hand a NaN coordinate a zero gradient)."""
+    one = torch.ones((), dtype=x.dtype, device=x.device)
+    xc = torch.where(x < -1, -one, torch.where(x > 1, one, x))
+    u = (xc + 1) / 2 * (n - 1)
+    fl = torch.floor(u.detach())
+    t = u - fl
+    j0 = torch.nan_to_num(fl, nan=0.0).to(torch.long)
+    idx = [(j0 + k).clamp(0, n - 1) for k in (-1, 0, 1, 2)]
+    a, tt = WARP_ALPHA, t * t
+    w = [((a * t - 2 * a) * t + a) * t, ((a + 2) * t - (a + 3)) * tt + 1, ((-(a + 2) * t + (2 * a + 3)) * t - a) * t,
+         (a - a * t) * tt]
+    return idx, w
+
+
+def _warp_torch(image, x, y, gain):
+    """The definition in plain torch ops (any device, any float dtype): 16 gathers and the weight algebra around them."""
+    B, H, W, _ = image.shape
+    cols, wx = _warp_axis(x, W)
+    rows, wy = _warp_axis(y, H)
+    b = torch.arange(B, device=image.device)[:, None, None]
+    out = None
+    for i in range(4):
+        row = None
+        for j in range(4):
+            term = wx[j][..., None] * image[b, rows[i], cols[j]]
+            row = term if row is None else row + term
+        out = wy[i][..., None] * row if out is None else out + wy[i][..., None] * row
+    return out if gain is None else out * gain
+
+
+def warp_bicubic(image, x, y, gain=None, fused=None):
+    """Bicubic resampling of an image at per-pixel source coordinates, times an optional gain: the distortion warp and the
+    relative illumination of a rendered image (the reference's `interpolate_bicubic`, image_ops.py:109-198, which cannot run
+    as written: it calls `.float()` on Python ints, sizes its output by the input's pixel count, and its `base.repeat` only
+    lines up when input and output sizes agree).
+
+    image [B, H, W, C]; x, y [B or 1, Ho, Wo] (the same shape): normalised source coordinates, -1 at the centre of the first
+    column (row) and +1 at the centre of the last; gain [B or 1, Ho, Wo, C or 1] or None.  Returns [B, Ho, Wo, C].
+
+    Per output pixel: xc = clamp(x, -1, 1), u = (xc + 1) / 2 (W - 1), j0 = floor(u), t = u - j0; the taps are the columns
+    j0 - 1, j0, j0 + 1, j0 + 2, each clipped into [0, W - 1] (replicate padding); rows likewise from y and H.  The weights are
+    the reference's matrix with a = -0.75, in order of the tap's offset:
+        w(-1) = a (t^3 - 2 t^2 + t)            w(0) = (a + 2) t^3 - (a + 3) t^2 + 1
+        w(1)  = -(a + 2) t^3 + (2a + 3) t^2 - a t      w(2) = a (t^2 - t^3)
+    and out[b,yo,xo,c] = gain sum_i sum_j wy_i wx_j image[b, row_i, col_j, c].  The weights sum to 1 (constants are
+    reproduced); lines are not (only a = -0.5 does that): on the ramp image[.., q, ..] = q the interior result is
+    j0 + t^3 - 1.5 t^2 + 1.5 t.
+
+    Gradients: d/dx is the derivative weights times (W - 1)/2 where -1 <= x <= 1 (x = +-1 exactly included) and zero outside;
+    the interpolant is C1 across integer u, replicate edges included, and at an integer u the cell with t = 0 is used; d/dy
+    likewise; d/dgain; d/dimage.  Whatever is shared (x, y or gain by the batch, gain by the channels) receives the sum over
+    what shares it.  A NaN coordinate gives NaN in that output pixel and in that pixel's gradients.
+
+    Deviations from the letter of image_ops.py:109-198: (1) the output size comes from the coordinates' shape, not from an
+    `out_size` argument; (2) the coordinates are per-pixel arrays, optionally per lens, not one x and one y vector; (3) the
+    integer sizes are ints; (4) the dead `out_size` and `base` bookkeeping is dropped.  PARITY UNPINNED: the text cannot run.
+
+    `fused=False`: the definition in plain torch ops -- any device, any float dtype, autograd does the rest.  `fused=True`:
+    the HIP kernels of csrc/tl_warp.hip (ops.WarpFunction): float32 tensors on one GPU, one launch forward and one backward
+    for the gradients to x, y and gain; anything else raises (there is no CPU fallback).  The gradient to the image is a
+    scatter and deliberately not a kernel (without atomics it needs a sort or bucket pass; with atomics it would be the first
+    result of this library that is not bit-reproducible): with `image.requires_grad`, `fused=True` raises and says so.
+    `fused=None` (default): the kernels when they apply and the image needs no gradient, torch otherwise."""
+    if image.dim() != 4:
+        raise ValueError(f"warp_bicubic: image must be [B, H, W, C], got {tuple(image.shape)}")
+    B, H, W, Cc = image.shape
+    if x.dim() != 3 or y.shape != x.shape or x.shape[0] not in (1, B):
+        raise ValueError(f"warp_bicubic: x and y must both be [B or 1, Ho, Wo] with B = {B}, got {tuple(x.shape)} and {tuple(y.shape)}")
+    Ho, Wo = x.shape[1:]
+    if min(B, H, W, Cc, Ho, Wo) < 1:
+        raise ValueError(f"warp_bicubic: every size must be at least 1, got image {tuple(image.shape)} and x {tuple(x.shape)}")
+    if gain is not None and (gain.dim() != 4 or gain.shape[0] not in (1, B) or tuple(gain.shape[1:3]) != (Ho, Wo)
+                             or gain.shape[3] not in (1, Cc)):
+        raise ValueError(f"warp_bicubic: gain must be [B or 1, {Ho}, {Wo}, C or 1] with B = {B}, C = {Cc}, got {tuple(gain.shape)}")
+    tensors = [t for t in (image, x, y, gain) if t is not None]
+    applies = image.is_cuda and all(t.device == image.device and t.dtype == torch.float32 for t in tensors)
+    image_grad = image.requires_grad and torch.is_grad_enabled()
+    if fused is None:
+        fused = applies and not image_grad      # the kernels beat the torch path on both recorded workloads (profiles/warp_timing.txt)
+    if not fused:
+        return _warp_torch(image, x, y, gain)
+    if image_grad:
+        raise RuntimeError("warp_bicubic(fused=True): the image requires a gradient, and the image gradient is a scatter that is "
+                           "deliberately not a kernel (it would need atomics, the first result here that is not bit-reproducible, "
+                           "or a sort pass): use fused=False or fused=None, or detach the image")
+    if not applies:
+        what = ", ".join(f"{n} {t.dtype} on {t.device}" for n, t in zip(("image", "x", "y", "gain"), (image, x, y, gain)) if t is not None)
+        raise RuntimeError(f"warp_bicubic(fused=True): {what}; the fused warp runs only as HIP kernels on float32 tensors on "
+                           "one AMD GPU (there is no CPU fallback): use fused=False")
+    return ops.WarpFunction.apply(image, x, y, gain)
+
+
+def _pixel_axes(out_size, aspect, dtype, device):
+    """Normalised pixel-centre coordinates xn [Wo], yn [Ho] (-1 .. +1, 0 for a single pixel) and the relative image height
+    h [Ho, Wo]: the distance from the image centre in units of the half-diagonal.  aspect = width / height (default Wo / Ho)."""
+    Ho, Wo = (int(v) for v in out_size)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"out_size must be (Ho, Wo) >= 1, got {tuple(out_size)}")
+    lin = lambda n: torch.linspace(-1, 1, n, dtype=dtype, device=device) if n > 1 else torch.zeros(1, dtype=dtype, device=device)  # noqa: E731
+    xn, yn = lin(Wo), lin(Ho)
+    a = float(Wo) / float(Ho) if aspect is None else float(aspect)
+    h = torch.sqrt((xn[None, :] * a) ** 2 + yn[:, None] ** 2) / (a * a + 1) ** 0.5
+    return xn, yn, h
+
+
+def radial_map(values, fields, out_size, v0=0.0, aspect=None):
+    """A radial profile painted over the image: values [L, K] or [L, K, C], sampled at the relative fields `fields` [K]
+    (ascending, > 0), become [L, Ho, Wo, C or 1] by piecewise-linear interpolation in h, the pixel's distance from the image
+    centre in units of the half-diagonal (the corner pixels are at h = 1).  There is a node (0, v0) at the centre -- v0 = 0
+    for distortion, 1 for relative illumination -- and the profile is held constant beyond the last field.  `aspect` is the
+    image's width / height (default Wo / Ho: square pixels).  Plain torch ops, differentiable in `values`."""
+    if values.dim() not in (2, 3):
+        raise ValueError(f"radial_map: values must be [L, K] or [L, K, C], got {tuple(values.shape)}")
+    f = torch.as_tensor(fields, dtype=values.dtype, device=values.device).reshape(-1)
+    K = f.numel()
+    if values.shape[1] != K or K < 1:
+        raise ValueError(f"radial_map: values {tuple(values.shape)} hold {values.shape[1]} samples per lens, fields {K}")
+    if not (bool((f > 0).all()) and bool((f[1:] > f[:-1]).all())):
+        raise ValueError("radial_map: fields must be ascending and > 0")
+    v = values if values.dim() == 3 else values[..., None]                               # [L, K, C or 1]
+    _, _, h = _pixel_axes(out_size, aspect, values.dtype, values.device)
+    nodes_h = torch.cat((f.new_zeros(1), f))                                             # [K + 1]
+    nodes_v = torch.cat((torch.full_like(v[:, :1], float(v0)), v), dim=1)                # [L, K + 1, C or 1]
+    seg = (torch.searchsorted(nodes_h, h.contiguous(), right=True) - 1).clamp(0, K - 1)  # [Ho, Wo]
+    frac = ((h - nodes_h[seg]) / (nodes_h[seg + 1] - nodes_h[seg])).clamp(max=1.0)[None, :, :, None]
+    lo, hi = nodes_v[:, seg], nodes_v[:, seg + 1]                                        # [L, Ho, Wo, C or 1]
+    return lo + frac * (hi - lo)
+
+
+def distortion_grid(d, fields, out_size, aspect=None):
+    """The source coordinates that warp an ideal image into the distorted one the sensor sees: d [L, K] is the relative
+    distortion (metrics.compute_distortion) at the relative fields `fields` [K] (ascending, > 0).  Returns x, y [L, Ho, Wo],
+
+        (x, y) = (x_out, y_out) / (1 + D(h_out)),
+
+    D the radial profile of d (radial_map with 0 at the centre), (x_out, y_out) the normalised pixel centres and h_out their
+    relative image height.  This is the first-order inverse of "ideal height -> real height = ideal (1 + D(ideal))": the sensor
+    pixel at the real position samples the scene at the ideal one.  The exact inverse would evaluate D at the ideal height,
+    not at the real one; the difference is O(D D').  Plain torch ops, differentiable in d."""
+    if d.dim() != 2:
+        raise ValueError(f"distortion_grid: d must be [L, K], got {tuple(d.shape)}")
+    D = radial_map(d, fields, out_size, 0.0, aspect)[..., 0]
+    xn, yn, _ = _pixel_axes(out_size, aspect, d.dtype, d.device)
+    return xn[None, None, :] / (1 + D), yn[None, :, None] / (1 + D)

@@ -616,6 +616,75 @@ class SvolaFunction(torch.autograd.Function):
         return g_image, g_psfs, None
 
 
+# C-ABI calls of WarpFunction since import (tests: the backward runs only when a coordinate or the gain needs a gradient), and
+# the pointers the last forward handed to the kernel (strided views go through as they are: no copy)
+_warp_calls = {"fwd": 0, "bwd": 0, "image_ptr": None, "x_ptr": None, "y_ptr": None, "gain_ptr": None}
+
+
+def warp_counts() -> dict:
+    """{'fwd': n, 'bwd': n, 'image_ptr', 'x_ptr', 'y_ptr', 'gain_ptr': data pointers of the last forward's arguments}."""
+    return dict(_warp_calls)
+
+
+class WarpFunction(torch.autograd.Function):
+    """out [B,Ho,Wo,C] = gain x the bicubic resampling of image [B,H,W,C] at the normalised coordinates x, y [B or 1,Ho,Wo]
+    (tl_warp_fwd / tl_warp_bwd; imaging.warp_bicubic(fused=True), which checks the arguments).  gain [B or 1,Ho,Wo,C or 1] or
+    None.
+
+    float32 on one GPU; every tensor is taken with the strides it has.  Differentiable in x, y and gain: one backward launch,
+    and only when one of them needs a gradient.  The image gradient (a scatter) is not a kernel: asking for it raises."""
+
+    @staticmethod
+    def _geom(image, x, y, gain, g_x=None, g_y=None, g_gain=None):
+        B, H, W, Cc = image.shape
+        q = _lib.tl_warp_geom(device=image.device.index, B=B, H=H, W=W, C=Cc, Ho=x.shape[1], Wo=x.shape[2], coord_batch=x.shape[0],
+                              gain_batch=1 if gain is None else gain.shape[0], gain_channels=1 if gain is None else gain.shape[3])
+        q.image_stride[:] = image.stride()
+        q.x_stride[:] = x.stride()
+        q.y_stride[:] = y.stride()
+        q.g_x_stride[:] = (g_x if g_x is not None else x).stride()
+        q.g_y_stride[:] = (g_y if g_y is not None else y).stride()
+        if gain is not None:
+            q.gain_stride[:] = gain.stride()
+            q.g_gain_stride[:] = (g_gain if g_gain is not None else gain).stride()
+        return q
+
+    @staticmethod
+    def forward(ctx, image, x, y, gain):
+        ctx.set_materialize_grads(False)
+        dev = image.device
+        out = torch.empty((image.shape[0], x.shape[1], x.shape[2], image.shape[3]), dtype=torch.float32, device=dev)
+        q = WarpFunction._geom(image, x, y, gain)
+        _call("tl_warp_fwd", dev, C.byref(q), image, x, y, gain, out)
+        _warp_calls["fwd"] += 1
+        _warp_calls.update(image_ptr=image.data_ptr(), x_ptr=x.data_ptr(), y_ptr=y.data_ptr(),
+                           gain_ptr=None if gain is None else gain.data_ptr())
+        ctx.save_for_backward(image, x, y, gain)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        need_image, need_x, need_y, need_gain = ctx.needs_input_grad[:4]
+        if need_image:
+            raise RuntimeError("WarpFunction: the gradient to the image is a scatter and is not a kernel; use "
+                               "imaging.warp_bicubic(fused=False) when the image needs a gradient")
+        if g_out is None or not (need_x or need_y or need_gain):
+            return None, None, None, None
+        image, x, y, gain = ctx.saved_tensors
+        dev = image.device
+        g_out = g_out.to(torch.float32).contiguous()
+        g_x = g_y = g_gain = None
+        if need_x or need_y:
+            g_x = torch.empty(x.shape, dtype=torch.float32, device=dev)
+            g_y = torch.empty(y.shape, dtype=torch.float32, device=dev)
+        if need_gain:
+            g_gain = torch.empty(gain.shape, dtype=torch.float32, device=dev)
+        q = WarpFunction._geom(image, x, y, gain, g_x, g_y, g_gain)
+        _call("tl_warp_bwd", dev, C.byref(q), image, x, y, gain, g_out, g_x, g_y, g_gain)
+        _warp_calls["bwd"] += 1
+        return None, g_x if need_x else None, g_y if need_y else None, g_gain
+
+
 class PupilPositionFunction(torch.autograd.Function):
     """z [B] = paraxial entrance-pupil position from the rows in front of the stop: c, t [B,K], n [B,K+1]
     (tl_pupil_position: one tiny kernel forward, one backward, one thread per lens; mode 'strict': the value is the
