@@ -96,6 +96,59 @@ def test_cabi_error_codes(ta):
     p.B, p.F = 0, 1                                                                 # B = 0 is read as one lens
     assert lib.tl_workspace_bytes(C.byref(p)) > 0
     torch.cuda.synchronize()
+    # The workspace each trace entry asks for, at a valid problem of the same size (F = W = 1, S = 3, P = 64: one block per
+    # grid row): tl_trace_fwd its moment partials alone (1 row x 1 block x 10 moments x 8 B), tl_trace_bwd the checkpoint
+    # kernel's partial row (tl_bwd_row(4, false) = 20 columns x 8 B), tl_trace_bwd_from_outputs all of tl_workspace_bytes.
+    # One byte less is refused; exactly enough gives the gradients of a generous workspace, bit for bit.
+    import yaml_free_lenses as L
+    from torchoptics_amd import ops
+    d = L.PRESCRIPTIONS["singlet"]
+    S, P = 3, 64
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=DEV)        # noqa: E731
+    x_e = torch.linspace(-2.0, 2.0, P, device=DEV).reshape(1, 1, P, 1)
+    y_e = torch.linspace(-1.0, 1.5, P, device=DEV).reshape(1, 1, P, 1)
+    z, cx, cy, c, t = f32([3.0]), f32([[0.02]]), f32([[0.05]]), f32([d["c"]]), f32([d["t"]])
+    mu = f32([[[1.0, 1.0 / d["nd"][0], d["nd"][0]]]])
+    mask = torch.ones(1, S, dtype=torch.uint8, device=DEV)
+    q = ops._problem(x_e, y_e, z, cx, cy, c, t, mu, mask, True, "strict")             # (holds addresses, no references)
+    n = lib.tl_workspace_bytes(C.byref(q))
+    need_f, need_b = 10 * 8, 20 * 8
+    assert n > need_b
+    new = lambda *s: torch.zeros(s, device=DEV)                             # noqa: E731
+    ray = [new(1, 1, 1, P) for _ in range(4)]
+    flag = [torch.zeros(1, 1, 1, P, dtype=torch.uint8, device=DEV) for _ in range(2)]
+    mom = torch.zeros(1, _lib.TL_NMOM, dtype=torch.float64, device=DEV)
+    rays = _lib.rays(x=ray[0], y=ray[1], cx=ray[2], cy=ray[3], ok=flag[0], back=flag[1], moments=mom)
+    sd = dict(gx=new(1, 1, 1, P) + 1e-3, gy=new(1, 1, 1, P) + 1e-3, g_moments=mom.clone() + 1e-3)      # (kept alive here)
+    seeds = _lib.seeds(**sd)
+    st = ops._stream_ptr(torch.device(DEV))
+    EWORKSPACE = -3
+
+    def run(call, nbytes, ws_bytes):
+        """(return code, gradients) of `call` told that its workspace holds nbytes; the buffer itself holds ws_bytes, 0xFF."""
+        ws = torch.full((ws_bytes,), 0xFF, dtype=torch.uint8, device=DEV)
+        gr = dict(g_c=new(1, S), g_t=new(1, S), g_mu=new(1, 1, S), g_z=new(1), g_cx=new(1, 1), g_cy=new(1, 1))
+        # (the forward, told the whole size, clears the walk-back's poison word in front of every backward call)
+        assert lib.tl_trace_fwd(C.byref(q), rays, _lib.ptr(ws), ws_bytes, st) == 0, lib.tl_last_error()
+        rc = call(_lib.grads(**gr), _lib.ptr(ws), nbytes)
+        torch.cuda.synchronize()
+        return rc, torch.cat([v.reshape(-1) for v in gr.values()])
+    fwd = lambda g_, ws_, n_: lib.tl_trace_fwd(C.byref(q), rays, ws_, n_, st)                             # noqa: E731
+    bwd = lambda g_, ws_, n_: lib.tl_trace_bwd(C.byref(q), seeds, g_, ws_, n_, st)                        # noqa: E731
+    inv = lambda g_, ws_, n_: lib.tl_trace_bwd_from_outputs(C.byref(q), seeds, rays, g_, ws_, n_, st)     # noqa: E731
+    for name, call, need in (("tl_trace_fwd", fwd, need_f), ("tl_trace_bwd", bwd, need_b), ("tl_trace_bwd_from_outputs", inv, n)):
+        rc, _ = run(call, need - 1, n)
+        assert rc == EWORKSPACE and b"workspace" in lib.tl_last_error() and name.encode() in lib.tl_last_error(), (name, rc)
+        if call is fwd:
+            mom.zero_()
+            rc, _ = run(call, need, n)
+            assert rc == 0 and flag[0].any() and mom[0, 3].item() == flag[0].sum().item(), (name, rc, lib.tl_last_error())
+            continue
+        rc, got = run(call, need, n)
+        assert rc == 0, (name, lib.tl_last_error())
+        rc, want = run(call, 1 << 20, 1 << 20)
+        assert rc == 0, (name, lib.tl_last_error())
+        assert torch.isfinite(got).all() and got.abs().max().item() > 0 and torch.equal(got, want), (name, got, want)
 
 
 def test_empty_pupil(ta):

@@ -234,6 +234,49 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     assert big - small >= ((1 << 24) - (1 << 20)) // 256 * 4          # one byte per chunk and wave of the block
 
 
+# B, F, W, S, P, asph -> tl_workspace_bytes, tl_workspace_bytes_f64 (no TL_* variable set): the sizes callers have been told
+# since the scan map joined the workspace.  asph = 1: surf_kind, kappa and poly non-NULL (never dereferenced by the sizing).
+WORKSPACE_SIZES = [
+    ((0, 1, 1, 1, 1, 0), 720, 344),
+    ((1, 1, 1, 3, 255, 0), 768, 472),
+    ((1, 3, 3, 7, 256, 0), 4832, 4504),
+    ((1, 3, 3, 7, 257, 0), 9152, 8752),
+    ((1, 3, 3, 5, 0, 0), 4144, 3352),
+    ((2, 3, 3, 4, 100000, 0), 688656, 660496),
+    ((256, 8, 3, 7, 64, 0), 2973952, 2900224),
+    ((4096, 5, 3, 3, 64, 0), 15974656, 13271296),
+    ((1, 3, 3, 11, 1048576, 0), 3391744, 3354880),
+    ((1, 3, 3, 11, 1048576, 1), 7631104, 3354880),
+    ((1, 1, 1, 11, 4194304, 0), 1507584, 1491200),
+    ((1, 8, 3, 13, 4194304, 1), 18317440, 7026304),
+    ((1, 3, 3, 20, 5592406, 0), 10428968, 10691752),
+    ((1, 1, 1, 20, 16777216, 0), 5079296, 5341440),
+    ((1, 1, 1, 21, 65536, 0), 341248, 350464),
+    ((1, 1, 1, 32, 65536, 1), 1129728, 530688),
+    ((1, 1, 1, 33, 4096, 0), 30464, 34432),           # S > 32 is sized as the 32-row bucket (the entry points refuse it)
+    ((1, 3, 3, 7, 16777216, 0), 6783232, 4350208),
+    ((1, 3, 3, 11, 16777216, 1), 17326336, 6709504),
+    ((0, 0, 1, 3, 255, 0), 0, 0),                     # F < 1: no size
+]
+
+
+def test_workspace_sizes_are_pinned():
+    """tl_workspace_bytes / tl_workspace_bytes_f64 over launch plans of every kind (one block per row, a grid that grows,
+    the capped grid, R = 16 rays per lane, lens batches, aspheric rows, every row bucket edge): host arithmetic only."""
+    import ctypes as C
+    from torchoptics_amd import _lib
+    assert not [k for k in os.environ if re.match(r"TL_(FWD|BWD|PLAN)_", k)], "the launch-plan switches change these sizes"
+    dll = _lib.lib()
+    one = 8                                               # any non-NULL address: never dereferenced by the sizing calls
+    for (B, F, W, S, P, asph), want32, want64 in WORKSPACE_SIZES:
+        p = _lib.tl_problem()
+        p.B, p.F, p.W, p.S, p.P = B, F, W, S, P
+        if asph:
+            p.surf_kind = p.kappa = p.poly = one
+        got = (dll.tl_workspace_bytes(C.byref(p)), dll.tl_workspace_bytes_f64(C.byref(p)))
+        assert got == (want32, want64), ((B, F, W, S, P, asph), got)
+
+
 def test_gradient_free_conversions_are_memoised_safely():
     """lens_modeling caches the padding of constant nd / v and their dispersion (an optimisation loop rebuilds
     the same Lens every step).  The cache must notice new data at a recycled address, in-place updates of the

@@ -7,13 +7,12 @@
 #include <stdlib.h>
 #include <string.h>
 
-namespace {
+static thread_local char g_err[512] = "";
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, const char *detail = "")
+namespace tl_host {          // (declared in tl_common.h)
+int fail(int code, const char *msg)
 {
-    snprintf(g_err, sizeof(g_err), fmt, detail);
+    snprintf(g_err, sizeof(g_err), "%s", msg);
     return code;
 }
 
@@ -22,6 +21,22 @@ int hip_fail(int herr, const char *where)
     snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString((hipError_t)herr));
     return TL_ELAUNCH;
 }
+
+int use_device(int device)
+{
+    const hipError_t e = hipSetDevice(device);
+    return e == hipSuccess ? TL_OK : hip_fail(e, "hipSetDevice");
+}
+
+int launched(const char *what)
+{
+    const int herr = (int)hipGetLastError();
+    return herr ? hip_fail(herr, what) : TL_OK;
+}
+}
+using namespace tl_host;
+
+namespace {
 
 constexpr int kBlock = 256;
 
@@ -87,6 +102,68 @@ Plan plan_bwd(const tl_problem *p)
     return make_plan(p->P, rows_bfw(p), cap, rmax, few, chunks * rows_bfw(p) >= (int64_t)rbig * big ? rbig : rwant);
 }
 
+// ---------------------------------------------------------------- the workspace
+// Where the trace entry points keep what in the caller's workspace, from the problem alone: one workspace serves the
+// forward and both backward calls of a step, and each of them finds the same places.
+//
+//   0                                                 total - 256 - scan     total - 256    total - 64    total
+//   | moment partials of the forward             ... | scan map of the      | slack ...    | poison word | ... |
+//   | checkpoint partials (tl_trace_bwd)         ... |  penalty walk-back   |
+//   | walk-back partials | its fallback's        ... |
+//
+// The host reads this struct.  The kernels are handed the poison word's address and count back from it:
+// tl_scanmap(poison, rows, nchunks) in tl_kernels.inc is poison + 64 - 256 - tl_scanmap_bytes(rows, nchunks) (tl_common.h),
+// the `scan` bytes that end 256 bytes before `total` here.
+struct Layout {
+    Plan fwd, bwd, fb;            // plan_fwd, plan_bwd, plan_bwd_fallback
+    int rows;                     // of the grid: rows_bfw
+    int ns, ncol_ck, ncol_inv;    // the checkpoint kernel's row bucket; doubles per partial row of it and of the walk-back
+    size_t mom, ck, inv, inv_fb;  // bytes of the partial arrays: the first three start at 0, the fallback's at `inv`
+    size_t scan, total;
+
+    tl_part part(void *ws, const Plan &pl, size_t off = 0) const { return {(double *)((char *)ws + off), pl.nbx, pl.R}; }
+    unsigned *poison(void *ws) const { return (unsigned *)((char *)ws + total - 64); }
+};
+
+// (the sizing calls answer 0 for these; the entry points refuse them in check_problem)
+inline bool no_layout(const tl_problem *p) { return !p || p->F < 1 || p->W < 1 || p->S < 1 || p->P < 0; }
+
+Layout layout(const tl_problem *p)
+{
+    Layout L{};
+    L.fwd = plan_fwd(p); L.bwd = plan_bwd(p); L.fb = plan_bwd_fallback(p);
+    L.rows = rows_bfw(p);
+    const bool asph = p->surf_kind != nullptr;
+    L.ns = tl_bwd_bucket(p->S) < 0 ? TL_MAX_SURFACES : tl_bwd_bucket(p->S);     // (S > 32 is sized as 32 and refused by the entries)
+    L.ncol_ck = tl_bwd_row(L.ns, asph);
+    L.ncol_inv = (asph ? 8 : 3) * p->S + 3;
+    const size_t rows = (size_t)L.rows;
+    L.mom = rows * L.fwd.nbx * TL_NMOM * sizeof(double);
+    L.ck = rows * L.bwd.nbx * (size_t)L.ncol_ck * sizeof(double);
+    L.inv = rows * L.bwd.nbx * (size_t)L.ncol_inv * sizeof(double);
+    L.inv_fb = rows * L.fb.nbx * (size_t)L.ncol_ck * sizeof(double);
+    L.scan = tl_scanmap_bytes(L.rows, ((int64_t)p->P + kBlock - 1) / kBlock);
+    // the walk-back next to the larger of the two checkpoint grids (the fallback's is the smaller one under the default
+    // plan; TL_PLAN_FEW / TL_PLAN_R can make it the larger): more than the picture needs when ck > inv_fb, and the size
+    // callers have always been told
+    const size_t back = L.inv + (L.ck > L.inv_fb ? L.ck : L.inv_fb);
+    L.total = (L.mom > back ? L.mom : back) + L.scan + 256;
+    return L;
+}
+
+// the double-precision twin: moment partials or the backward's (8 S + 3 columns) at 0, 256 bytes of slack
+Layout layout_f64(const tl_problem *p)
+{
+    Layout L{};
+    L.fwd = plan_fwd(p); L.bwd = plan_bwd(p);
+    L.rows = rows_bfw(p);
+    L.ncol_ck = 8 * p->S + 3;
+    L.mom = (size_t)L.rows * L.fwd.nbx * TL_NMOM * sizeof(double);
+    L.ck = (size_t)L.rows * L.bwd.nbx * (size_t)L.ncol_ck * sizeof(double);
+    L.total = (L.mom > L.ck ? L.mom : L.ck) + 256;
+    return L;
+}
+
 int check_problem(const tl_problem *p)
 {
     if (!p) return fail(TL_EINVAL, "tl_problem is NULL");
@@ -145,7 +222,7 @@ __device__ __forceinline__ double sum_rows(const double *part, int64_t nrows, in
     return block_sum_256(acc, sm);
 }
 
-// clear_word (nullable): the walk-back's poison word of this problem's workspace (poison_word below), cleared here
+// clear_word (nullable): the walk-back's poison word of this problem's workspace (Layout::poison), cleared here
 // so that a step replayed from a HIP graph -- same token every replay -- starts clean without a memset node
 __global__ __launch_bounds__(kBlock) void reduce_moments_kernel(const double *__restrict__ part,
                                                                 double *__restrict__ mom, int W, int nbx,
@@ -158,35 +235,35 @@ __global__ __launch_bounds__(kBlock) void reduce_moments_kernel(const double *__
     if (clear_word && blockIdx.x == 0 && threadIdx.x == 0) *clear_word = 0u;
 }
 
-__global__ __launch_bounds__(kBlock) void reduce_bwd_kernel(const double *__restrict__ part, int NS, int F,
-                                                            int W, int S, int nbx, float *__restrict__ g_c,
-                                                            float *__restrict__ g_t, float *__restrict__ g_mu,
-                                                            float *__restrict__ g_z, float *__restrict__ g_cx,
-                                                            float *__restrict__ g_cy, int ncol,
-                                                            float *__restrict__ g_kappa, float *__restrict__ g_poly,
-                                                            const double *__restrict__ alt_part, int alt_NS,
-                                                            const double *__restrict__ fmom,
-                                                            const unsigned *__restrict__ poison,
-                                                            unsigned token, int alt_nbx, float *__restrict__ g_n,
-                                                            int add_alt)
+// One array of block partials to sum: its rows were written for `ns` surface rows by nbx blocks per grid row.
+struct RedSrc { const double *part; int ns, nbx; };
+// When a second array (the checkpoint fallback's) stands behind the first: what decides between them, or for their sum.
+// add_dead: the fallback took the rays that died on the way (penalty term); split_ill: the forward left per-ray conditioning
+// flags (tl_problem.cond_flags), so ill-conditioned rays were split between the two launches as well.
+struct RedPick { const double *fmom; const unsigned *poison; unsigned token; bool add_dead, split_ill; };
+
+__global__ __launch_bounds__(kBlock) void reduce_bwd_kernel(const RedSrc src, const RedSrc alt, const RedPick pick, int F, int W,
+                                                            int S, const tl_grads g)
 {
     __shared__ double sm[kBlock];
-    // two candidate partial arrays (walk-back kernel / checkpoint fallback): the forward's conditioning count
-    // and the walk-back's poison word (== this call's token) say which of the two launches did the work (same rule as
-    // fallback_needed in tl_kernels.inc).  add_alt (penalty term): when the walk-back did its work, the checkpoint
-    // launch behind it took the rays that died on the way -- the result is the SUM of the two arrays.
+    // two candidate partial arrays (walk-back kernel / checkpoint fallback; alt all zero: no second array): the forward's
+    // conditioning count and the walk-back's poison word (== this call's token) say which of the two launches did the work
+    // (same rule as fallback_needed in tl_kernels.inc).  add_dead (penalty term): when the walk-back did its work, the
+    // checkpoint launch behind it took the rays that died on the way -- the result is the SUM of the two arrays.
     // The count and the word are read FIRST and looked at LAST: the sum over the walk-back's array -- nearly always the
     // one that counts -- is formed while those loads are in flight (two dependent round trips off this tiny kernel).
     double n_ill = 0.0;
     unsigned pz = 0u;
-    if (alt_part) {
-        if (fmom)
-            for (int f = 0; f < F * (int)gridDim.y; ++f) n_ill += fmom[(size_t)f * TL_NMOM + 9];
-        if (poison) pz = *poison;
+    if (alt.part) {
+        if (pick.fmom)
+            for (int f = 0; f < F * (int)gridDim.y; ++f) n_ill += pick.fmom[(size_t)f * TL_NMOM + 9];
+        if (pick.poison) pz = *pick.poison;
     }
     // one block per output scalar: g_c[S] | g_t[S] | g_mu[W,S] | g_z | g_cx[F] | g_cy[F] [| g_kappa[S] | g_poly[S,4]] [| g_n[W,S+1]]
     // of lens blockIdx.y, whose partial rows are those of the fields [lens F, (lens + 1) F)
     const int lens = blockIdx.y;
+    float *g_c = g.g_c, *g_t = g.g_t, *g_mu = g.g_mu, *g_z = g.g_z, *g_cx = g.g_cx, *g_cy = g.g_cy;
+    float *g_kappa = g.g_kappa, *g_poly = g.g_poly, *g_n = g.g_n_index;
     g_c += lens * S; g_t += lens * S; g_mu += lens * W * S; g_z += lens; g_cx += lens * F; g_cy += lens * F;
     if (g_kappa) { g_kappa += lens * S; g_poly += lens * S * TL_MAX_POLY; }
     if (g_n) g_n += lens * W * (S + 1);
@@ -209,15 +286,13 @@ __global__ __launch_bounds__(kBlock) void reduce_bwd_kernel(const double *__rest
         const int w = b / (S + 1), k = b % (S + 1);
         ca = g_kappa ? 8 : 3; c0 = 3 + k; w0 = w; nw = 1; out = g_n + b;
     }
-    (void)ncol;
-    double s = sum_rows(part, (int64_t)gridDim.y * F * W * nbx, ca * NS + c0, W, nbx, lens * F + f0, nf, w0, nw, sm);
-    if (alt_part) {
-        // add_alt bit 1: the forward left per-ray conditioning flags (tl_problem.cond_flags), so ill-conditioned rays
-        // (n_ill > 0) were split between the two launches as well, instead of sending the whole launch to the checkpoint kernel
-        const bool alt_only = (n_ill > 0.0 && !(add_alt & 2)) || (poison && pz == token);
-        if (alt_only || (add_alt & 1) || n_ill > 0.0) {
+    double s = sum_rows(src.part, (int64_t)gridDim.y * F * W * src.nbx, ca * src.ns + c0, W, src.nbx, lens * F + f0, nf, w0, nw, sm);
+    if (alt.part) {
+        // split_ill: ill-conditioned rays (n_ill > 0) were split per ray, instead of sending the whole launch to the checkpoint kernel
+        const bool alt_only = (n_ill > 0.0 && !pick.split_ill) || (pick.poison && pz == pick.token);
+        if (alt_only || pick.add_dead || n_ill > 0.0) {
             __syncthreads();                          // sm is reused
-            const double s2 = sum_rows(alt_part, (int64_t)gridDim.y * F * W * alt_nbx, ca * alt_NS + c0, W, alt_nbx,
+            const double s2 = sum_rows(alt.part, (int64_t)gridDim.y * F * W * alt.nbx, ca * alt.ns + c0, W, alt.nbx,
                                        lens * F + f0, nf, w0, nw, sm);
             s = alt_only ? s2 : s + s2;
         }
@@ -377,12 +452,6 @@ __global__ __launch_bounds__(kBlock) void spot_seed_kernel(int P, int W, const f
 }
 
 }  // namespace
-
-// the calling thread's error message, for the other translation units that hold C-ABI entry points (tl_psf.hip)
-namespace tl_host {
-int fail(int code, const char *msg) { return ::fail(code, "%s", msg); }
-int hip_fail(int herr, const char *where) { return ::hip_fail(herr, where); }
-}
 
 // =================================================================== C ABI
 // Paraxial entrance-pupil position (the `z` argument of the trace): z = B/A of the ordered product
@@ -718,27 +787,7 @@ const char *tl_last_error(void) { return g_err; }
 
 size_t tl_problem_size(void) { return sizeof(tl_problem); }
 
-// The walk-back kernel's poison word lives in the slack at the END of the workspace this problem asks for (the
-// last 256 bytes belong to no partial array), at an address tl_trace_fwd can compute as well.
-static unsigned *poison_word(const tl_problem *p, void *workspace)
-{
-    return (unsigned *)((char *)workspace + tl_workspace_bytes(p) - 64);
-}
-
-size_t tl_workspace_bytes(const tl_problem *p)
-{
-    if (!p || p->F < 1 || p->W < 1 || p->S < 1 || p->P < 0) return 0;
-    const Plan pf = plan_fwd(p), pb = plan_bwd(p), pk = plan_bwd_fallback(p);
-    const int ns = tl_bwd_bucket(p->S);
-    const size_t fw = (size_t)rows_bfw(p);
-    const size_t a = fw * pf.nbx * TL_NMOM * sizeof(double);
-    // (the fallback's grid is the smaller one under the default plan; TL_PLAN_FEW / TL_PLAN_R can make it the larger)
-    const size_t b = fw * (pb.nbx > pk.nbx ? pb.nbx : pk.nbx) * (size_t)tl_bwd_row(ns < 0 ? TL_MAX_SURFACES : ns, p->surf_kind != nullptr) * sizeof(double);
-    const size_t c = fw * pb.nbx * (size_t)((p->surf_kind ? 8 : 3) * p->S + 3) * sizeof(double);   // walk-back kernel next to its fallback
-    // + the penalty walk-back's scan map, right below the 256-byte slack at the end (the poison word lives in that slack)
-    const size_t scan = tl_scanmap_bytes(rows_bfw(p), ((int64_t)p->P + kBlock - 1) / kBlock);
-    return (a > b + c ? a : b + c) + scan + 256;
-}
+size_t tl_workspace_bytes(const tl_problem *p) { return no_layout(p) ? 0 : layout(p).total; }
 
 int tl_trace_fwd(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream)
 {
@@ -756,32 +805,34 @@ int tl_trace_fwd(const tl_problem *p, const tl_rays *out, void *workspace, size_
         }
         return TL_OK;
     }
-    hipError_t e = hipSetDevice(p->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const Plan pl = plan_fwd(p);
-    double *part = nullptr;
-    if (moments) {
-        const size_t need = (size_t)rows_bfw(p) * pl.nbx * TL_NMOM * sizeof(double);
-        if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_fwd");
-        part = (double *)workspace;
-    }
+    if ((rc = use_device(p->device))) return rc;
+    const Layout L = layout(p);
+    if (moments && (!workspace || workspace_bytes < L.mom)) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_fwd");
+    const tl_part part = L.part(moments ? workspace : nullptr, L.fwd);
+    // given the whole workspace, the forward clears the walk-back's poison word for a replayed step (reduce_moments_kernel)
+    unsigned *const clear = (workspace && workspace_bytes >= L.total) ? L.poison(workspace) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     tl_problem q = *p;
     if (!out->opd) q.n_index = nullptr;          // the kernel accumulates the path length only when asked
-    int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_fwd(q, *out, part, pl.nbx, pl.R, st)
-                                         : tl_strict::api_fwd(q, *out, part, pl.nbx, pl.R, st);
+    const int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_fwd(q, *out, part, st) : tl_strict::api_fwd(q, *out, part, st);
     if (herr) return hip_fail(herr, "trace_fwd_kernel launch");
     if (moments) {
-        unsigned *clear = (workspace_bytes >= tl_workspace_bytes(p)) ? poison_word(p, workspace) : nullptr;
-        hipLaunchKernelGGL(reduce_moments_kernel, dim3(lenses(p) * p->F * TL_NMOM), dim3(kBlock), 0, st, part, moments, p->W, pl.nbx, clear);
-        herr = (int)hipGetLastError();
-        if (herr) return hip_fail(herr, "reduce_moments_kernel launch");
-    } else if (workspace && workspace_bytes >= tl_workspace_bytes(p)) {
-        // no moments, so no reduction kernel to clear the walk-back's poison word for a replayed step: clear it here
-        hipError_t e2 = hipMemsetAsync(poison_word(p, workspace), 0, sizeof(unsigned), st);
-        if (e2 != hipSuccess) return hip_fail(e2, "hipMemsetAsync(poison word)");
+        hipLaunchKernelGGL(reduce_moments_kernel, dim3(lenses(p) * p->F * TL_NMOM), dim3(kBlock), 0, st, part.part, moments, p->W, part.nbx, clear);
+        return launched("reduce_moments_kernel launch");
+    }
+    if (clear) {                                 // no moments, so no reduction kernel to clear the word: clear it here
+        const hipError_t e = hipMemsetAsync(clear, 0, sizeof(unsigned), st);
+        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(poison word)");
     }
     return TL_OK;
+}
+
+// the sums over one partial array, or over the two of a walk-back (alt, pick: see reduce_bwd_kernel), into the gradients
+static int reduce_bwd(const tl_problem *p, const tl_grads *out, const RedSrc &src, const RedSrc &alt, const RedPick &pick, hipStream_t st)
+{
+    const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (p->surf_kind ? 5 * p->S : 0) + (out->g_n_index ? p->W * (p->S + 1) : 0);
+    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, src, alt, pick, p->F, p->W, p->S, *out);
+    return launched("reduce_bwd_kernel launch");
 }
 
 // the argument checks both backward entry points share (before any HIP call)
@@ -806,10 +857,10 @@ int tl_trace_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out, vo
     int rc = check_bwd(p, g, out);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(p->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if ((rc = use_device(p->device))) return rc;
     if (p->P == 0) {
         const size_t S = p->S, B = (size_t)lenses(p);
+        hipError_t e;
         if ((e = hipMemsetAsync(out->g_c, 0, B * S * 4, st)) || (e = hipMemsetAsync(out->g_t, 0, B * S * 4, st)) ||
             (e = hipMemsetAsync(out->g_mu, 0, B * S * p->W * 4, st)) || (e = hipMemsetAsync(out->g_z, 0, B * 4, st)) ||
             (e = hipMemsetAsync(out->g_cx, 0, B * p->F * 4, st)) || (e = hipMemsetAsync(out->g_cy, 0, B * p->F * 4, st)) ||
@@ -819,23 +870,12 @@ int tl_trace_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out, vo
             return hip_fail(e, "hipMemsetAsync(grads)");
         return TL_OK;
     }
-    const Plan pl = plan_bwd(p);
-    const int ns = tl_bwd_bucket(p->S);
-    const bool asph = p->surf_kind != nullptr;
-    const int ncol = tl_bwd_row(ns, asph);
-    const size_t need = (size_t)rows_bfw(p) * pl.nbx * (size_t)ncol * sizeof(double);
-    if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd");
-    double *part = (double *)workspace;
-    int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_bwd(*p, *g, *out, part, pl.nbx, pl.R, st)
-                                         : tl_strict::api_bwd(*p, *g, *out, part, pl.nbx, pl.R, st);
+    const Layout L = layout(p);
+    if (!workspace || workspace_bytes < L.ck) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd");
+    const tl_part part = L.part(workspace, L.bwd);
+    const int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_bwd(*p, *g, *out, part, st) : tl_strict::api_bwd(*p, *g, *out, part, st);
     if (herr) return hip_fail(herr, "trace_bwd_kernel launch");
-    const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0) + (g->g_opd ? p->W * (p->S + 1) : 0);
-    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, ns, p->F, p->W, p->S, pl.nbx, out->g_c,
-                       out->g_t, out->g_mu, out->g_z, out->g_cx, out->g_cy, ncol, out->g_kappa, out->g_poly,
-                       (const double *)nullptr, 0, (const double *)nullptr, (const unsigned *)nullptr, 0u, 0, out->g_n_index, 0);
-    herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "reduce_bwd_kernel launch");
-    return TL_OK;
+    return reduce_bwd(p, out, {part.part, L.ns, part.nbx}, RedSrc{}, RedPick{}, st);
 }
 
 int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_rays *fwd, const tl_grads *out,
@@ -859,36 +899,20 @@ int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_r
     if ((p->aggregate && !(tl_walk_unrolled(p->S, p->P) && hits_ok)) || p->P == 0)
         return tl_trace_bwd(p, g, out, workspace, workspace_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipSetDevice(p->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const Plan pl = plan_bwd(p);
-    const Plan pk = plan_bwd_fallback(p);              // the fallback is launched too
-    const bool asph = p->surf_kind != nullptr;
-    const int ncol = (asph ? 8 : 3) * p->S + 3, ns = tl_bwd_bucket(p->S), ncol_ck = tl_bwd_row(ns, asph);
-    const size_t rows = (size_t)rows_bfw(p) * pl.nbx, rows_ck = (size_t)rows_bfw(p) * pk.nbx;
-    const size_t need_inv = rows * ncol * sizeof(double), need_ck = rows_ck * ncol_ck * sizeof(double);
-    const size_t need_scan = tl_scanmap_bytes(rows_bfw(p), ((int64_t)p->P + kBlock - 1) / kBlock);
-    if (!workspace || workspace_bytes < tl_workspace_bytes(p) || tl_workspace_bytes(p) < need_inv + need_ck + need_scan + 256)
-        return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd_from_outputs");
-    double *part = (double *)workspace, *part_ck = part + rows * ncol;
-    unsigned *poison = poison_word(p, workspace);      // the walk-back writes `token` here on a non-finite adjoint
+    if ((rc = use_device(p->device))) return rc;
+    const Layout L = layout(p);                        // the fallback is launched too: both partial arrays, scan map, poison word
+    if (!workspace || workspace_bytes < L.total) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd_from_outputs");
     static std::atomic<uint32_t> calls{0};
     uint32_t token = (calls.fetch_add(1u) + 1u) * 0x9E3779B1u;         // unique per call, nothing like stale data
     if (token == 0u) token = 1u;
     // (Recorded into a HIP graph the call is replayed with the SAME token every time; the word is cleared by the
     //  forward call of the same step, see reduce_moments_kernel, so a poisoned replay does not stick.)
-    int herr = (p->mode == TL_MODE_FAST)
-                   ? tl_fast::api_bwd_inv(*p, *g, f, *out, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st)
-                   : tl_strict::api_bwd_inv(*p, *g, f, *out, part, part_ck, poison, token, pl.nbx, pl.R, pk.nbx, pk.R, st);
+    // the walk-back writes `token` into the poison word on a non-finite adjoint
+    const tl_walkback w = {L.part(workspace, L.bwd), L.part(workspace, L.fb, L.inv), L.poison(workspace), token};
+    const int herr = (p->mode == TL_MODE_FAST) ? tl_fast::api_bwd_inv(*p, *g, f, *out, w, st) : tl_strict::api_bwd_inv(*p, *g, f, *out, w, st);
     if (herr) return hip_fail(herr, "trace_bwd_inv_kernel launch");
-    const int nout = 2 * p->S + p->W * p->S + 1 + 2 * p->F + (asph ? 5 * p->S : 0);
-    hipLaunchKernelGGL(reduce_bwd_kernel, dim3(nout, lenses(p)), dim3(kBlock), 0, st, part, p->S, p->F, p->W, p->S, pl.nbx, out->g_c,
-                       out->g_t, out->g_mu, out->g_z, out->g_cx, out->g_cy, ncol, out->g_kappa, out->g_poly,
-                       (const double *)part_ck, ns, (const double *)f.moments, (const unsigned *)poison, token, pk.nbx,
-                       (float *)nullptr, (p->aggregate ? 1 : 0) | (p->cond_flags ? 2 : 0));
-    herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "reduce_bwd_kernel launch");
-    return TL_OK;
+    return reduce_bwd(p, out, {w.inv.part, p->S, w.inv.nbx}, {w.ck.part, L.ns, w.ck.nbx},
+                      {f.moments, w.poison, token, p->aggregate != 0, p->cond_flags != nullptr}, st);
 }
 
 int tl_spot_moments(int32_t device, int32_t F, int32_t P, int32_t W, const float *x, const float *y,
@@ -897,21 +921,18 @@ int tl_spot_moments(int32_t device, int32_t F, int32_t P, int32_t W, const float
 {
     if (F < 1 || W < 1 || P < 1 || !y || !ok || !moments) return fail(TL_EINVAL, "tl_spot_moments: bad argument");
     if ((int64_t)F * W > 65535) return fail(TL_EINVAL, "F*W exceeds 65535");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     const Plan pl = make_plan(P, F * W, 4096, 64);
     const size_t need = (size_t)F * W * pl.nbx * TL_NMOM * sizeof(double);
     if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_spot_moments");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(spot_moments_kernel, dim3(pl.nbx, F * W), dim3(kBlock), 0, st, P, W, x, y, ok, s_f, s_p, s_w,
                        (double *)workspace, pl.R);
-    int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "spot_moments_kernel launch");
+    if (const int rc = launched("spot_moments_kernel launch")) return rc;
+    unsigned *const no_poison_word = nullptr;                    // (no walk-back shares this workspace)
     hipLaunchKernelGGL(reduce_moments_kernel, dim3(F * TL_NMOM), dim3(kBlock), 0, st, (const double *)workspace,
-                       moments, W, pl.nbx, (unsigned *)nullptr);
-    herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "reduce_moments_kernel launch");
-    return TL_OK;
+                       moments, W, pl.nbx, no_poison_word);
+    return launched("reduce_moments_kernel launch");
 }
 
 int tl_spot_rms(int32_t device, int32_t B, int32_t F, double n_per_field, const double *moments, float *rms,
@@ -919,12 +940,9 @@ int tl_spot_rms(int32_t device, int32_t B, int32_t F, double n_per_field, const 
 {
     if (B < 1 || F < 1 || !(n_per_field > 0.0) || !moments || !rms || !d_moments)
         return fail(TL_EINVAL, "tl_spot_rms: bad argument");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(spot_rms_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, moments, F, n_per_field, rms, d_moments);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "spot_rms_kernel launch");
-    return TL_OK;
+    return launched("spot_rms_kernel launch");
 }
 
 int tl_unsup_loss(int32_t device, int32_t B, int32_t F, double n_per_field, const double *moments, const double *n_sequence,
@@ -934,13 +952,10 @@ int tl_unsup_loss(int32_t device, int32_t B, int32_t F, double n_per_field, cons
     if (B < 1 || F < 1 || !(n_per_field > 0.0) || !moments || !loss || !rms || !penalty || !d_rms ||
         (!n_sequence && !(n_sequence_all > 0.0)))
         return fail(TL_EINVAL, "tl_unsup_loss: bad argument");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(unsup_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, moments, F, n_per_field, n_sequence,
                        n_sequence_all, penalty_rate, loss, rms, penalty, d_rms);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "unsup_loss_kernel launch");
-    return TL_OK;
+    return launched("unsup_loss_kernel launch");
 }
 
 int tl_unsup_loss_bwd(int32_t device, int32_t B, int32_t F, const double *d_rms, const float *g_loss, const float *g_rms,
@@ -950,14 +965,11 @@ int tl_unsup_loss_bwd(int32_t device, int32_t B, int32_t F, const double *d_rms,
     if (B < 1 || F < 1 || !d_rms || !g_moments || (!g_loss && !g_rms && !g_penalty) || (g_stride != 0 && g_stride != 1) ||
         (!n_sequence && !(n_sequence_all > 0.0)))
         return fail(TL_EINVAL, "tl_unsup_loss_bwd: bad argument");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     const int total = B * F * TL_NMOM;
     hipLaunchKernelGGL(unsup_loss_bwd_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, d_rms, F,
                        total, g_loss, g_rms, g_penalty, g_stride, n_sequence, n_sequence_all, penalty_rate, g_moments);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "unsup_loss_bwd_kernel launch");
-    return TL_OK;
+    return launched("unsup_loss_bwd_kernel launch");
 }
 
 int tl_spot_seed(int32_t device, int32_t F, int32_t P, int32_t W, const float *x, const float *y, const uint8_t *ok,
@@ -965,13 +977,10 @@ int tl_spot_seed(int32_t device, int32_t F, int32_t P, int32_t W, const float *x
 {
     if (F < 1 || W < 1 || P < 1 || !y || !ok || !g_moments) return fail(TL_EINVAL, "tl_spot_seed: bad argument");
     if ((int64_t)F * W > 65535) return fail(TL_EINVAL, "F*W exceeds 65535");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(spot_seed_kernel, dim3((P + kBlock - 1) / kBlock, F * W), dim3(kBlock), 0, (hipStream_t)stream,
                        P, W, x, y, ok, s_f, s_p, s_w, g_moments, gx, gy);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "spot_seed_kernel launch");
-    return TL_OK;
+    return launched("spot_seed_kernel launch");
 }
 
 int tl_pupil_position(int32_t device, int32_t B, int32_t K, const float *c, const float *t, const float *n, float *z,
@@ -981,13 +990,10 @@ int tl_pupil_position(int32_t device, int32_t B, int32_t K, const float *c, cons
     if (B < 1 || K < 1 || K > TL_MAX_SURFACES || !c || !t || !n) return fail(TL_EINVAL, "tl_pupil_position: bad argument");
     if (!z && !g_z) return fail(TL_EINVAL, "tl_pupil_position: neither z nor g_z given");
     if (g_z && (!g_c || !g_t || !g_n)) return fail(TL_EINVAL, "tl_pupil_position: g_z needs g_c, g_t and g_n");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(pupil_position_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, K, c, t, n, z, g_z, g_c, g_t, g_n,
                        mode == TL_MODE_STRICT ? 1 : 0);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "pupil_position_kernel launch");
-    return TL_OK;
+    return launched("pupil_position_kernel launch");
 }
 
 // The aimed fan in one launch: x = clamp(xp x_scale, -2, 2) (epd / 2), y = clamp(yp y_scale + y_offset, -2, 2) (epd / 2) --
@@ -1020,13 +1026,10 @@ int tl_aim_fan(int32_t device, int32_t B, int32_t F, int32_t W, int32_t P, const
     if (B < 1 || F < 1 || W < 1 || P < 1 || !xp || !yp || !x_scale || !y_scale || !y_offset || !epd || !x_out || !y_out)
         return fail(TL_EINVAL, "tl_aim_fan: bad argument");
     if ((int64_t)B * F * W > 65535) return fail(TL_EINVAL, "B*F*W exceeds 65535");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(aim_fan_kernel, dim3((P + kBlock - 1) / kBlock, B * F * W), dim3(kBlock), 0, (hipStream_t)stream, P, F, W, xp,
                        yp, x_scale, y_scale, y_offset, epd, x_out, y_out);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "aim_fan_kernel launch");
-    return TL_OK;
+    return launched("aim_fan_kernel launch");
 }
 
 int tl_ray_aim(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const float *c, const float *t, const float *n,
@@ -1039,14 +1042,11 @@ int tl_ray_aim(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const
         return fail(TL_EINVAL, "tl_ray_aim: bad argument");
     if ((surf_kind != nullptr) != (kappa != nullptr) || (surf_kind != nullptr) != (poly != nullptr))
         return fail(TL_EINVAL, "tl_ray_aim: surf_kind, kappa and poly must be given together (or all NULL)");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     const int nthr = B * F * W;
     hipLaunchKernelGGL(ray_aim_kernel, dim3((nthr + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, F, W, K, c, t, n, n_d, mask,
                        kappa, poly, surf_kind, z, hfov, fields, epd, allow_backward, x_scale, y_scale, y_offset);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "ray_aim_kernel launch");
-    return TL_OK;
+    return launched("ray_aim_kernel launch");
 }
 
 int tl_ray_aim_iter(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, const float *c, const float *t, const float *n,
@@ -1064,14 +1064,11 @@ int tl_ray_aim_iter(int32_t device, int32_t B, int32_t F, int32_t W, int32_t K, 
         return fail(TL_EINVAL, "tl_ray_aim_iter: surf_kind, kappa and poly must be given together (or all NULL)");
     const int64_t groups = (int64_t)B * F * W, per_block = 64 / kAimGroup;
     if (groups > INT32_MAX / kAimGroup) return fail(TL_EINVAL, "tl_ray_aim_iter: B*F*W too large");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(ray_aim_iter_kernel, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(64), 0,
                        (hipStream_t)stream, B, F, W, K, c, t, n, n_d, mask, kappa, poly, surf_kind, z, hfov, fields, epd,
                        allow_backward, n_iter, tee_ref, rs, x_scale, y_scale, y_offset);
-    const int herr = (int)hipGetLastError();
-    if (herr) return hip_fail(herr, "ray_aim_iter_kernel launch");
-    return TL_OK;
+    return launched("ray_aim_iter_kernel launch");
 }
 
 // ---------------------------------------------------------------- double precision (RayTracer(double_precision=True))
@@ -1084,14 +1081,7 @@ static int check_f64(const tl_problem *p)
     return TL_OK;
 }
 
-size_t tl_workspace_bytes_f64(const tl_problem *p)
-{
-    if (!p || p->F < 1 || p->W < 1 || p->S < 1 || p->P < 0) return 0;
-    const Plan pb = plan_bwd(p), pf = plan_fwd(p);
-    const size_t rows = (size_t)rows_bfw(p);
-    const size_t a = rows * pf.nbx * TL_NMOM * sizeof(double), b = rows * pb.nbx * (size_t)(8 * p->S + 3) * sizeof(double);
-    return (a > b ? a : b) + 256;
-}
+size_t tl_workspace_bytes_f64(const tl_problem *p) { return no_layout(p) ? 0 : layout_f64(p).total; }
 
 int tl_trace_fwd_f64(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream)
 {
@@ -1099,19 +1089,14 @@ int tl_trace_fwd_f64(const tl_problem *p, const tl_rays *out, void *workspace, s
     if (rc) return rc;
     if (!out) return fail(TL_EINVAL, "the tl_rays block is NULL");
     if (out->opd || out->stacks) return fail(TL_EINVAL, "the double-precision trace has no opd and no stacks output");
-    hipError_t e = hipSetDevice(p->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const Plan pl = plan_fwd(p);
-    double *part = nullptr;
-    if (out->moments) {
-        const size_t need = (size_t)rows_bfw(p) * pl.nbx * TL_NMOM * sizeof(double);
-        if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_fwd_f64");
-        part = (double *)workspace;
-    }
-    int herr = tl_f64::launch_fwd(*p, *out, part, pl.nbx, (hipStream_t)stream);
+    if ((rc = use_device(p->device))) return rc;
+    const Layout L = layout_f64(p);
+    if (out->moments && (!workspace || workspace_bytes < L.mom)) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_fwd_f64");
+    double *const part = out->moments ? (double *)workspace : nullptr;
+    int herr = tl_f64::launch_fwd(*p, *out, part, L.fwd.nbx, (hipStream_t)stream);
     if (herr) return hip_fail(herr, "tl_f64::fwd_kernel launch");
     if (out->moments) {
-        herr = tl_f64::launch_reduce_moments(*p, part, out->moments, pl.nbx, (hipStream_t)stream);
+        herr = tl_f64::launch_reduce_moments(*p, part, out->moments, L.fwd.nbx, (hipStream_t)stream);
         if (herr) return hip_fail(herr, "tl_f64::reduce_moments_kernel launch");
     }
     return TL_OK;
@@ -1128,12 +1113,10 @@ int tl_trace_bwd_f64(const tl_problem *p, const tl_seeds *g, const tl_grads *out
     if (!out->g_c || !out->g_t || !out->g_mu || !out->g_z || !out->g_cx || !out->g_cy)
         return fail(TL_EINVAL, "a parameter-gradient output is NULL");
     if (p->surf_kind && (!out->g_kappa || !out->g_poly)) return fail(TL_EINVAL, "aspheric rows need g_kappa and g_poly outputs");
-    hipError_t e = hipSetDevice(p->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const Plan pl = plan_bwd(p);
-    const size_t need = (size_t)rows_bfw(p) * pl.nbx * (size_t)(8 * p->S + 3) * sizeof(double);
-    if (!workspace || workspace_bytes < need) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd_f64");
-    const int herr = tl_f64::launch_bwd(*p, *g, *out, (double *)workspace, pl.nbx, (hipStream_t)stream);
+    if ((rc = use_device(p->device))) return rc;
+    const Layout L = layout_f64(p);
+    if (!workspace || workspace_bytes < L.ck) return fail(TL_EWORKSPACE, "workspace too small for tl_trace_bwd_f64");
+    const int herr = tl_f64::launch_bwd(*p, *g, *out, (double *)workspace, L.bwd.nbx, (hipStream_t)stream);
     if (herr) return hip_fail(herr, "tl_f64::bwd_kernel launch");
     return TL_OK;
 }
@@ -1143,8 +1126,7 @@ int tl_selftest_arith(int32_t device, int32_t mode, const float *a, const float 
 {
     if (!a || !b || !quot || !root || n < 1) return fail(TL_EINVAL, "tl_selftest_arith: bad argument");
     if (mode != TL_MODE_STRICT && mode != TL_MODE_FAST) return fail(TL_EINVAL, "unknown mode");
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (const int rc = use_device(device)) return rc;
     const int herr = mode == TL_MODE_FAST ? tl_fast::api_selftest_arith(a, b, n, quot, root, (hipStream_t)stream)
                                           : tl_strict::api_selftest_arith(a, b, n, quot, root, (hipStream_t)stream);
     if (herr) return hip_fail(herr, "selftest_arith_kernel launch");

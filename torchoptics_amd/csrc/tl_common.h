@@ -41,17 +41,25 @@ struct tl_fallback {
     const uint8_t *dead_ok;
 };
 
+// One array of block partials in the workspace and the plan of the launch that fills it: nbx blocks per grid row, each
+// thread tracing up to R rays.  What tl_walkback carries down to a walk-back launch: its own partials, those of the
+// checkpoint launch queued behind it, and the poison word / token that tell the two apart (see tl_fallback).
+struct tl_part { double *part; int nbx, R; };
+struct tl_walkback {
+    tl_part inv, ck;
+    unsigned *poison;
+    unsigned token;
+};
+
 // per-mode launchers (defined once, at the end of tl_kernels.inc, for the mode of the including unit); return hipError_t
-// as int.  The blocks are the C entry's, forwarded as they are; `part*`, the plans (nbx, R), poison and token are what the
-// entry point computed.
+// as int.  The blocks are the C entry's, forwarded as they are; tl_part / tl_walkback are filled from the entry point's
+// workspace layout (tl_api.hip: Layout).
 #define TL_DECLARE_MODE(NS)                                                                                        \
     namespace NS {                                                                                                 \
-    int api_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, int R, hipStream_t st);            \
-    int api_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, int R,         \
-                hipStream_t st);                                                                                   \
+    int api_fwd(const tl_problem &p, const tl_rays &out, const tl_part &w, hipStream_t st);                        \
+    int api_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, const tl_part &w, hipStream_t st);    \
     int api_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &fwd, const tl_grads &out,               \
-                    double *part_inv, double *part_ck, unsigned *poison, unsigned token, int nbx, int R,           \
-                    int nbx_ck, int R_ck, hipStream_t st);                                                         \
+                    const tl_walkback &w, hipStream_t st);                                                         \
     int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st);   \
     }
 TL_DECLARE_MODE(tl_strict)
@@ -62,4 +70,13 @@ namespace tl_f64 {
 int launch_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, hipStream_t st);
 int launch_reduce_moments(const tl_problem &p, const double *part, double *mom, int nbx, hipStream_t st);
 int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, hipStream_t st);
+}
+
+// The calling thread's error message (tl_last_error) and the frame around every launch of a C entry point; defined in
+// tl_api.hip, used by every translation unit that holds entry points.
+namespace tl_host {
+int fail(int code, const char *msg);            // sets the message, returns code
+int hip_fail(int herr, const char *where);      // "<where>: <HIP's error string>", returns TL_ELAUNCH
+int use_device(int device);                     // hipSetDevice: TL_OK, or hip_fail(.., "hipSetDevice")
+int launched(const char *what);                 // hipGetLastError() behind a launch: TL_OK, or hip_fail(.., what)
 }

@@ -464,13 +464,12 @@ __global__ __launch_bounds__(kBlock) void bwd_kernel(const tl_problem p, const d
 }
 
 // sum part[col][rows of lens, fields f0.., wavelengths w0..] -> one double (fixed order)
-__global__ __launch_bounds__(kBlock) void reduce_kernel(const double *__restrict__ part, int n_rows_all, int ncol_unused, int F, int W,
+__global__ __launch_bounds__(kBlock) void reduce_kernel(const double *__restrict__ part, int F, int W,
                                                         int S, int nbx, int asph, double *__restrict__ g_c, double *__restrict__ g_t,
                                                         double *__restrict__ g_mu, double *__restrict__ g_z, double *__restrict__ g_cx,
                                                         double *__restrict__ g_cy, double *__restrict__ g_kappa,
                                                         double *__restrict__ g_poly)
 {
-    (void)ncol_unused;
     __shared__ double sm[kWaves];
     const int lens = blockIdx.y;
     int b = blockIdx.x, col, f0 = 0, nf = F, w0 = 0, nw = W;
@@ -482,7 +481,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(const double *__restrict
     else if ((b -= 1) < F) { col = 3 * S + 1; f0 = b; nf = 1; out = g_cx + lens * F + b; }
     else if ((b -= F) < F) { col = 3 * S + 2; f0 = b; nf = 1; out = g_cy + lens * F + b; }
     else { b -= F; if (!asph) return; if (b < S) { col = 3 * S + 3 + b; out = g_kappa + lens * S + b; } else { col = 4 * S + 3 + (b - S); out = g_poly + lens * S * 4 + (b - S); } }
-    const double *colp = part + (size_t)col * n_rows_all;
+    const double *colp = part + (size_t)col * ((size_t)gridDim.y * F * W * nbx);      // [column][rows of every lens]
     double acc = 0.0;
     for (int f = lens * F + f0; f < lens * F + f0 + nf; ++f) {
         const double *run = colp + ((size_t)f * W + w0) * nbx;
@@ -533,7 +532,7 @@ int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, doub
     if (herr) return herr;
     const int asph = p.surf_kind != nullptr;
     const int nout = 2 * p.S + p.W * p.S + 1 + 2 * p.F + (asph ? 5 * p.S : 0);
-    hipLaunchKernelGGL(reduce_kernel, dim3(nout, B), dim3(kBlock), 0, st, (const double *)part, B * p.F * p.W * nbx, 0, p.F, p.W, p.S, nbx,
+    hipLaunchKernelGGL(reduce_kernel, dim3(nout, B), dim3(kBlock), 0, st, (const double *)part, p.F, p.W, p.S, nbx,
                        asph, (double *)out.g_c, (double *)out.g_t, (double *)out.g_mu, (double *)out.g_z, (double *)out.g_cx,
                        (double *)out.g_cy, (double *)out.g_kappa, (double *)out.g_poly);
     return (int)hipGetLastError();

@@ -2382,11 +2382,11 @@ static int launch_selftest_arith(const float *a, const float *b, int64_t n, floa
 // ------------------------------------------------------------------ host launchers
 // (the C entry's blocks -- tl_rays, tl_seeds, tl_grads -- come down as they are: a kernel's pointer list is written out
 // once, at its hipLaunchKernelGGL)
-static int launch_fwd(const tl_problem &p, const tl_rays &o, double *part, int nbx, int R, hipStream_t st)
+static int launch_fwd(const tl_problem &p, const tl_rays &o, const tl_part &w, hipStream_t st)
 {
-    dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
+    dim3 grid(w.nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
 #define TL_FWD(PEN_, ASPH_, OPD_) \
-    hipLaunchKernelGGL((trace_fwd_kernel<PEN_, ASPH_, OPD_>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, o.opd, o.stacks, part, R)
+    hipLaunchKernelGGL((trace_fwd_kernel<PEN_, ASPH_, OPD_>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, o.opd, o.stacks, w.part, w.R)
     const bool asph = p.surf_kind != nullptr, wopd = p.n_index != nullptr && o.opd != nullptr;
     if (p.aggregate && asph) TL_FWD(true, true, false);
     else if (p.aggregate) TL_FWD(true, false, false);
@@ -2395,7 +2395,7 @@ static int launch_fwd(const tl_problem &p, const tl_rays &o, double *part, int n
     else if (wopd) TL_FWD(false, false, true);
 #if TL_FAST
     // two rays per lane: -10 % in fast mode (latency-bound chains), +4 % in strict mode (issue-bound, fewer waves)
-    else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, part, R);
+    else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part, w.R);
 #else
     else TL_FWD(false, false, false);
 #endif
@@ -2404,15 +2404,15 @@ static int launch_fwd(const tl_problem &p, const tl_rays &o, double *part, int n
 }
 
 template <int NS>
-static int launch_bwd_ns(const tl_problem &p, const tl_seeds &g, const tl_grads &o, double *part, int nbx, int R,
-                         hipStream_t st, const tl_fallback &fb)
+static int launch_bwd_ns(const tl_problem &p, const tl_seeds &g, const tl_grads &o, const tl_part &w, hipStream_t st,
+                         const tl_fallback &fb)
 {
-    dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
+    dim3 grid(w.nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
     // (gstk: the per-ray stack seeds, kPenRay; the caller has checked p.aggregate)
     const float *gstk = g.g_stacks;
 #define TL_BWD(ASPH_, PEN_) \
     hipLaunchKernelGGL((trace_bwd_kernel<NS, ASPH_, PEN_>), grid, block, 0, st, p, g.gx, g.gy, g.gcx, g.gcy, g.g_moments, \
-                       o.g_x_in, o.g_y_in, part, R, fb.mom, fb.poison, fb.token, g.g_opd, fb.dead_ok, gstk)
+                       o.g_x_in, o.g_y_in, w.part, w.R, fb.mom, fb.poison, fb.token, g.g_opd, fb.dead_ok, gstk)
     if (p.surf_kind && p.aggregate && gstk) TL_BWD(true, kPenRay);
     else if (p.surf_kind && p.aggregate) TL_BWD(true, kPenUniform);
     else if (p.surf_kind) TL_BWD(true, kPenNone);
@@ -2424,31 +2424,30 @@ static int launch_bwd_ns(const tl_problem &p, const tl_seeds &g, const tl_grads 
 }
 
 // the checkpoint kernel of the row bucket tl_bwd_bucket(p.S) (its partial rows: tl_bwd_row doubles); fb: see tl_fallback
-static int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &o, double *part, int nbx, int R,
-                      hipStream_t st, const tl_fallback &fb = {})
+static int launch_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &o, const tl_part &w, hipStream_t st,
+                      const tl_fallback &fb = {})
 {
     const int ns = tl_bwd_bucket(p.S);
     switch (ns) {
-    case 4:  return launch_bwd_ns<4>(p, g, o, part, nbx, R, st, fb);
-    case 8:  return launch_bwd_ns<8>(p, g, o, part, nbx, R, st, fb);
-    case 12: return launch_bwd_ns<12>(p, g, o, part, nbx, R, st, fb);
-    case 16: return launch_bwd_ns<16>(p, g, o, part, nbx, R, st, fb);
-    case 20: return launch_bwd_ns<20>(p, g, o, part, nbx, R, st, fb);
-    case 24: return launch_bwd_ns<24>(p, g, o, part, nbx, R, st, fb);
-    case 32: return launch_bwd_ns<32>(p, g, o, part, nbx, R, st, fb);
+    case 4:  return launch_bwd_ns<4>(p, g, o, w, st, fb);
+    case 8:  return launch_bwd_ns<8>(p, g, o, w, st, fb);
+    case 12: return launch_bwd_ns<12>(p, g, o, w, st, fb);
+    case 16: return launch_bwd_ns<16>(p, g, o, w, st, fb);
+    case 20: return launch_bwd_ns<20>(p, g, o, w, st, fb);
+    case 24: return launch_bwd_ns<24>(p, g, o, w, st, fb);
+    case 32: return launch_bwd_ns<32>(p, g, o, w, st, fb);
     default: return -1;
     }
 }
 
-// part_inv / part_ck: partial rows of the walk-back kernel (3S+3 columns) and of its checkpoint fallback
+// w.inv / w.ck: partial rows of the walk-back kernel (3S+3 columns) and of its checkpoint fallback
 // (3NS+3 columns); exactly one of the two launches does the work, decided on the device (fallback_needed) -- except
 // with the penalty term, where the checkpoint kernel also takes the rays that died on the way (see trace_bwd_kernel).
 // (f.ok: the forward's ok bytes, or p.cond_flags in their place when the forward wrote those)
-static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &f, const tl_grads &o, double *part_inv,
-                          double *part_ck, unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck,
+static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &f, const tl_grads &o, const tl_walkback &w,
                           hipStream_t st)
 {
-    dim3 grid(nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
+    dim3 grid(w.inv.nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
     // TL_INV_LDS_PAD (bytes, development only): extra dynamic LDS per block = fewer resident blocks per CU, to measure how
     // the kernel's throughput depends on its occupancy without touching its code.  TL_INV_ROLLED=1 (development only):
     // the rolled kernel for every lens, for A/B timing against the unrolled one.
@@ -2460,7 +2459,7 @@ static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays 
     const size_t lds_asph = hits ? (size_t)2 * p.asph_hit_slots * kBlock * sizeof(float) : 0;
     const float *gstk = g.g_stacks;
 #define TL_INV_ARGS p, g.gx, g.gy, g.gcx, g.gcy, g.g_moments, f.x, f.y, f.cx, f.cy, f.ok, f.moments, o.g_x_in, o.g_y_in, \
-                    part_inv, R, poison, token
+                    w.inv.part, w.inv.R, w.poison, w.token
 #define TL_INVU_V(NS_, ASPH_, PEN_) \
     hipLaunchKernelGGL((trace_bwd_inv_unrolled_kernel<NS_, ASPH_, PEN_>), grid, block, \
                        (NS_ < kInvUnrollPairMin ? 2 : 1) * lds + lds_asph + lds_pad, st, TL_INV_ARGS, gstk)
@@ -2490,20 +2489,18 @@ static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays 
 #undef TL_INV_ARGS
     const int herr = (int)hipGetLastError();
     if (herr) return herr;
-    return launch_bwd(p, g, o, part_ck, nbx_ck, R_ck, st, {f.moments, poison, token, (pen || p.cond_flags) ? f.ok : nullptr});
+    return launch_bwd(p, g, o, w.ck, st, {f.moments, w.poison, w.token, (pen || p.cond_flags) ? f.ok : nullptr});
 }
 
 }  // namespace TL_NS
 
 // the per-mode entry points tl_common.h declares (TL_DECLARE_MODE), for the mode this translation unit is built in
 namespace TL_API_NS {
-int api_fwd(const tl_problem &p, const tl_rays &out, double *part, int nbx, int R, hipStream_t st)
-{ return TL_NS::launch_fwd(p, out, part, nbx, R, st); }
-int api_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, double *part, int nbx, int R, hipStream_t st)
-{ return TL_NS::launch_bwd(p, g, out, part, nbx, R, st); }
-int api_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &fwd, const tl_grads &out, double *part_inv,
-                double *part_ck, unsigned *poison, unsigned token, int nbx, int R, int nbx_ck, int R_ck, hipStream_t st)
-{ return TL_NS::launch_bwd_inv(p, g, fwd, out, part_inv, part_ck, poison, token, nbx, R, nbx_ck, R_ck, st); }
+int api_fwd(const tl_problem &p, const tl_rays &out, const tl_part &w, hipStream_t st) { return TL_NS::launch_fwd(p, out, w, st); }
+int api_bwd(const tl_problem &p, const tl_seeds &g, const tl_grads &out, const tl_part &w, hipStream_t st)
+{ return TL_NS::launch_bwd(p, g, out, w, st); }
+int api_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays &fwd, const tl_grads &out, const tl_walkback &w, hipStream_t st)
+{ return TL_NS::launch_bwd_inv(p, g, fwd, out, w, st); }
 int api_selftest_arith(const float *a, const float *b, int64_t n, float *quot, float *root, hipStream_t st)
 { return TL_NS::launch_selftest_arith(a, b, n, quot, root, st); }
 }

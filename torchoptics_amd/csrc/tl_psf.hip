@@ -17,11 +17,6 @@
 
 #include <stdio.h>
 
-namespace tl_host {                 // tl_api.hip: the calling thread's error message
-int fail(int code, const char *msg);
-int hip_fail(int herr, const char *where);
-}
-
 namespace {
 
 constexpr int kBlock = 256;

@@ -30,11 +30,6 @@
 
 #include <algorithm>
 
-namespace tl_host {                 // tl_api.hip: the calling thread's error message
-int fail(int code, const char *msg);
-int hip_fail(int herr, const char *where);
-}
-
 namespace {
 
 constexpr int kBlock = 256;
