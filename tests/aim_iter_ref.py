@@ -14,7 +14,18 @@ Per (lens, field, wavelength):
           d ys/d yp after); dead rays and non-finite steps take no step; s_k = s_{k-1} + d
   map     x_scale = (p0.x + s.x) / p0.x, y_scale = ((p0.u + s.u) - (p0.l + s.l)) / (p0.u - p0.l),
           y_offset = (p0.l s.u - p0.u s.l) / (p0.l - p0.u)
+
+aim(..., jacobian="central") restates the kernel's own Jacobian instead: the three points p, p + h, p - h, a step only when
+all three rays live, the sum d(xs + ys) at step 1 and the coordinate's own partial after that.  Aspheric rows (kappa, poly,
+kind) and allow_backward go through to the oracle; raw_inputs() takes plain arrays for fronts no Lens describes.
+
+aim_kernel_order() is a third evaluation, in fp64 scalars and in the ORDER OF OPERATIONS of aim_trace in csrc/tl_api.hip
+(vector-form refraction, d = e + tmp / (cz + cos_i), mu formed in fp32 from the indices, Newton with the early exit): what
+the kernel would give without its final rounding.  tests/aim_cases.py uses it to show its allowance sufficient, and its
+`wrong` switches to show the bound sharp.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -23,8 +34,37 @@ from oracle.trace_oracle import trace_skew_general
 D_LINE = 587.6
 
 
+def _f32(v):
+    """An array's values rounded to fp32, as an fp64 tensor."""
+    return torch.as_tensor(np.asarray(v, dtype=np.float64)).float().double()
+
+
+def raw_inputs(c, t, n, n_d, mask, z, hfov, fields, epd, kappa=None, poly=None, kind=None, allow_backward=True):
+    """The kernel's inputs from plain arrays, no Lens needed: c, t, mask [B,K], n [B,K,W], n_d [B,K], z, hfov, epd [B],
+    fields [F], kappa [B,K], poly [B,K,4], kind [B,K] (all three or none).  Everything is rounded to fp32 first, the angle
+    hfov * fields and the index ratios mu are formed in fp32 and the sine is the correctly rounded fp32 one."""
+    c, t, n, n_d, z, hfov, fields, epd = (_f32(v) for v in (c, t, n, n_d, z, hfov, fields, epd))
+    B, K, W = n.shape
+    n_d = n_d.reshape(B, K, 1)
+
+    def mu_of(nk):                                                          # fp32 ratio n_{k-1} / n_k, as the trace forms it
+        nk = nk.float()
+        prev = torch.cat((torch.ones_like(nk[:, :1]), nk[:, :-1]), dim=1)
+        return (prev / nk).double().transpose(1, 2)                         # [B,W,K]
+    ang = hfov.float()[:, None] * fields.float()[None, :]                   # fp32 angle
+    cy = torch.sin(ang.double()).float().double()                           # the correctly rounded fp32 sine
+    inp = dict(c=c, t=t, mu=mu_of(n), mu_d=mu_of(n_d), mask=torch.as_tensor(np.asarray(mask)).bool().reshape(B, K), z=z,
+               cy=cy, half=0.5 * epd, allow_backward=bool(allow_backward), n=n, n_d=n_d.reshape(B, K),
+               kappa=None, poly=None, kind=None)
+    if kind is not None:
+        inp.update(kappa=_f32(kappa).reshape(B, K), poly=_f32(poly).reshape(B, K, 4),
+                   kind=torch.as_tensor(np.asarray(kind)).bool().reshape(B, K))
+    return inp
+
+
 def inputs(lens, specs, rel_fields, wavelengths, allow_backward=True, z=None):
-    """The kernel's inputs of a CPU fp32 Lens / Specs pair, as fp64 tensors [B, ...]."""
+    """The kernel's inputs of a CPU fp32 Lens / Specs pair, as fp64 tensors [B, ...].  An aspheric Lens brings its kappa
+    and poly rows; kind is what RayTracer derives from them (any non-zero term)."""
     from torchoptics_amd.paraxial import compute_pupil_position
     with torch.no_grad():
         front = lens.detach().up_to_stop()
@@ -32,27 +72,35 @@ def inputs(lens, specs, rel_fields, wavelengths, allow_backward=True, z=None):
             z = compute_pupil_position(lens.detach(), front=front)
         n = front.get_refractive_indices(list(wavelengths)).float()           # [B,K,W]
         n_d = front.get_refractive_indices([D_LINE]).float()                   # [B,K,1]
-
-        def mu_of(nk):                                                          # fp32 ratio n_{k-1} / n_k, as the trace forms it
-            prev = torch.cat((torch.ones_like(nk[:, :1]), nk[:, :-1]), dim=1)
-            return (prev / nk).double().transpose(1, 2)                         # [B,W,K]
-        fields = torch.tensor(list(rel_fields), dtype=torch.float32)
-        ang = specs.hfov.detach().float()[:, None] * fields[None, :]           # fp32 angle
-        cy = torch.sin(ang.double()).float().double()                           # the correctly rounded fp32 sine
-        return dict(c=front.c.detach().double(), t=front.t.detach().double(), mu=mu_of(n), mu_d=mu_of(n_d),
-                    mask=front.structure.mask_torch.clone(), z=z.detach().float().double(), cy=cy,
-                    half=0.5 * specs.epd.detach().float().double(), allow_backward=allow_backward)
+        kap = pol = kind = None
+        if getattr(front, "kappa", None) is not None:
+            kap, pol = front.kappa.detach().float(), front.poly.detach().float()
+            kind = (kap != 0) | (pol != 0).any(dim=-1)
+        return raw_inputs(front.c.detach().float(), front.t.detach().float(), n, n_d, front.structure.mask_torch.clone(),
+                          z.detach().float(), specs.hfov.detach().float(), list(rel_fields), specs.epd.detach().float(),
+                          kap, pol, kind, allow_backward)
 
 
 def _trace(inp, x, y, cy, mu):
-    """Trace relative pupil points x, y [B,F,R,W] to the stop; returns stop x, y (fp64, differentiable) and ok."""
+    """Trace relative pupil points x, y [B,F,R,W] to the stop; returns stop x, y (fp64, differentiable) and ok.  With
+    aspheric rows the lenses go through the oracle one at a time: its kind is one list for all lenses."""
     B = inp["c"].shape[0]
     half = inp["half"].reshape(B, 1, 1, 1)
-    out = trace_skew_general(x * half, y * half, inp["z"].reshape(B, 1, 1, 1), torch.zeros((), dtype=torch.float64),
-                             cy, inp["c"].reshape(B, 1, 1, 1, -1), inp["t"].reshape(B, 1, 1, 1, -1),
-                             mu.reshape(B, 1, 1, mu.shape[1], -1), inp["mask"].reshape(B, 1, 1, 1, -1),
-                             allow_backward_rays=inp["allow_backward"])
-    return out[0], out[1], out[4]
+
+    def go(sl, kw):
+        nb = inp["c"][sl].shape[0]
+        xs, ys = (v if v.shape[0] == 1 and B > 1 else v[sl] for v in (x, y))
+        cys = cy if cy.dim() == 0 else cy[sl]
+        out = trace_skew_general(xs * half[sl], ys * half[sl], inp["z"][sl].reshape(nb, 1, 1, 1),
+                                 torch.zeros((), dtype=torch.float64), cys, inp["c"][sl].reshape(nb, 1, 1, 1, -1),
+                                 inp["t"][sl].reshape(nb, 1, 1, 1, -1), mu[sl].reshape(nb, 1, 1, mu.shape[1], -1),
+                                 inp["mask"][sl].reshape(nb, 1, 1, 1, -1), allow_backward_rays=inp["allow_backward"], **kw)
+        return out[0], out[1], out[4]
+    if inp.get("kind") is None:
+        return go(slice(None), {})
+    res = [go(slice(b, b + 1), dict(kappa=inp["kappa"][b], poly=inp["poly"][b], kind=[int(k) for k in inp["kind"][b]]))
+           for b in range(B)]
+    return tuple(torch.cat([r[i] for r in res], dim=0) for i in range(3))
 
 
 def marginal_rs(inp):
@@ -71,9 +119,7 @@ def tee_points(p0, s):
     return x, y
 
 
-def aim(inp, n_iter, tee_ref=None, rs=None, return_history=False):
-    """The aimed map (x_scale, y_scale, y_offset) [B,F,W] fp64 after n_iter steps; with return_history also the list of
-    accumulated steps s_k [B,F,3,W] and the per-step dead-ray masks."""
+def _p0_rs(inp, tee_ref, rs):
     B, W = inp["c"].shape[0], inp["mu"].shape[1]
     F = inp["cy"].shape[1]
     if tee_ref is None:
@@ -84,51 +130,241 @@ def aim(inp, n_iter, tee_ref=None, rs=None, return_history=False):
         rs, ok_m = marginal_rs(inp)
     else:
         rs, ok_m = torch.as_tensor(rs).float().double().reshape(B), torch.ones(B, dtype=torch.bool)
+    return p0, rs, ok_m
+
+
+def aim_detail(inp, n_iter, tee_ref=None, rs=None, jacobian="autograd", h=1e-4):
+    """aim() with everything it went through: dict(map, p0 [B,F,3,W], rs [B], ok_m [B], and per step the lists s
+    (accumulated step), d (the step taken), j (the Jacobian used), dead (no step taken for want of a live ray))."""
+    assert jacobian in ("autograd", "central")
+    B, W = inp["c"].shape[0], inp["mu"].shape[1]
+    F = inp["cy"].shape[1]
+    p0, rs, ok_m = _p0_rs(inp, tee_ref, rs)
     rs4 = rs.reshape(B, 1, 1, 1)
     cy = inp["cy"].reshape(B, F, 1, 1)
     s = torch.zeros(B, F, 3, W, dtype=torch.float64)
-    hist, dead = [], []
+    hist, steps, jacs, dead = [], [], [], []
     for k in range(n_iter):
         x, y = tee_points(p0, s)
-        x, y = x.detach().requires_grad_(True), y.detach().requires_grad_(True)
-        with torch.enable_grad():
-            xs, ys, ok = _trace(inp, x, y, cy, inp["mu"])
-            xs_rel, ys_rel = xs / rs4, ys / rs4
+        if jacobian == "autograd":
+            x, y = x.detach().requires_grad_(True), y.detach().requires_grad_(True)
+            with torch.enable_grad():
+                xs, ys, ok = _trace(inp, x, y, cy, inp["mu"])
+                xs_rel, ys_rel = xs / rs4, ys / rs4
+                if k == 0:
+                    jx, jy = torch.autograd.grad(xs_rel.sum() + ys_rel.sum(), (x, y))
+                else:
+                    jx, = torch.autograd.grad(xs_rel.sum(), (x,), retain_graph=True)
+                    jy, = torch.autograd.grad(ys_rel.sum(), (y,))
+            pos = torch.cat((ys_rel[:, :, :2], xs_rel[:, :, 2:]), dim=2).detach()
+            j = torch.cat((jy[:, :, :2], jx[:, :, 2:]), dim=2)
+        else:
+            # the kernel's: the three points p, p + h, p - h along the coordinate that moves; a step only when all three live
+            ex = torch.tensor([0.0, 0.0, h], dtype=torch.float64).reshape(1, 1, 3, 1)
+            ey = torch.tensor([h, h, 0.0], dtype=torch.float64).reshape(1, 1, 3, 1)
+            with torch.no_grad():
+                x0, y0, ok0 = _trace(inp, x, y, cy, inp["mu"])
+                xa, ya, oka = _trace(inp, x + ex, y + ey, cy, inp["mu"])
+                xb, yb, okb = _trace(inp, x - ex, y - ey, cy, inp["mu"])
+            ok = ok0 & oka & okb
             if k == 0:
-                jx, jy = torch.autograd.grad(xs_rel.sum() + ys_rel.sum(), (x, y))
+                num = (xa + ya) - (xb + yb)                                  # d(xs + ys), the reference's Jacobian
             else:
-                jx, = torch.autograd.grad(xs_rel.sum(), (x,), retain_graph=True)
-                jy, = torch.autograd.grad(ys_rel.sum(), (y,))
-        pos = torch.cat((ys_rel[:, :, :2], xs_rel[:, :, 2:]), dim=2).detach()
-        j = torch.cat((jy[:, :, :2], jx[:, :, 2:]), dim=2)
+                num = torch.cat(((ya - yb)[:, :, :2], (xa - xb)[:, :, 2:]), dim=2)
+            j = num / (2.0 * h * rs4)
+            pos = torch.cat((y0[:, :, :2], x0[:, :, 2:]), dim=2) / rs4
         d = -(pos - p0) / j
         live = ok & ok_m.reshape(B, 1, 1, 1)
         d = torch.where(live & torch.isfinite(d), d, torch.zeros_like(d))
         s = s + d
         hist.append(s.clone())
+        steps.append(d.clone())
+        jacs.append(j.detach().clone())
         dead.append(~live)
     x_scale = (p0[:, :, 2] + s[:, :, 2]) / p0[:, :, 2]
     y_scale = ((p0[:, :, 1] + s[:, :, 1]) - (p0[:, :, 0] + s[:, :, 0])) / (p0[:, :, 1] - p0[:, :, 0])
     y_offset = (p0[:, :, 0] * s[:, :, 1] - p0[:, :, 1] * s[:, :, 0]) / (p0[:, :, 0] - p0[:, :, 1])
+    return dict(map=(x_scale, y_scale, y_offset), p0=p0, rs=rs, ok_m=ok_m, s=hist, d=steps, j=jacs, dead=dead)
+
+
+def aim(inp, n_iter, tee_ref=None, rs=None, return_history=False, jacobian="autograd", h=1e-4):
+    """The aimed map (x_scale, y_scale, y_offset) [B,F,W] fp64 after n_iter steps; with return_history also the list of
+    accumulated steps s_k [B,F,3,W] and the per-step dead-ray masks.  jacobian: 'autograd' (the reference's mechanism) or
+    'central' (the kernel's central differences at h)."""
+    r = aim_detail(inp, n_iter, tee_ref, rs, jacobian, h)
     if return_history:
-        return (x_scale, y_scale, y_offset), hist, dead
-    return x_scale, y_scale, y_offset
+        return r["map"], r["s"], r["dead"]
+    return r["map"]
 
 
-def residual(inp, n_iter, tee_ref=None, rs=None):
+def residual(inp, n_iter, tee_ref=None, rs=None, jacobian="autograd", h=1e-4):
     """Error stop / rs - p0 of the three tee rays [B,F,3,W] (bottom y, top y, sagittal x) after n_iter steps, at the
     points the returned map sends the reference points to."""
     B, W = inp["c"].shape[0], inp["mu"].shape[1]
     F = inp["cy"].shape[1]
-    _, hist, _ = aim(inp, n_iter, tee_ref, rs, return_history=True)
-    p0 = (torch.tensor([-1.0, 1.0, 1.0], dtype=torch.float64).reshape(1, 1, 3, 1) if tee_ref is None
-          else torch.as_tensor(tee_ref).float().double().reshape(B, F, 3, 1)).expand(B, F, 3, W)
+    r = aim_detail(inp, n_iter, tee_ref, rs, jacobian, h)
+    hist, p0 = r["s"], r["p0"]
     rs_ = marginal_rs(inp)[0] if rs is None else torch.as_tensor(rs).float().double().reshape(B)
     x, y = tee_points(p0, hist[-1] if hist else torch.zeros(B, F, 3, W, dtype=torch.float64))
     with torch.no_grad():
         xs, ys, ok = _trace(inp, x, y, inp["cy"].reshape(B, F, 1, 1), inp["mu"])
     rel = torch.cat((ys[:, :, :2], xs[:, :, 2:]), dim=2) / rs_.reshape(B, 1, 1, 1)
     return torch.where(ok, rel - p0, torch.full_like(rel, float("nan")))
+
+
+WRONG = ("sum-jacobian", "sagittal-y0", "mu-fp64", "rs-f-line", "dead-steps", "no-a10", "next-wavelength", "next-lens-poly",
+         "next-lens-rs", "ignore-allow-backward")
+
+
+def _kernel_trace(L, w, x, y, z, cx, cy, wrong):
+    """aim_trace of csrc/tl_api.hip, operation for operation, in Python floats (fp64).  L: one lens' rows as lists; w < 0 is
+    the d line.  Returns (ok, xo, yo)."""
+    eps = 1e-6
+    force = wrong == "dead-steps"                                          # (wrong on purpose: nothing kills a ray)
+    allow_back = L["allow_back"] or wrong == "ignore-allow-backward"
+    cz = math.sqrt((1.0 - cx * cx) - cy * cy)
+    n_prev = 1.0
+    K = L["K"]
+    for k in range(K):
+        c, t = L["c"][k], L["t"][k]
+        n_k = L["n_d"][k] if w < 0 else L["n"][k][w]
+        mu = n_prev / n_k if wrong == "mu-fp64" else float(np.float32(n_prev) / np.float32(n_k))
+        n_prev = n_k
+        if not (L["kind"] is not None and L["kind"][k]):
+            e = -((x * cx + y * cy) + z * cz)
+            mz = z + e * cz
+            m2 = ((x * x + y * y) + z * z) - e * e
+            tmp = c * m2 - 2.0 * mz
+            cos2 = cz * cz - c * tmp
+            if cos2 - eps < 0.0:
+                if not force:
+                    return False, 0.0, 0.0
+                cos2 = abs(cos2) + eps
+            cos_i = math.sqrt(cos2)
+            d = e + tmp / (cz + cos_i)
+            dz = d * cz
+            X, Y, Z = x + d * cx, y + d * cy, z + dz
+            nx, ny, nz = -c * X, -c * Y, 1.0 - c * Z
+        else:
+            kap = L["kappa"][k]
+            a0, a1, a2, a3 = L["poly"][k]
+            if wrong == "no-a10":
+                a3 = 0.0
+            Kc = 1.0 + kap
+            e = -((x * cx + y * cy) + Kc * (z * cz))
+            dd = (cx * cx + cy * cy) + Kc * (cz * cz)
+            rr = (x * x + y * y) + Kc * (z * z)
+            bq, cq = c * e + cz, c * rr - 2.0 * z
+            disc = bq * bq - (c * dd) * cq
+            if disc - eps < 0.0:
+                if not force:
+                    return False, 0.0, 0.0
+                disc = abs(disc) + eps
+            s = cq / (bq + math.sqrt(disc))
+            dsag = rho = F = 0.0
+            bad = False
+            for _ in range(12):
+                X, Y, Z = x + s * cx, y + s * cy, z + s * cz
+                rho = X * X + Y * Y
+                q2 = 1.0 - Kc * c * c * rho
+                bad = q2 - eps < 0.0
+                q = math.sqrt(1.0 if bad else q2)
+                sag = c * rho / (1.0 + q) + rho * rho * (a0 + rho * (a1 + rho * (a2 + rho * a3)))
+                dsag = c / (2.0 * q) + rho * (2.0 * a0 + rho * (3.0 * a1 + rho * (4.0 * a2 + rho * (5.0 * a3))))
+                F = Z - sag
+                if abs(F) <= 1e-13 * (1.0 + abs(Z)):
+                    break
+                s -= F / (cz - dsag * (2.0 * (X * cx + Y * cy)))
+            if (bad or not (abs(F) <= 1e-9 * (1.0 + abs(Z)))) and not force:
+                return False, 0.0, 0.0
+            dz = s * cz
+            m = 2.0 * dsag
+            inv_n = 1.0 / math.sqrt(1.0 + m * m * rho)
+            nx, ny, nz = -(m * X) * inv_n, -(m * Y) * inv_n, inv_n
+            cos_i = (cx * nx + cy * ny) + cz * nz
+        cos2_t = 1.0 - (mu * mu) * (1.0 - cos_i * cos_i)
+        if cos2_t - eps < 0.0:
+            if not force:
+                return False, 0.0, 0.0
+            cos2_t = abs(cos2_t) + eps
+        g = math.sqrt(cos2_t) - mu * cos_i
+        cx3, cy3 = mu * cx + g * nx, mu * cy + g * ny
+        czsq = 1.0 - (cx3 * cx3 + cy3 * cy3)
+        if k > 0 and L["mask"][k - 1] and dz < 0.0 and not allow_back and not force:
+            return False, 0.0, 0.0
+        if czsq - eps < 0.0:
+            if not force:
+                return False, 0.0, 0.0
+            czsq = abs(czsq) + eps
+        x, y, z = X, Y, Z - t
+        cx, cy, cz = cx3, cy3, math.sqrt(czsq)
+    dzi = -z
+    dist = dzi / cz
+    if L["mask"][K - 1] and dzi < 0.0 and not allow_back and not force:
+        return False, 0.0, 0.0
+    return True, x + dist * cx, y + dist * cy
+
+
+def aim_kernel_order(inp, n_iter, tee_ref=None, rs=None, h=1e-4, wrong=None):
+    """ray_aim_iter_kernel restated in fp64 scalars in its own order of operations: the map [3,B,F,W] (numpy fp64) before
+    the kernel's rounding to fp32.  inp from raw_inputs() / inputs().  wrong: None, or one of WRONG -- a deliberately wrong
+    evaluation, for the sharpness test of the bound."""
+    assert wrong is None or wrong in WRONG
+    B, K, W = inp["n"].shape
+    F = inp["cy"].shape[1]
+    tee = None if tee_ref is None else torch.as_tensor(tee_ref).float().double().reshape(B, F, 3).tolist()
+    rs_in = None if rs is None else torch.as_tensor(rs).float().double().reshape(B).tolist()
+    out = np.zeros((3, B, F, W))
+    lenses = []
+    for b in range(B):
+        asph = inp.get("kind") is not None
+        lenses.append(dict(K=K, c=inp["c"][b].tolist(), t=inp["t"][b].tolist(), n=inp["n"][b].tolist(), n_d=inp["n_d"][b].tolist(),
+                           mask=inp["mask"][b].tolist(), kind=inp["kind"][b].tolist() if asph else None,
+                           kappa=inp["kappa"][b].tolist() if asph else None, poly=inp["poly"][b].tolist() if asph else None,
+                           allow_back=inp["allow_backward"]))
+    for b in range(B):
+        L = lenses[b]
+        if wrong == "next-lens-poly" and L["kind"] is not None:
+            L = dict(L, poly=lenses[(b + 1) % B]["poly"])
+        z0, half = float(inp["z"][b]), float(inp["half"][b])
+        for f in range(F):
+            cyf = float(inp["cy"][b, f])
+            for w in range(W):
+                wt = (w + 1) % W if wrong == "next-wavelength" else w
+                if rs_in is not None:
+                    ok_m, r_s = True, rs_in[(b + 1) % B if wrong == "next-lens-rs" else b]
+                elif wrong == "rs-f-line":
+                    ok_m, _, r_s = _kernel_trace(L, W - 1, 0.0, half, z0, 0.0, 0.0, wrong)
+                else:
+                    ok_m, _, r_s = _kernel_trace(L, -1, 0.0, half, z0, 0.0, 0.0, wrong)
+                p0 = [-1.0, 1.0, 1.0] if tee is None else tee[b][f]
+                y_sag = 0.0 if wrong == "sagittal-y0" else 0.5 * (p0[0] + p0[1])
+                s = [0.0, 0.0, 0.0]
+                for k in range(n_iter):
+                    if not ok_m:
+                        break
+                    step = [0.0, 0.0, 0.0]
+                    for q in range(3):
+                        px, py = (p0[2] + s[2], y_sag) if q == 2 else (0.0, p0[q] + s[q])
+                        res = []
+                        for off in (0.0, h, -h):
+                            ex, ey = (off, 0.0) if q == 2 else (0.0, off)
+                            res.append(_kernel_trace(L, wt, (px + ex) * half, (py + ey) * half, z0, 0.0, cyf, wrong))
+                        (ok0, x0, y0), (oka, xa, ya), (okb, xb, yb) = res
+                        if not (ok0 and oka and okb):
+                            continue
+                        if k == 0 or wrong == "sum-jacobian":
+                            j = ((xa + ya) - (xb + yb)) / (2.0 * h * r_s)
+                        else:
+                            j = ((xa - xb) if q == 2 else (ya - yb)) / (2.0 * h * r_s)
+                        pos = (x0 if q == 2 else y0) / r_s
+                        d = -(pos - p0[q]) / j if j != 0.0 else float("nan")
+                        step[q] = d if math.isfinite(d) else 0.0
+                    s = [step[q] if k == 0 else s[q] + step[q] for q in range(3)]
+                out[0, b, f, w] = (p0[2] + s[2]) / p0[2]
+                out[1, b, f, w] = ((p0[1] + s[1]) - (p0[0] + s[0])) / (p0[1] - p0[0])
+                out[2, b, f, w] = (p0[0] * s[1] - p0[1] * s[0]) / (p0[0] - p0[1])
+    return out
 
 
 def aimed_fan(aim_map, xp, yp, epd):

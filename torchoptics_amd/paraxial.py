@@ -110,11 +110,13 @@ def compute_last_curvature(structures, c: torch.Tensor, t: torch.Tensor, nd: tor
     return c2d[mask]
 
 
-def compute_pupil_radius(specs, lens2stop, default_device="cuda") -> torch.Tensor:
-    """Height of the marginal ray (relative pupil y = 1, on axis, d line) at the stop."""
+def compute_pupil_radius(specs, lens2stop, default_device="cuda", return_ok=False, allow_backward_rays=True) -> torch.Tensor:
+    """Height of the marginal ray (relative pupil y = 1, on axis, d line) at the stop; with return_ok also whether the
+    ray arrived there alive (under the caller's allow_backward_rays)."""
     from .ray_tracing import RayTracer
     x = torch.zeros(1, 1, 1, 1, device=default_device)
     y = torch.ones(1, 1, 1, 1, device=default_device)
-    tracer = RayTracer(rel_fields=[0.], vig_fn=None, wavelengths=['d'], default_device=default_device)
-    _, yp, *_ = tracer.trace_rays(specs, lens2stop, xy=(x, y), use_vig=False)
-    return yp.reshape(yp.shape[0])
+    tracer = RayTracer(rel_fields=[0.], vig_fn=None, wavelengths=['d'], default_device=default_device,
+                       allow_backward_rays=allow_backward_rays)
+    _, yp, _, _, ok, _ = tracer.trace_rays(specs, lens2stop, xy=(x, y), use_vig=False)
+    return (yp.reshape(yp.shape[0]), ok.reshape(ok.shape[0])) if return_ok else yp.reshape(yp.shape[0])

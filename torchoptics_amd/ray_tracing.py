@@ -786,10 +786,13 @@ class RayTracer:
                 return self._ray_aiming_kernel(specs2stop, lens2stop, z, tee_ref=tee_ref, rs=rs)
         if front is not None:
             lens2stop = lens2stop.detach()
+        ok_m = None
         if self.ray_aiming_mode == 'paraxial':
             rs = (compute_magnification(lens2stop) * specs2stop.epd / 2).reshape(-1, 1, 1, 1)
         else:
-            rs = compute_pupil_radius(specs2stop, lens2stop, default_device=self.default_device).reshape(-1, 1, 1, 1)
+            rs, ok_m = compute_pupil_radius(specs2stop, lens2stop, default_device=self.default_device, return_ok=True,
+                                            allow_backward_rays=self.allow_backward_rays)
+            rs, ok_m = rs.reshape(-1, 1, 1, 1), ok_m.reshape(-1, 1, 1, 1)
 
         xt0, yt0 = tee(None, self.default_device)
         shape = (len(lens), len(self.rel_fields), xt0.shape[2], len(self.wavelengths))
@@ -803,7 +806,7 @@ class RayTracer:
             with torch.enable_grad():
                 xt = (xt_ref + sx).detach().requires_grad_(True)
                 yt = (yt_ref + sy).detach().requires_grad_(True)
-                xs, ys, *_ = self.trace_rays(specs2stop, lens2stop, up_to_stop=True, use_vig=False, xy=(xt, yt))
+                xs, ys, _, _, ok, _ = self.trace_rays(specs2stop, lens2stop, up_to_stop=True, use_vig=False, xy=(xt, yt))
                 xs_rel, ys_rel = xs / rs, ys / rs
                 if k == 0:
                     # the reference back-propagates ones through xs_rel and then ys_rel into the same .grad
@@ -817,8 +820,13 @@ class RayTracer:
             xs_rel, ys_rel = xs_rel.detach(), ys_rel.detach()
             dx = -(xs_rel - xt_ref) / jx
             dy = -(ys_rel - yt_ref) / jy
-            dx = torch.where(torch.isfinite(dx), dx, torch.zeros_like(dx))
-            dy = torch.where(torch.isfinite(dy), dy, torch.zeros_like(dy))
+            # a dead ray takes no step.  One that missed or was totally reflected comes back zeroed, with a zero Jacobian
+            # and so a non-finite step; one flagged at the stop plane itself (allow_backward_rays=False, arriving from
+            # behind it) keeps its coordinates, and so does a marginal ray flagged there: those are dropped by their flag,
+            # as tl_ray_aim_iter drops them
+            live = ok if ok_m is None else ok & ok_m
+            dx = torch.where(torch.isfinite(dx) & live, dx, torch.zeros_like(dx))
+            dy = torch.where(torch.isfinite(dy) & live, dy, torch.zeros_like(dy))
             if n_iter == 1:
                 sx, sy = dx, dy                  # (the map below reads only the sagittal x and the meridional y steps)
             else:
