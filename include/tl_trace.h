@@ -458,7 +458,7 @@ int tl_svola_bwd_image(const tl_svola_geom *g, const int32_t *r0, const int32_t 
  *                 B > 1, gain_channels 1 with C > 1) receives the sum over what shares it, taken inside one lane in a fixed
  *                 order (b outer, c inner): no atomics, no workspace, the same bits on every run.
  * Only clipped integer indices form addresses, so no coordinate value can read outside the image; a NaN coordinate gives NaN
- * in that pixel's output and gradients and nowhere else.  The gradient to the image (a scatter) is not provided.
+ * in that pixel's output and gradients and nowhere else.  The gradient to the image is tl_warp_bwd_image below.
  * TL_EINVAL before any HIP call, with the function's name and the argument in the message: a required pointer NULL, a size
  * below 1 (or H, W, Ho, Wo above 2^20), coord_batch or gain_batch neither 1 nor B, gain_channels neither 1 nor C.  C is not a
  * grid dimension and has no upper limit; B is cut into launches of 65535 lenses.  No host synchronisation, no allocation;
@@ -484,6 +484,39 @@ int tl_warp_fwd(const tl_warp_geom *g, const float *image, const float *x, const
                 void *stream);
 int tl_warp_bwd(const tl_warp_geom *g, const float *image, const float *x, const float *y, const float *gain, const float *g_out,
                 float *g_x, float *g_y, float *g_gain, void *stream);
+
+/*
+ * The gradient of sum(g_out out) to the image of tl_warp_fwd: a scatter,
+ *     g_image[b,r,q,c] = sum over output pixels and taps (i,j) with (row_i, col_j) = (r,q) of wy_i wx_j a,
+ *     a = g_out[b,yo,xo,c] gain[..] (gain 1 when NULL), taken as the fp32 product,
+ * accumulated in 64-bit FIXED POINT with integer atomics, so the result has the same bits in any order or grouping of the
+ * output pixels, under any launch plan and in every run.  The image is not read (the gradient is linear in it); only B, H, W,
+ * C of it are used, image_stride and the g_*_stride members are not.  g_out and g_image are contiguous [B,Ho,Wo,C] and
+ * [B,H,W,C] floats.  The contract:
+ *   scale         m = the largest finite |a| of the whole call; E with 2^(E-1) <= m < 2^E; Hb = ceil(log2(16 Ho Wo)), in
+ *                 integers; the quantum is Q = 2^(E + Hb - 62).  Ho Wo <= 2^26, so Hb <= 30 and Q <= 2^(E-32).
+ *   contribution  the fp32 product (wy_i wx_j) a, times 1/Q in fp64 (exact), rounded to the nearest int64, added with an
+ *                 integer atomic.  |wy wx| <= 1 and at most 16 Ho Wo <= 2^Hb contributions reach one address, so
+ *                 |sum| <= 2^62: overflow is impossible by construction.
+ *   result        fp32(sum Q), rounded once.  A source pixel that no tap reaches is +0.0; m = 0, or no finite a, gives zeros.
+ *   non-finite    a non-finite a, or a NaN coordinate (whose taps are the clipped indices around j0 = 0, as in the forward),
+ *                 is left out of m and of the sums and marks its destination elements instead: a marked element is NaN,
+ *                 every other element keeps the bits of the clean run.
+ *   error         per contribution at most Q/2, plus the fp32 roundings of weights and products and the one of the result:
+ *                 ABSOLUTE on the scale of the largest seed (at least 2^-32 of m), not relative per pixel.
+ *   consequences  scaling g_out by a power of two scales the result exactly (barring fp32 under- or overflow of the
+ *                 products); the result does not depend on the launch plan or on `flags`.
+ * A pre-pass finds m on the device (integer atomicMax on the bit pattern), the scatter kernel privatises a box of the source
+ * image in LDS per tile of output pixels and flushes it with one atomic per touched entry, a last kernel converts.
+ * `flags` bit 0: direct global atomics only, no LDS box (the A/B switch; the same bits).  `work`: the accumulators, the marks
+ * and the m word, tl_warp_bwd_image_work_bytes(g) bytes (0 for a geometry that is refused), aligned to 8; it is cleared
+ * inside the call and holds nothing afterwards.  No host synchronisation, no allocation; the launches go on `stream`.
+ * TL_EINVAL before any HIP call as for tl_warp_bwd, and for Ho Wo > 2^26, B H W C > 2^40, unknown flag bits, and a
+ * workspace that is NULL, misaligned or too small.
+ */
+size_t tl_warp_bwd_image_work_bytes(const tl_warp_geom *g);
+int tl_warp_bwd_image(const tl_warp_geom *g, const float *x, const float *y, const float *gain, const float *g_out,
+                      float *g_image, void *work, size_t work_bytes, int flags, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

@@ -126,6 +126,9 @@ _SIGNATURES = {
     # geom | image, x, y, gain | out | stream          and          geom | image, x, y, gain | g_out | g_x, g_y, g_gain | stream
     "tl_warp_fwd": (C.c_int, [C.POINTER(tl_warp_geom)] + [_VP] * 4 + [_VP] + [_VP]),
     "tl_warp_bwd": (C.c_int, [C.POINTER(tl_warp_geom)] + [_VP] * 4 + [_VP] + [_VP] * 3 + [_VP]),
+    # geom | x, y, gain | g_out | g_image | work, work_bytes | flags (bit 0: direct atomics, no LDS box) | stream
+    "tl_warp_bwd_image_work_bytes": (C.c_size_t, [C.POINTER(tl_warp_geom)]),
+    "tl_warp_bwd_image": (C.c_int, [C.POINTER(tl_warp_geom)] + [_VP] * 3 + [_VP] + [_VP] + [_VP, C.c_size_t] + [C.c_int] + [_VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

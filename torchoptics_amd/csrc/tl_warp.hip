@@ -23,8 +23,11 @@
 // batch but not by the channels keeps its C running sums in g_gain itself (the lane that owns the pixel stores, then reads,
 // adds and stores its own element again: program order, one lane, no other writer).
 //
-// The gradient to the image is a scatter and is not a kernel here.
+// The gradient to the image is a scatter: tl_warp_bwd_image at the end of this file, with its own contract (64-bit fixed-point
+// integer atomics on a scale taken from the data, so the same bits in any order).
 #include "tl_common.h"
+
+#include <limits.h>
 
 #include <stdio.h>
 
@@ -180,6 +183,220 @@ __global__ __launch_bounds__(kBlock) void warp_bwd_kernel(const Geo g, const flo
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the gradient to the image
+//
+//   g_image[b,r,q,c] = sum over output pixels and taps (i,j) with (row_i, col_j) = (r,q) of wy_i wx_j a,   a = g_out gain
+//
+// A scatter: many output pixels add into one source pixel.  Float atomics would make the sum depend on the arrival order.
+// Integer addition is associative, so every contribution is converted to a 64-bit fixed-point integer on ONE scale for the
+// whole call and added with plain integer atomics: the same bits in any order, grouping, launch plan and run.
+//
+// THE SCALE.  m = the largest finite |a| of the call (a as the fp32 product g_out gain; pre-pass, integer atomicMax on the
+// bit pattern, which orders non-negative floats); E with 2^(E-1) <= m < 2^E; Hb = ceil(log2(16 Ho Wo)); the quantum is
+// Q = 2^(E + Hb - 62).  Ho Wo <= 2^26, so Hb <= 30 and Q <= 2^(E-32): the error is ABSOLUTE, on the scale of the largest
+// seed, at least 2^-32 of it; it is not relative per pixel.
+// ONE CONTRIBUTION.  The fp32 product (wy_i wx_j) a, times 1/Q in fp64 (a power of two: exact), rounded to the nearest int64.
+// NO OVERFLOW.  |wy wx| <= 1 and |a| < 2^E, so |contribution| <= 2^(62-Hb); at most 16 Ho Wo <= 2^Hb contributions reach one
+// address (16 taps of every output pixel of one lens), so |sum| <= 2^62.  (The fp32 Horner forms can exceed 1 by an ulp
+// next to t = 0 or 1; the spare bit between 2^62 and 2^63 holds that with room to spare.)  The LDS box below holds partial
+// sums of the same contributions, so the same bound holds there.
+// THE RESULT.  fp32(sum Q), rounded once (the int64 is narrowed with a sticky bit first, so the conversion through fp64 does
+// not round twice).  A source pixel that no tap reaches is +0.0; m = 0 or no finite a gives zeros.
+// NON-FINITE.  A non-finite a, or a NaN coordinate (NaN weights; taps = the clipped indices around j0 = 0, as in axis_taps),
+// is left out of m and of the sums and sets the bit of its destination element in a flag plane instead; a flagged element
+// comes out NaN, every other element keeps the bits of the clean run.
+//
+// WORKSPACE (tl_warp_bwd_image_work_bytes): [0, 256) word 0 = the bits of m | int64 accumulators, PLANAR [B,C,H,W], so that
+// neighbouring columns of one channel are neighbouring 8-byte words | one flag bit per element of g_image in its own
+// (channel-last) order.  Cleared by one memset node at the head of the call.
+//
+// SCATTER KERNEL.  One lane per output pixel, a block owns a tile of 32 x 8 output pixels (lanes along xo), the lens in
+// grid y.  Taps and weights are axis_taps' (with stride 1 the offsets are the clipped indices).  Privatised in LDS: the block
+// takes a box origin from its smallest clipped row and column (LDS atomicMin: block-uniform); contributions that land in
+// the 16 x 48 source box at that origin are added in LDS (6 KiB: occupancy is not limited by it), the others go straight to
+// the global accumulator; after a barrier the block adds its non-zero box entries to global memory, consecutive lanes on
+// consecutive columns of a row.  The channels loop through the same box.  For a smooth map of magnification near 1 this
+// replaces 16 global atomics per pixel and channel by about 1.7; for an arbitrary map everything takes the direct path.
+// flags bit 0 skips the box altogether (the A/B switch; the same contributions, so the same bits).
+constexpr int kTileX = 32, kTileY = 8;          // kTileX kTileY = kBlock
+constexpr int kBoxH = 16, kBoxW = 48;
+constexpr int64_t kMaxPixels = (int64_t)1 << 26;
+constexpr int64_t kMaxElements = (int64_t)1 << 40;
+constexpr size_t kWorkHead = 256;
+constexpr unsigned kInfBits = 0x7f800000u;
+static_assert(kTileX * kTileY == kBlock, "one lane per output pixel of the tile");
+
+typedef unsigned long long u64;
+
+// k with Q = 2^k, from the bits of m (> 0, finite)
+__device__ __forceinline__ int quantum_exponent(const unsigned mbits, const int Hb)
+{
+    const int e = (int)(mbits >> 23);
+    const int E = e ? e - 126 : (32 - __clz((int)mbits)) - 149;       // subnormal m: highest set bit p, 2^(p-149) <= m < 2^(p-148)
+    return E + Hb - 62;
+}
+
+__device__ __forceinline__ double pow2(const int k) { return __longlong_as_double((long long)(k + 1023) << 52); }   // |k| < 1023
+
+// grid-stride over the B Ho Wo output pixels of the call; one atomic per block at the most
+__global__ __launch_bounds__(kBlock) void warp_image_max_kernel(const Geo g, const float *__restrict__ gain,
+                                                                const float *__restrict__ g_out, unsigned *__restrict__ m, const int64_t n)
+{
+    __shared__ unsigned wave_best[kBlock / 64];
+    const int64_t pixels = (int64_t)g.Ho * g.Wo;
+    const int64_t gcs = g.gc == 1 ? 0 : g.gn_s[3];
+    unsigned best = 0;
+    for (int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x; at < n; at += (int64_t)gridDim.x * kBlock) {
+        const int64_t b = at / pixels, p = at - b * pixels;
+        const int yo = (int)(p / g.Wo), xo = (int)(p - (int64_t)yo * g.Wo);
+        const float *__restrict__ go = g_out + at * g.C;
+        const float *__restrict__ gp = gain ? gain + (g.gb == 1 ? 0 : b) * g.gn_s[0] + (int64_t)yo * g.gn_s[1] + (int64_t)xo * g.gn_s[2]
+                                            : nullptr;
+        for (int c = 0; c < g.C; ++c) {
+            const float a = gp ? go[c] * gp[(int64_t)c * gcs] : go[c];
+            const unsigned bits = __float_as_uint(a) & 0x7fffffffu;
+            if (bits < kInfBits) best = max(best, bits);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) best = max(best, (unsigned)__shfl_xor((int)best, off));
+    if ((threadIdx.x & 63) == 0) wave_best[threadIdx.x / 64] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < kBlock / 64; ++k) best = max(best, wave_best[k]);
+        // one word for the whole call: a block adds its atomic only when it would raise the word it sees (a stale view costs
+        // an atomic, never the maximum), so the traffic to that one address dies out as m settles
+        if (best > __hip_atomic_load(m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(m, best);
+    }
+}
+
+// grid (tiles of 32 x 8 output pixels, lenses of this launch)
+__global__ __launch_bounds__(kBlock) void warp_image_scatter_kernel(const Geo g, const float *__restrict__ x, const float *__restrict__ y,
+                                                                    const float *__restrict__ gain, const float *__restrict__ g_out,
+                                                                    const unsigned *__restrict__ m, u64 *__restrict__ acc,
+                                                                    unsigned *__restrict__ flags, const int Hb, const int direct,
+                                                                    const int b0)
+{
+    __shared__ u64 box[kBoxH * kBoxW];
+    __shared__ int origin[2];
+    const unsigned mbits = *m;
+    const double inv_q = mbits ? pow2(-quantum_exponent(mbits, Hb)) : 0.0;      // m = 0: every finite contribution is 0
+    const int tiles_x = (g.Wo + kTileX - 1) / kTileX;
+    const int ty = (int)(blockIdx.x / tiles_x), tx = (int)(blockIdx.x - (unsigned)ty * tiles_x);
+    const int xo = tx * kTileX + (threadIdx.x & (kTileX - 1)), yo = ty * kTileY + (threadIdx.x / kTileX);
+    const bool active = xo < g.Wo && yo < g.Ho;
+    const int b = b0 + blockIdx.y, bc = g.cb == 1 ? 0 : b;
+    int64_t ri[4] = {0, 0, 0, 0}, ci[4] = {0, 0, 0, 0};
+    float wy[4], wx[4], dw[4], w[16];
+    bool pass, w_finite = false;
+    if (active) {
+        axis_taps(x[(int64_t)bc * g.x_s[0] + (int64_t)yo * g.x_s[1] + (int64_t)xo * g.x_s[2]], g.W, 1, ci, wx, dw, pass);
+        axis_taps(y[(int64_t)bc * g.y_s[0] + (int64_t)yo * g.y_s[1] + (int64_t)xo * g.y_s[2]], g.H, 1, ri, wy, dw, pass);
+        w_finite = wx[0] == wx[0] && wy[0] == wy[0];      // a NaN coordinate makes all four weights of its axis NaN
+#pragma unroll
+        for (int k = 0; k < 16; ++k) w[k] = wy[k / 4] * wx[k % 4];
+    }
+    int r0 = 0, c0 = 0;
+    if (!direct) {
+        if (threadIdx.x == 0) origin[0] = origin[1] = INT_MAX;
+        for (int e = threadIdx.x; e < kBoxH * kBoxW; e += kBlock) box[e] = 0;
+        __syncthreads();
+        if (active) {                                  // tap 0 is the smallest clipped index of the pixel
+            atomicMin(&origin[0], (int)ri[0]);
+            atomicMin(&origin[1], (int)ci[0]);
+        }
+        __syncthreads();
+        r0 = origin[0];
+        c0 = origin[1];
+    }
+    // per tap row / column: its place in the box (rows as multiples of the box width), or -1 when it is outside; and the
+    // row's offset in a plane of the global accumulator.  Only clipped indices (0 <= r < H, 0 <= q < W) enter any of them.
+    int box_r[4], box_c[4];
+    int64_t row_at[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int dr = (int)ri[k] - r0, dc = (int)ci[k] - c0;                       // >= 0: the origin is the smallest
+        box_r[k] = !direct && (unsigned)dr < (unsigned)kBoxH ? dr * kBoxW : -1;
+        box_c[k] = !direct && (unsigned)dc < (unsigned)kBoxW ? dc : -1;
+        row_at[k] = ri[k] * g.W;
+    }
+    const float *__restrict__ go = g_out + (((size_t)b * g.Ho + yo) * g.Wo + xo) * g.C;               // read only when active
+    const float *__restrict__ gp = gain ? gain + (int64_t)(g.gb == 1 ? 0 : b) * g.gn_s[0] + (int64_t)yo * g.gn_s[1]
+                                                 + (int64_t)xo * g.gn_s[2] : nullptr;
+    const int64_t gcs = g.gc == 1 ? 0 : g.gn_s[3];
+    const int64_t plane_size = (int64_t)g.H * g.W;
+#pragma unroll 1
+    for (int c = 0; c < g.C; ++c) {
+        u64 *__restrict__ plane = acc + ((int64_t)b * g.C + c) * plane_size;
+        if (active) {
+            const float a = gp ? go[c] * gp[(int64_t)c * gcs] : go[c];
+            if (w_finite && (__float_as_uint(a) & 0x7fffffffu) < kInfBits) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int i = k / 4, j = k % 4;
+                    const long long v = __double2ll_rn((double)(w[k] * a) * inv_q);
+                    if ((box_r[i] | box_c[j]) >= 0) atomicAdd(&box[box_r[i] + box_c[j]], (u64)v);     // both inside the box
+                    else if (v != 0) atomicAdd(&plane[row_at[i] + ci[j]], (u64)v);
+                }
+            } else {                                   // non-finite: mark the 16 destination elements, add nothing
+                for (int k = 0; k < 16; ++k) {
+                    const int64_t e = (((int64_t)b * plane_size + row_at[k / 4] + ci[k % 4]) * g.C) + c;
+                    atomicOr(&flags[e >> 5], 1u << (unsigned)(e & 31));
+                }
+            }
+        }
+        if (!direct) {
+            __syncthreads();
+            for (int e = threadIdx.x; e < kBoxH * kBoxW; e += kBlock) {          // consecutive lanes: consecutive columns of a row
+                const u64 v = box[e];
+                if (v == 0) continue;
+                box[e] = 0;
+                const int r = r0 + e / kBoxW, q = c0 + e % kBoxW;
+                if (r < g.H && q < g.W) atomicAdd(&plane[(int64_t)r * g.W + q], v);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// grid-stride over the n = B H W C elements of g_image
+__global__ __launch_bounds__(kBlock) void warp_image_final_kernel(const Geo g, const unsigned *__restrict__ m, const u64 *__restrict__ acc,
+                                                                  const unsigned *__restrict__ flags, float *__restrict__ g_image,
+                                                                  const int Hb, const int64_t n)
+{
+    const unsigned mbits = *m;
+    const double q2048 = mbits ? pow2(quantum_exponent(mbits, Hb) + 11) : 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += (int64_t)gridDim.x * kBlock) {
+        int64_t t = e / g.C;
+        const int c = (int)(e - t * g.C);
+        const int q = (int)(t % g.W);
+        t /= g.W;
+        const int r = (int)(t % g.H);
+        const int64_t b = t / g.H;
+        const long long s = (long long)acc[((b * g.C + c) * g.H + r) * g.W + q];
+        // 53 bits and a sticky bit (round to odd): the two conversions below then round sum Q once, to fp32
+        const long long hi = (s >> 11) | (long long)((s & 0x7ff) != 0);
+        float v = s == 0 ? 0.f : (float)((double)hi * q2048);
+        if ((flags[e >> 5] >> (unsigned)(e & 31)) & 1u) v = __uint_as_float(0x7fc00000u);
+        g_image[e] = v;
+    }
+}
+
+int64_t image_elements(const tl_warp_geom *g) { return (int64_t)g->B * g->H * g->W * g->C; }   // after the size checks only
+
+bool image_sizes_ok(const tl_warp_geom *g)
+{
+    if (g->B < 1 || g->H < 1 || g->W < 1 || g->C < 1 || g->H > kMaxEdge || g->W > kMaxEdge) return false;
+    return (int64_t)g->H * g->W <= kMaxElements && (int64_t)g->B * g->C <= kMaxElements / ((int64_t)g->H * g->W);
+}
+
+size_t image_work_bytes(const int64_t n)
+{
+    const size_t raw = kWorkHead + (size_t)n * sizeof(u64) + (size_t)((n + 31) / 32) * sizeof(unsigned);
+    return (raw + 255) / 256 * 256;
+}
+
 // Everything that can be refused without a HIP call.
 int check_geom(const char *fn, const tl_warp_geom *g, bool has_gain)
 {
@@ -265,6 +482,65 @@ int tl_warp_bwd(const tl_warp_geom *g, const float *image, const float *x, const
         const int herr = (int)hipGetLastError();
         if (herr) return tl_host::hip_fail(herr, "warp_bwd_kernel launch");
     }
+    return TL_OK;
+}
+
+size_t tl_warp_bwd_image_work_bytes(const tl_warp_geom *g)
+{
+    return g && image_sizes_ok(g) ? image_work_bytes(image_elements(g)) : 0;
+}
+
+int tl_warp_bwd_image(const tl_warp_geom *g, const float *x, const float *y, const float *gain, const float *g_out, float *g_image,
+                      void *work, size_t work_bytes, int flags, void *stream)
+{
+    const int rc = check_geom("tl_warp_bwd_image", g, gain != nullptr);
+    if (rc) return rc;
+    if (!x || !y) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: x or y is NULL");
+    if (!g_out) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: g_out is NULL");
+    if (!g_image) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: g_image is NULL");
+    if ((int64_t)g->Ho * g->Wo > kMaxPixels)
+        return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: Ho Wo must be <= 2^26 (the headroom of the 64-bit accumulators)");
+    if (!image_sizes_ok(g)) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: B H W C must be <= 2^40");
+    if (flags & ~1) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: flags has bits other than bit 0 (direct atomics) set");
+    const int64_t n = image_elements(g);
+    const size_t need = image_work_bytes(n);
+    if (!work) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: work is NULL");
+    if ((uintptr_t)work % 8) return tl_host::fail(TL_EINVAL, "tl_warp_bwd_image: work must be aligned to 8 bytes");
+    if (work_bytes < need) {
+        static thread_local char msg[160];
+        snprintf(msg, sizeof(msg), "tl_warp_bwd_image: work_bytes is %zu, tl_warp_bwd_image_work_bytes asks for %zu", work_bytes, need);
+        return tl_host::fail(TL_EINVAL, msg);
+    }
+    hipError_t e = hipSetDevice(g->device);
+    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    const Geo q = make_geo(g);
+    unsigned *m = (unsigned *)work;
+    u64 *acc = (u64 *)((char *)work + kWorkHead);
+    unsigned *marks = (unsigned *)(acc + n);
+    const int64_t pixels = (int64_t)g->Ho * g->Wo;
+    int Hb = 0;                                          // ceil(log2(16 Ho Wo)), in integers
+    while (((int64_t)1 << Hb) < 16 * pixels) ++Hb;
+    e = hipMemsetAsync(work, 0, need, st);
+    if (e != hipSuccess) return tl_host::hip_fail(e, "hipMemsetAsync of the warp image workspace");
+    const unsigned tiles = (unsigned)((g->Wo + kTileX - 1) / kTileX) * (unsigned)((g->Ho + kTileY - 1) / kTileY);
+    {
+        const int64_t all = (int64_t)g->B * pixels;                   // <= 2^31 2^26
+        const unsigned mblocks = (unsigned)std::min<int64_t>((all + kBlock - 1) / kBlock, 2048);
+        hipLaunchKernelGGL(warp_image_max_kernel, dim3(mblocks), dim3(kBlock), 0, st, q, gain, g_out, m, all);
+        const int herr = (int)hipGetLastError();
+        if (herr) return tl_host::hip_fail(herr, "warp_image_max_kernel launch");
+    }
+    for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
+        hipLaunchKernelGGL(warp_image_scatter_kernel, dim3(tiles, std::min(kMaxY, g->B - b0)), dim3(kBlock), 0, st, q, x, y, gain, g_out,
+                           m, acc, marks, Hb, flags & 1, b0);
+        const int herr = (int)hipGetLastError();
+        if (herr) return tl_host::hip_fail(herr, "warp_image_scatter_kernel launch");
+    }
+    const unsigned fblocks = (unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)1 << 20);
+    hipLaunchKernelGGL(warp_image_final_kernel, dim3(fblocks), dim3(kBlock), 0, st, q, m, acc, marks, g_image, Hb, n);
+    const int herr = (int)hipGetLastError();
+    if (herr) return tl_host::hip_fail(herr, "warp_image_final_kernel launch");
     return TL_OK;
 }
 

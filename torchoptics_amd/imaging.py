@@ -172,6 +172,7 @@ def psf_grid_from_fields(kernels, grid_shape, index_map=None):
 
 
 WARP_ALPHA = -0.75        # the cubic convolution parameter of the reference's matrix (image_ops.py:150-153)
+WARP_IMAGE_GRAD_MAX_PIXELS = 1 << 26      # Ho Wo of the fixed-point image gradient (tl_warp_bwd_image)
 
 
 def _warp_axis(x, n):
@@ -207,7 +208,7 @@ def _warp_torch(image, x, y, gain):
     return out if gain is None else out * gain
 
 
-def warp_bicubic(image, x, y, gain=None, fused=None):
+def warp_bicubic(image, x, y, gain=None, fused=None, image_grad="torch"):
     """Bicubic resampling of an image at per-pixel source coordinates, times an optional gain: the distortion warp and the
     relative illumination of a rendered image (the reference's `interpolate_bicubic`, image_ops.py:109-198, which cannot run
     as written: it calls `.float()` on Python ints, sizes its output by the input's pixel count, and its `base.repeat` only
@@ -236,10 +237,24 @@ def warp_bicubic(image, x, y, gain=None, fused=None):
 
     `fused=False`: the definition in plain torch ops -- any device, any float dtype, autograd does the rest.  `fused=True`:
     the HIP kernels of csrc/tl_warp.hip (ops.WarpFunction): float32 tensors on one GPU, one launch forward and one backward
-    for the gradients to x, y and gain; anything else raises (there is no CPU fallback).  The gradient to the image is a
-    scatter and deliberately not a kernel (without atomics it needs a sort or bucket pass; with atomics it would be the first
-    result of this library that is not bit-reproducible): with `image.requires_grad`, `fused=True` raises and says so.
-    `fused=None` (default): the kernels when they apply and the image needs no gradient, torch otherwise."""
+    for the gradients to x, y and gain; anything else raises (there is no CPU fallback).  `fused=None` (default): the kernels
+    when they apply, torch otherwise.
+
+    The gradient to the image is a scatter, and `image_grad` says who computes it when `image.requires_grad`:
+    `"torch"` (default): not the kernels -- `fused=True` raises and says so, `fused=None` takes the torch path.
+    `"fused"`: tl_warp_bwd_image -- `fused=True` no longer raises for it and `fused=None` takes the kernels whenever they
+    apply.  Its contract: with a = g_out gain (the fp32 product), m the largest finite |a| of the call, 2^(E-1) <= m < 2^E and
+    Hb = ceil(log2(16 Ho Wo)), every contribution wy_i wx_j a (an fp32 product) is rounded to a multiple of the quantum
+    Q = 2^(E + Hb - 62) and added as a 64-bit integer; the result is fp32(sum Q), rounded once.  Integer sums do not depend on
+    the order, so the result has the same bits in every run, for any order or grouping of the output pixels and under any
+    launch plan, and scaling g_out by a power of two scales it exactly.  At most 16 Ho Wo <= 2^Hb contributions of magnitude
+    <= 2^(62 - Hb) quanta reach one element, so the sum cannot overflow; this needs Ho Wo <= 2^26 (then Q <= 2^(E-32)), and
+    a larger output raises a RuntimeError with `fused=True` and takes the torch path with `fused=None`.  The error is
+    ABSOLUTE on the scale of the largest seed -- Q/2 per contribution, at least 2^-32 of m -- and not relative per pixel: where
+    seeds of very different magnitude meet in one call, the small ones are resolved to 2^-32 of the largest.  A source pixel
+    that no tap reaches gets exactly +0.0.  A non-finite a, or a NaN coordinate, is left out of m and of the sums and turns the
+    elements under its 16 clipped taps into NaN; every other element keeps the bits of the clean run.
+    Any other value of `image_grad` is a ValueError."""
     if image.dim() != 4:
         raise ValueError(f"warp_bicubic: image must be [B, H, W, C], got {tuple(image.shape)}")
     B, H, W, Cc = image.shape
@@ -251,22 +266,29 @@ def warp_bicubic(image, x, y, gain=None, fused=None):
     if gain is not None and (gain.dim() != 4 or gain.shape[0] not in (1, B) or tuple(gain.shape[1:3]) != (Ho, Wo)
                              or gain.shape[3] not in (1, Cc)):
         raise ValueError(f"warp_bicubic: gain must be [B or 1, {Ho}, {Wo}, C or 1] with B = {B}, C = {Cc}, got {tuple(gain.shape)}")
+    if image_grad not in ("torch", "fused"):
+        raise ValueError(f"warp_bicubic: image_grad must be 'torch' or 'fused', got {image_grad!r}")
     tensors = [t for t in (image, x, y, gain) if t is not None]
     applies = image.is_cuda and all(t.device == image.device and t.dtype == torch.float32 for t in tensors)
-    image_grad = image.requires_grad and torch.is_grad_enabled()
+    needs_image_grad = image.requires_grad and torch.is_grad_enabled()
+    too_large = needs_image_grad and image_grad == "fused" and Ho * Wo > WARP_IMAGE_GRAD_MAX_PIXELS
     if fused is None:
-        fused = applies and not image_grad      # the kernels beat the torch path on both recorded workloads (profiles/warp_timing.txt)
+        # the kernels beat the torch path on the recorded workloads (profiles/warp_timing.txt, warp_image_grad_timing.txt)
+        fused = applies and not too_large and (not needs_image_grad or image_grad == "fused")
     if not fused:
         return _warp_torch(image, x, y, gain)
-    if image_grad:
+    if needs_image_grad and image_grad != "fused":
         raise RuntimeError("warp_bicubic(fused=True): the image requires a gradient, and the image gradient is a scatter that is "
                            "deliberately not a kernel (it would need atomics, the first result here that is not bit-reproducible, "
                            "or a sort pass): use fused=False or fused=None, or detach the image")
+    if too_large:
+        raise RuntimeError(f"warp_bicubic(fused=True, image_grad='fused'): the output has {Ho} x {Wo} pixels, and the fixed-point "
+                           "image gradient takes at most 2^26 (the headroom of its 64-bit sums): use fused=False")
     if not applies:
         what = ", ".join(f"{n} {t.dtype} on {t.device}" for n, t in zip(("image", "x", "y", "gain"), (image, x, y, gain)) if t is not None)
         raise RuntimeError(f"warp_bicubic(fused=True): {what}; the fused warp runs only as HIP kernels on float32 tensors on "
                            "one AMD GPU (there is no CPU fallback): use fused=False")
-    return ops.WarpFunction.apply(image, x, y, gain)
+    return ops.WarpFunction.apply(image, x, y, gain, image_grad == "fused")
 
 
 def _pixel_axes(out_size, aspect, dtype, device):

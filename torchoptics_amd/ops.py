@@ -616,23 +616,39 @@ class SvolaFunction(torch.autograd.Function):
         return g_image, g_psfs, None
 
 
-# C-ABI calls of WarpFunction since import (tests: the backward runs only when a coordinate or the gain needs a gradient), and
-# the pointers the last forward handed to the kernel (strided views go through as they are: no copy)
-_warp_calls = {"fwd": 0, "bwd": 0, "image_ptr": None, "x_ptr": None, "y_ptr": None, "gain_ptr": None}
+# C-ABI calls of WarpFunction since import (tests: the backward runs only when a coordinate or the gain needs a gradient, the
+# image backward only when the image does), and the pointers the last forward handed to the kernel (strided views go through
+# as they are: no copy)
+_warp_calls = {"fwd": 0, "bwd": 0, "bwd_image": 0, "image_ptr": None, "x_ptr": None, "y_ptr": None, "gain_ptr": None}
+_WARP_IMAGE_PATHS = {"auto": 0, "direct": 1}      # tl_warp_bwd_image's flags
+_warp_image_path = "auto"
 
 
 def warp_counts() -> dict:
-    """{'fwd': n, 'bwd': n, 'image_ptr', 'x_ptr', 'y_ptr', 'gain_ptr': data pointers of the last forward's arguments}."""
+    """{'fwd': n, 'bwd': n, 'bwd_image': n, 'image_ptr', 'x_ptr', 'y_ptr', 'gain_ptr': data pointers of the last forward's
+    arguments}."""
     return dict(_warp_calls)
+
+
+def set_warp_image_grad_path(path: str) -> None:
+    """How tl_warp_bwd_image adds up: 'auto' (default) privatises a box of the source image in LDS per tile of output pixels,
+    'direct' sends every contribution to the global accumulator.  The same bits either way (64-bit integer sums); 'direct'
+    is the A/B switch and the cross-check of the two paths."""
+    global _warp_image_path
+    if path not in _WARP_IMAGE_PATHS:
+        raise ValueError(f"set_warp_image_grad_path: path must be one of {sorted(_WARP_IMAGE_PATHS)}, got {path!r}")
+    _warp_image_path = path
 
 
 class WarpFunction(torch.autograd.Function):
     """out [B,Ho,Wo,C] = gain x the bicubic resampling of image [B,H,W,C] at the normalised coordinates x, y [B or 1,Ho,Wo]
-    (tl_warp_fwd / tl_warp_bwd; imaging.warp_bicubic(fused=True), which checks the arguments).  gain [B or 1,Ho,Wo,C or 1] or
-    None.
+    (tl_warp_fwd / tl_warp_bwd / tl_warp_bwd_image; imaging.warp_bicubic(fused=True), which checks the arguments).  gain
+    [B or 1,Ho,Wo,C or 1] or None.  An optional fifth argument, True, allows the gradient to the image.
 
     float32 on one GPU; every tensor is taken with the strides it has.  Differentiable in x, y and gain: one backward launch,
-    and only when one of them needs a gradient.  The image gradient (a scatter) is not a kernel: asking for it raises."""
+    and only when one of them needs a gradient.  The image gradient is a scatter in 64-bit fixed point (tl_warp_bwd_image:
+    bit-reproducible, error absolute on the scale of the largest seed); it runs once, only when the image needs a gradient,
+    and only when the fifth argument allowed it: otherwise asking for it raises."""
 
     @staticmethod
     def _geom(image, x, y, gain, g_x=None, g_y=None, g_gain=None):
@@ -650,8 +666,10 @@ class WarpFunction(torch.autograd.Function):
         return q
 
     @staticmethod
-    def forward(ctx, image, x, y, gain):
+    def forward(ctx, image, x, y, gain, *allow_image_grad):
         ctx.set_materialize_grads(False)
+        ctx.image_grad = bool(allow_image_grad and allow_image_grad[0])
+        ctx.n_in = 4 + len(allow_image_grad)
         dev = image.device
         out = torch.empty((image.shape[0], x.shape[1], x.shape[2], image.shape[3]), dtype=torch.float32, device=dev)
         q = WarpFunction._geom(image, x, y, gain)
@@ -665,24 +683,34 @@ class WarpFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out):
         need_image, need_x, need_y, need_gain = ctx.needs_input_grad[:4]
-        if need_image:
+        if need_image and not ctx.image_grad:
             raise RuntimeError("WarpFunction: the gradient to the image is a scatter and is not a kernel; use "
                                "imaging.warp_bicubic(fused=False) when the image needs a gradient")
-        if g_out is None or not (need_x or need_y or need_gain):
-            return None, None, None, None
+        none = (None,) * (ctx.n_in - 4)
+        if g_out is None or not (need_image or need_x or need_y or need_gain):
+            return (None, None, None, None) + none
         image, x, y, gain = ctx.saved_tensors
         dev = image.device
         g_out = g_out.to(torch.float32).contiguous()
-        g_x = g_y = g_gain = None
-        if need_x or need_y:
-            g_x = torch.empty(x.shape, dtype=torch.float32, device=dev)
-            g_y = torch.empty(y.shape, dtype=torch.float32, device=dev)
-        if need_gain:
-            g_gain = torch.empty(gain.shape, dtype=torch.float32, device=dev)
-        q = WarpFunction._geom(image, x, y, gain, g_x, g_y, g_gain)
-        _call("tl_warp_bwd", dev, C.byref(q), image, x, y, gain, g_out, g_x, g_y, g_gain)
-        _warp_calls["bwd"] += 1
-        return None, g_x if need_x else None, g_y if need_y else None, g_gain
+        g_image = g_x = g_y = g_gain = None
+        if need_x or need_y or need_gain:
+            if need_x or need_y:
+                g_x = torch.empty(x.shape, dtype=torch.float32, device=dev)
+                g_y = torch.empty(y.shape, dtype=torch.float32, device=dev)
+            if need_gain:
+                g_gain = torch.empty(gain.shape, dtype=torch.float32, device=dev)
+            q = WarpFunction._geom(image, x, y, gain, g_x, g_y, g_gain)
+            _call("tl_warp_bwd", dev, C.byref(q), image, x, y, gain, g_out, g_x, g_y, g_gain)
+            _warp_calls["bwd"] += 1
+        if need_image:
+            g_image = torch.empty(image.shape, dtype=torch.float32, device=dev)
+            q = WarpFunction._geom(image, x, y, gain)
+            nbytes = _lib.lib().tl_warp_bwd_image_work_bytes(C.byref(q))
+            ws = _workspace(nbytes, dev)
+            _call("tl_warp_bwd_image", dev, C.byref(q), x, y, gain, g_out, g_image, ws, ws.numel(),
+                  _WARP_IMAGE_PATHS[_warp_image_path])
+            _warp_calls["bwd_image"] += 1
+        return (g_image, g_x if need_x else None, g_y if need_y else None, g_gain) + none
 
 
 class PupilPositionFunction(torch.autograd.Function):
