@@ -391,6 +391,49 @@ int tl_psf_accumulate_bwd(int32_t device, int32_t G, int32_t W, int64_t R, const
                           size_t workspace_bytes, void *stream);
 
 /*
+ * The PSF soft histogram of K traced fans on G grids, each grid reading ONE fan rotated about the grid's centre: the PSF
+ * grid over an image of a rotationally symmetric lens, where the PSF at azimuth phi is the histogram of the +y-meridian spot
+ * rotated by phi (imaging.psf_grid_from_trace(fused=True); additive entry points, ABI unchanged).  x, y, weight, ok, gx, gy
+ * are addressed as above with the SOURCE index: ray r of fan k, channel w is element k s_g + w s_w + r, k < K.  Per grid
+ * g < G, with k = src[g] (device int32 [G], 0 <= src[g] < K) and c[g], s[g] (device floats [G], cos and sin of the angle):
+ *     xi = x[k,w,r],   eta = y[k,w,r] - y_centre[k]                       y_centre is per SOURCE, [K]
+ *     x' = fma(c, xi, s * eta),   y' = fma(c, eta, -(s * xi))             float32: one product, one fma each, as written
+ *     u = x' / x_pitch[g],   v = y' / y_pitch[g]                          the pitches are per GRID, [G]
+ *     hist[g,w,i,j] = sum_r wt_r Gy_i(v) Gx_j(u),   j < nx, i < ny        float [G,W,ny,nx], Gx, Gy as above
+ * on the FULL grid: nothing is mirrored, x_first = 0.5 - nx/2 centres it as y_first = 0.5 - ny/2 does.  A ray of weight 0
+ * (or ok 0) is dropped BEFORE the rotation: it adds exactly 0 whatever its coordinates, NaN included.  With c = 1, s = 0 and
+ * src[g] = g the results have the bits of tl_psf_accumulate / _bwd on the same arguments (nxh = nx; the sign of a gradient
+ * that underflowed to an exact zero aside: turning it back adds 0 gy' to it).
+ * Forward: the scheme of tl_psf_accumulate (fp32 MFMA chains of 64 rays, fp64 totals, fixed-order partials): the same bits
+ * on every run, no atomics.
+ * Backward: g_hist [G,W,ny,nx] -> gx, gy [K,W,R] (strided like x, y; OVERWRITTEN) in SOURCE coordinates, the sum over the
+ * grids that read the fan.  field_start [K+1], field_grids [G] (device int32) are the CSR inverse of src: the grids of fan k
+ * are field_grids[field_start[k] .. field_start[k+1]), ascending.  One lane per source ray walks that list, rotates each
+ * grid's (gx', gy') back, t_xi = fma(c, gx', -(s * gy')), t_eta = fma(c, gy', s * gx'), and adds the terms in list order (the
+ * first is taken as it is): no atomics, the same bits on every run; a fan that no grid reads gets exactly +0.0.
+ * g_y_centre [K] (nullable) = -sum_{w,r} gy, reduced in fp64 in a fixed order.  The pitches and the weights carry no gradient.
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, nx or ny outside 1..32,
+ * G, K or W < 1, G W or K W > 2^20 = 1048576 (the rows are folded over two grid axes inside: the 65535 of tl_psf_accumulate
+ * does not bind), R < 1, G W R or K W R > 2^36, weight and ok both given.  NOT checked (it would need a host sync): the
+ * entries of src, field_start and field_grids -- an entry out of range reads or writes out of bounds; the caller guarantees
+ * 0 <= src[g] < K and that the CSR lists are the inverse of src.  TL_EWORKSPACE: fewer bytes than
+ * tl_psf_rot_workspace_bytes asks for (one size serves both calls; 0 for arguments out of range).  No host synchronisation;
+ * caller-owned buffers; re-entrant.
+ */
+size_t tl_psf_rot_workspace_bytes(int32_t G, int32_t K, int32_t W, int64_t R, int32_t nx, int32_t ny);
+int tl_psf_rot_accumulate(int32_t device, int32_t G, int32_t K, int32_t W, int64_t R, const float *x, const float *y,
+                          const float *weight, const uint8_t *ok, int64_t s_g, int64_t s_w, const int32_t *src, const float *c,
+                          const float *s, const float *x_pitch, const float *y_pitch, const float *y_centre, int32_t nx,
+                          int32_t ny, float x_first, float y_first, float *hist, void *workspace, size_t workspace_bytes,
+                          void *stream);
+int tl_psf_rot_accumulate_bwd(int32_t device, int32_t G, int32_t K, int32_t W, int64_t R, const float *x, const float *y,
+                              const float *weight, const uint8_t *ok, int64_t s_g, int64_t s_w, const int32_t *src,
+                              const float *c, const float *s, const float *x_pitch, const float *y_pitch,
+                              const float *y_centre, int32_t nx, int32_t ny, float x_first, float y_first,
+                              const int32_t *field_start, const int32_t *field_grids, const float *g_hist, float *gx, float *gy,
+                              float *g_y_centre, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Spatially varying overlap-add PSF convolution of an image and its adjoints (imaging.svola_convolution(fused=True);
  * additive entry points, ABI unchanged).  The image [B,H,W,C] is cut into a gh x gw grid of overlapping patches of
  * ph = H/gh + 2 oh rows and pw = W/gw + 2 ow columns in the frame of Ih = H + 2 oh rows and Iw = W + 2 ow columns (the image

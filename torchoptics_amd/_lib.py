@@ -118,6 +118,13 @@ _SIGNATURES = {
                           + [C.c_float] * 2 + [_VP] + _WS),
     "tl_psf_accumulate_bwd": (C.c_int, [C.c_int32] * 3 + [C.c_int64] + [_VP] * 4 + [C.c_int64] * 2 + [_VP] * 3 + [C.c_int32] * 2
                               + [C.c_float] * 2 + [_VP] * 6 + _WS),
+    "tl_psf_rot_workspace_bytes": (C.c_size_t, [C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 2),
+    # device, G, K, W, R | x, y, weight, ok | s_g, s_w | src, c, s | x_pitch, y_pitch, y_centre | nx, ny | x_first, y_first | ...
+    "tl_psf_rot_accumulate": (C.c_int, [C.c_int32] * 4 + [C.c_int64] + [_VP] * 4 + [C.c_int64] * 2 + [_VP] * 6 + [C.c_int32] * 2
+                              + [C.c_float] * 2 + [_VP] + _WS),
+    # ... | field_start, field_grids | g_hist | gx, gy, g_y_centre | ...
+    "tl_psf_rot_accumulate_bwd": (C.c_int, [C.c_int32] * 4 + [C.c_int64] + [_VP] * 4 + [C.c_int64] * 2 + [_VP] * 6
+                                  + [C.c_int32] * 2 + [C.c_float] * 2 + [_VP] * 6 + _WS),
     # geom, r0, r1, c0, c1 (host ints) | wr, wc (device doubles) | ...
     "tl_svola_workspace_bytes": (C.c_size_t, [_SV] + [_VP] * 4),
     "tl_svola_fwd": (C.c_int, [_SV] + [_VP] * 4 + [_VP] * 2 + [_VP] * 3 + [_VP]),

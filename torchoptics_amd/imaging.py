@@ -171,6 +171,170 @@ def psf_grid_from_fields(kernels, grid_shape, index_map=None):
     return kernels.permute(0, 2, 3, 1).unsqueeze(0)
 
 
+@functools.lru_cache(maxsize=64)
+def _psf_grid_cells(H, W, gh, gw, oh, ow, fields, aspect, blend):
+    geo = svola_geometry(H, W, gh, gw, oh, ow)
+    f = np.asarray(fields, dtype=np.float64)
+    # the middle pixel of a patch, (lo + hi - 1) / 2 in the frame, less the overlap margin; then _pixel_axes' normalisation,
+    # written (2 p - (n - 1)) / (n - 1) so that mirrored patches get exactly opposite coordinates
+    norm = lambda lo, hi, o, n: ((lo + hi - 1.0) - 2.0 * o - (n - 1)) / (n - 1) if n > 1 else np.zeros(len(lo))  # noqa: E731
+    yn, xn = norm(geo.r0, geo.r1, oh, H), norm(geo.c0, geo.c1, ow, W)
+    a = float(W) / float(H) if aspect is None else float(aspect)
+    X, Y = np.broadcast_to(xn[None, :] * a, (gh, gw)).reshape(-1), np.broadcast_to(yn[:, None], (gh, gw)).reshape(-1)
+    rad = np.hypot(X, Y)
+    h = rad / np.sqrt(a * a + 1.0)
+    centre = rad == 0
+    safe = np.where(centre, 1.0, rad)
+    s_cell, c_cell = np.where(centre, 0.0, X / safe), np.where(centre, 1.0, Y / safe)
+    src, cell, beta = [], [], []
+    for n in range(gh * gw):
+        if blend == "nearest":
+            terms = [(int(np.argmin(np.abs(f - h[n]))), 1.0)]
+        elif h[n] <= f[0]:
+            terms = [(0, 1.0)]
+        elif h[n] >= f[-1]:
+            terms = [(len(f) - 1, 1.0)]
+        else:
+            k = int(np.searchsorted(f, h[n], side="right")) - 1
+            t = (h[n] - f[k]) / (f[k + 1] - f[k])
+            terms = [(k, 1.0 - t), (k + 1, t)]
+        for k, b in terms:
+            if b != 0.0:
+                src.append(k)
+                cell.append(n)
+                beta.append(b)
+    cell = np.asarray(cell, dtype=np.int64)
+    grid = ops.psf_rot_grid(np.asarray(src, dtype=np.int64), c_cell[cell], s_cell[cell], len(f))
+    return SimpleNamespace(gh=gh, gw=gw, N=gh * gw, n_fields=len(f), X=X, Y=Y, h=h, s_cell=s_cell, c_cell=c_cell, grid=grid,
+                           src=grid.src, c=grid.c, s=grid.s, field_start=grid.field_start, field_grids=grid.field_grids,
+                           cell=cell, beta=np.asarray(beta, dtype=np.float64), batched={1: grid}, blend_tables={})
+
+
+def psf_grid_cells(image_size, grid_shape, overlap_size, fields, aspect=None, blend="linear"):
+    """Where the PSFs of a gh x gw svola grid come from, for a rotationally symmetric lens traced along the +y meridian: pure
+    host geometry (numpy, no GPU), memoised.
+
+    image_size (H, W), grid_shape (gh, gw) and overlap_size (int or (oh, ow)) are svola_convolution's; `fields` [K] are the
+    relative image heights of the traced fields (ascending, >= 0; 0 is allowed), in units of the half-diagonal as in
+    radial_map; `aspect` is width / height (default W / H).
+
+    Cell n = i gw + j sits at the middle of its patch [r0, r1) x [c0, c1) of svola_geometry less the overlap margin, in the
+    normalised pixel coordinates of the warp (columns are x, rows are y, both growing with the index, -1 .. +1 over the
+    image): (X, Y) = (x aspect, y) and h = |(X, Y)| / sqrt(aspect^2 + 1), 1 at the corner.  Its rotation is
+    (s, c) = (X, Y) / |(X, Y)|, (0, 1) at the exact centre: a spot traced at (xi, eta) about its centre lands at
+    x' = c xi + s eta (columns), y' = -s xi + c eta (rows), so the trace's +y meridian points along the cell's radius.
+    Every cell is up to two terms (field, beta): with blend="linear" the two traced fields that bracket h with linear weights
+    in h (one term of beta = 1 at or beyond the first and the last field, and terms of beta = 0 are dropped); with
+    blend="nearest" the nearest field alone.
+
+    Returns a namespace: the flat term list `src`, `c`, `s` [T] (int32 / float32, as the kernels take them), `cell` [T] (the
+    cell of every term, ascending) and `beta` [T] (float64; sums to 1 per cell), the CSR inverse of src `field_start` [K+1] and
+    `field_grids` [T], and per cell X, Y, h, s_cell, c_cell [N] (float64); `grid` is the ops.psf_rot_grid of the term list."""
+    H, W = (int(v) for v in image_size)
+    gh, gw = (int(v) for v in grid_shape)
+    oh, ow = (int(overlap_size),) * 2 if isinstance(overlap_size, int) else (int(v) for v in overlap_size)
+    f = tuple(float(v) for v in np.asarray(fields, dtype=np.float64).reshape(-1))
+    if len(f) < 1 or f[0] < 0 or any(b <= a for a, b in zip(f, f[1:])):
+        raise ValueError("psf_grid_cells: fields must be ascending and >= 0")
+    if blend not in ("linear", "nearest"):
+        raise ValueError(f"psf_grid_cells: blend must be 'linear' or 'nearest', got {blend!r}")
+    if gh < 1 or gw < 1:
+        raise ValueError(f"psf_grid_cells: grid_shape must be (gh, gw) >= 1, got {tuple(grid_shape)}")
+    return _psf_grid_cells(H, W, gh, gw, oh, ow, f, None if aspect is None else float(aspect), blend)
+
+
+def _batched_grid(cells, B):
+    """The term list of `cells` repeated for B lenses: grid b T + t reads fan b K + src[t]."""
+    if B not in cells.batched:
+        g, K = cells.grid, cells.n_fields
+        src = (np.arange(B)[:, None] * K + g.src[None, :].astype(np.int64)).reshape(-1)
+        cells.batched[B] = ops.psf_rot_grid(src, np.tile(g.c, B), np.tile(g.s, B), B * K)
+    return cells.batched[B]
+
+
+PSF_GRID_FUSED_BY_DEFAULT = True          # profiles/psf_grid_timing.txt
+
+
+def psf_grid_from_trace(x, y, ray_ok, cells, n_bins, increment, y_target=None, fused=None):
+    """The PSFs of a whole svola grid from one traced column of fields of a rotationally symmetric lens: psfs
+    [B, N, ny, nx, W], ready for svola_convolution.
+
+    x, y [B, F, P, W]: the tracer's outputs for F fields along the +y meridian (metrics.psf_from_trace takes the same);
+    ray_ok the same shape or None (every ray counts); cells: psf_grid_cells(...) for F fields; n_bins = (nx, ny);
+    `increment`: the pixel pitch of the sensor, required (a grid sized from the data makes no sense across cells);
+    y_target [B F] or None: the centre of every field's spot, by default its ok-weighted mean y as in psf_from_trace.
+
+    The kernel of one term (field k, rotation (c, s)) is the soft histogram of compute_psf on the FULL nx x ny grid (pixel
+    centres increment (j + 1/2 - nx/2), nothing mirrored) of the field's rays turned about (0, y_target[k]):
+        xi = x, eta = y - y_target[k];   x' = c xi + s eta,  y' = -s xi + c eta      (c, s: the float32 values of `cells`)
+    normalised to unit sum per channel; the PSF of a cell is sum beta kernel over its terms -- normalised first, blended
+    after, so that a vignetted field does not count for less.  Exact for a rotationally symmetric lens: nothing is resampled.
+
+    `fused=False`: the definition in plain torch ops (rotate per term, the two Gaussian operands, a matmul) -- any device, any
+    float dtype, and 8 (nx + ny) bytes per ray and TERM of operands.  `fused=True`: the HIP kernels of csrc/tl_psf.hip
+    (ops.PsfRotAccumulateFunction): float32 on the GPU, at most 32 bins per axis; the rotation and the field lookup happen in
+    the kernels' loads and nothing per ray and term is stored; anything else raises.  `fused=None` (default): the kernels when
+    they apply (they are faster on the recorded workload, profiles/psf_grid_timing.txt), torch otherwise.
+    Gradients flow to x and y, and to y_target when it is derived from them (or given as a tensor that requires one); the
+    pitch and ray_ok carry none."""
+    if x.dim() != 4 or y.shape != x.shape:
+        raise ValueError(f"psf_grid_from_trace: x and y must both be [B, F, P, W], got {tuple(x.shape)} and {tuple(y.shape)}")
+    B, F_, P, W = x.shape
+    if F_ != cells.n_fields:
+        raise ValueError(f"psf_grid_from_trace: x holds {F_} fields, the cells were laid out for {cells.n_fields}")
+    nx, ny = (int(v) for v in n_bins)
+    if nx < 1 or ny < 1:
+        raise ValueError(f"psf_grid_from_trace: n_bins must be (nx, ny) >= 1, got {tuple(n_bins)}")
+    inc = float(increment)
+    applies = (x.is_cuda and y.device == x.device and x.dtype == torch.float32 and y.dtype == torch.float32
+               and max(nx, ny) <= ops.PSF_MAX_BINS)
+    if fused is None:
+        fused = applies and PSF_GRID_FUSED_BY_DEFAULT
+    if fused:
+        if max(nx, ny) > ops.PSF_MAX_BINS:
+            raise ValueError(f"psf_grid_from_trace(fused=True) takes at most {ops.PSF_MAX_BINS} bins per axis, got {tuple(n_bins)}")
+        if not applies:
+            raise RuntimeError(f"psf_grid_from_trace(fused=True): x is {x.dtype} on {x.device}; the fused PSF runs only as a HIP "
+                               "kernel on float32 tensors on an AMD GPU (there is no CPU fallback): use fused=False")
+    K = B * F_
+    xs, ys = x.permute(0, 1, 3, 2).reshape(K, W, P), y.permute(0, 1, 3, 2).reshape(K, W, P)
+    ok = None if ray_ok is None else ray_ok.permute(0, 1, 3, 2).reshape(K, W, P)
+    if y_target is None:
+        if ok is None:
+            y_target = ys.reshape(K, -1).mean(dim=1)
+        else:
+            wf = ok.to(y.dtype)
+            y_target = (ys * wf).reshape(K, -1).sum(dim=1) / wf.reshape(K, -1).sum(dim=1).clamp_min(1)
+    else:
+        y_target = torch.as_tensor(y_target, dtype=y.dtype, device=y.device).reshape(K)
+    grid = _batched_grid(cells, B)
+    if fused:
+        hist = ops.PsfRotAccumulateFunction.apply(xs, ys, ok, grid, inc, inc, y_target, nx, ny, 0.5 - nx / 2, 0.5 - ny / 2)
+    else:
+        src = torch.from_numpy(grid.src.astype(np.int64)).to(x.device)
+        c = torch.from_numpy(grid.c).to(device=x.device, dtype=x.dtype)[:, None, None]
+        s = torch.from_numpy(grid.s).to(device=x.device, dtype=x.dtype)[:, None, None]
+        xi, eta = xs[src], (ys - y_target[:, None, None])[src]                              # [G, W, P]
+        xr, yr = c * xi + s * eta, c * eta - s * xi
+        rng = lambda n: (torch.arange(n, dtype=x.dtype, device=x.device) + (0.5 - n / 2)) * inc       # noqa: E731
+        g_x = torch.exp(-((xr[:, :, None, :] - rng(nx)[:, None]) / (inc / 2)) ** 2 / 2)      # [G, W, nx, P]
+        g_y = torch.exp(-((yr[:, :, None, :] - rng(ny)[:, None]) / (inc / 2)) ** 2 / 2)      # [G, W, ny, P]
+        if ok is not None:
+            g_y = g_y * ok[src][:, :, None, :].to(x.dtype)
+        hist = torch.matmul(g_y, g_x.transpose(-1, -2))                                      # [G, W, ny, nx]
+    kern = hist / hist.sum(dim=(-1, -2), keepdim=True)
+    key = (x.device, B, kern.dtype)
+    if key not in cells.blend_tables:                       # uploaded once per device, batch and dtype (a captured step uploads nothing)
+        cells.blend_tables[key] = (
+            torch.from_numpy((np.arange(B)[:, None] * cells.N + cells.cell[None, :]).reshape(-1)).to(x.device),
+            torch.from_numpy(np.tile(cells.beta, B)).to(device=x.device, dtype=kern.dtype))
+    cell, beta = cells.blend_tables[key]
+    assert kern.shape[0] == cell.numel()
+    psfs = torch.zeros((B * cells.N, W, ny, nx), dtype=kern.dtype, device=x.device).index_add(
+        0, cell, kern * beta[:, None, None, None])
+    return psfs.reshape(B, cells.N, W, ny, nx).permute(0, 1, 3, 4, 2)
+
+
 WARP_ALPHA = -0.75        # the cubic convolution parameter of the reference's matrix (image_ops.py:150-153)
 WARP_IMAGE_GRAD_MAX_PIXELS = 1 << 26      # Ho Wo of the fixed-point image gradient (tl_warp_bwd_image)
 

@@ -19,8 +19,10 @@ lenses is ONE launch (tl_problem.B); B = 1 is the reference's callers' case.
 """
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -537,6 +539,114 @@ class PsfAccumulateFunction(torch.autograd.Function):
               x_first, y_first, gh, gx, gy, g_xp, g_yp, g_yc, ws, ws.numel())
         g_xp, g_yp, g_yc = (g if g is None else g.reshape(s) for g, s in zip((g_xp, g_yp, g_yc), ctx.shapes))
         return (gx if need[0] else None, gy if need[1] else None, None, g_xp, g_yp, g_yc, None, None, None, None)
+
+
+PSF_ROT_MAX_ROWS = 1 << 20          # G W and K W of tl_psf_rot_accumulate (include/tl_trace.h)
+
+
+def psf_rot_grid(src, c, s, n_sources):
+    """The host side of G rotated grids over K = n_sources fans, checked here because the kernels cannot: src [G] (the fan
+    of every grid, 0 <= src < K), c, s [G] (cos and sin of its angle).  Returns a namespace of G, K, the arrays as the C ABI
+    takes them (int32 / float32) and the CSR inverse of src -- field_grids[field_start[k] : field_start[k+1]] are the grids
+    that read fan k, ascending -- with a cache of their device copies (uploaded once per device)."""
+    src = np.asarray(src).reshape(-1)
+    G, K = src.size, int(n_sources)
+    if G < 1 or K < 1:
+        raise ValueError(f"psf_rot_grid: at least one grid and one source fan are needed, got {G} and {K}")
+    if not np.issubdtype(src.dtype, np.integer) or int(src.min()) < 0 or int(src.max()) >= K:
+        raise ValueError(f"psf_rot_grid: src must hold integers in 0..{K - 1}")
+    c, s = (np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1)) for a in (c, s))
+    if c.size != G or s.size != G:
+        raise ValueError(f"psf_rot_grid: c and s must hold {G} entries, one per grid")
+    field_start = np.concatenate(([0], np.cumsum(np.bincount(src, minlength=K)))).astype(np.int32)
+    field_grids = np.argsort(src, kind="stable").astype(np.int32)
+    return SimpleNamespace(G=G, K=K, src=src.astype(np.int32), c=c, s=s, field_start=field_start, field_grids=field_grids,
+                           device_tables={})
+
+
+def _rot_tables(grid, dev):
+    key = (dev.type, dev.index)
+    if key not in grid.device_tables:
+        grid.device_tables[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in
+                                        (grid.src, grid.c, grid.s, grid.field_start, grid.field_grids))
+    return grid.device_tables[key]
+
+
+class PsfRotAccumulateFunction(torch.autograd.Function):
+    """hist [G,W,ny,nx] = sum_r wt_r Gy_i(r) Gx_j(r) of G full (un-mirrored) grids that each read one of K fans, rotated by
+    the grid's (c, s) about the fan's centre (tl_psf_rot_accumulate / tl_psf_rot_accumulate_bwd;
+    imaging.psf_grid_from_trace(fused=True)).
+
+    x, y [K,W,R] float32 on the GPU, taken as PsfAccumulateFunction takes them; weight likewise; grid: psf_rot_grid(...);
+    x_pitch, y_pitch: a float or a [G] tensor, explicit and WITHOUT gradient; y_centre [K], per source fan.  Differentiable
+    in x, y (source coordinates: the sum over the grids that read the fan) and y_centre; the weights carry NO gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, grid, x_pitch, y_pitch, y_centre, nx, ny, x_first, y_first):
+        for name, ten in (("x", x), ("y", y), ("y_centre", y_centre)):
+            _require_device(ten, name)
+            if ten.dtype != torch.float32:
+                raise RuntimeError(f"torchoptics_amd: the fused PSF takes float32 tensors; `{name}` is {ten.dtype} "
+                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        if not (1 <= nx <= PSF_MAX_BINS and 1 <= ny <= PSF_MAX_BINS):
+            raise ValueError(f"the fused PSF takes 1..{PSF_MAX_BINS} bins per axis (got {ny} x {nx})")
+        dev = x.device
+        K, W, R = x.shape
+        G = grid.G
+        if grid.K != K:
+            raise ValueError(f"the fused PSF grid was laid out for {grid.K} source fans, x holds {K}")
+        if G * W > PSF_ROT_MAX_ROWS or K * W > PSF_ROT_MAX_ROWS:
+            raise ValueError(f"the fused PSF grid takes at most {PSF_ROT_MAX_ROWS} (grid, channel) rows, got {G} x {W}")
+        if x.stride(2) != 1 or any(s == 0 for s in x.stride()[:2]):
+            x = x.contiguous()
+        if y.stride() != x.stride():
+            y = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev).copy_(y)
+        wf = wb = None
+        if weight is not None:
+            _require_device(weight, "weight")
+            if weight.dtype in (torch.bool, torch.uint8):
+                wb = weight.view(torch.uint8) if weight.dtype == torch.bool else weight
+            else:
+                wf = weight.detach().to(torch.float32)
+            wt = wb if wb is not None else wf
+            if wt.shape != x.shape:
+                raise ValueError("the fused PSF: weights must have the shape of x")
+            if wt.stride() != x.stride():
+                wt = torch.empty_strided(x.shape, x.stride(), dtype=wt.dtype, device=dev).copy_(wt)
+            wf, wb = (None, wt) if wb is not None else (wt, None)
+        pitch = lambda p: (p.detach().to(device=dev, dtype=torch.float32).reshape(G).contiguous() if torch.is_tensor(p)  # noqa: E731
+                           else torch.full((G,), float(p), dtype=torch.float32, device=dev))
+        xp, yp = pitch(x_pitch), pitch(y_pitch)
+        yc = y_centre.detach().reshape(K).contiguous()
+        src, c, s, fstart, fgrids = _rot_tables(grid, dev)
+        nbytes = _lib.lib().tl_psf_rot_workspace_bytes(G, K, W, R, nx, ny)
+        ws = _workspace(nbytes, dev)
+        hist = torch.empty((G, W, ny, nx), dtype=torch.float32, device=dev)
+        _call("tl_psf_rot_accumulate", dev, dev.index, G, K, W, R, x, y, wf, wb, x.stride(0), x.stride(1), src, c, s, xp, yp, yc,
+              nx, ny, float(x_first), float(y_first), hist, ws, ws.numel())
+        ctx.save_for_backward(x, y, wf, wb, xp, yp, yc)
+        ctx.grid = grid
+        ctx.geom = (nx, ny, float(x_first), float(y_first), nbytes)
+        ctx.yc_shape = y_centre.shape
+        return hist
+
+    @staticmethod
+    def backward(ctx, g_hist):
+        x, y, wf, wb, xp, yp, yc = ctx.saved_tensors
+        nx, ny, x_first, y_first, nbytes = ctx.geom
+        dev = x.device
+        K, W, R = x.shape
+        src, c, s, fstart, fgrids = _rot_tables(ctx.grid, dev)
+        gh = g_hist.to(torch.float32).contiguous()
+        gx = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
+        gy = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev)
+        need = ctx.needs_input_grad
+        g_yc = torch.empty(K, dtype=torch.float32, device=dev) if need[6] else None
+        ws = _workspace(nbytes, dev)
+        _call("tl_psf_rot_accumulate_bwd", dev, dev.index, ctx.grid.G, K, W, R, x, y, wf, wb, x.stride(0), x.stride(1), src, c, s,
+              xp, yp, yc, nx, ny, x_first, y_first, fstart, fgrids, gh, gx, gy, g_yc, ws, ws.numel())
+        return (gx if need[0] else None, gy if need[1] else None, None, None, None, None,
+                None if g_yc is None else g_yc.reshape(ctx.yc_shape), None, None, None, None)
 
 
 SVOLA_MAX_TAPS = 31       # rows / columns of a PSF the tl_svola_* kernels take (tile plus halo in LDS)
