@@ -404,9 +404,10 @@ Geo make_geo(const tl_svola_geom *g)
     return q;
 }
 
-// fn(tiles, row_base, col_base, n_rows, n_cols, b0, nb): every chunk of <= kMaxSeg x kMaxSeg tiles and <= 65535 / C lenses
+// fn(tiles, row_base, col_base, n_rows, n_cols, b0, nb) launches one chunk of <= kMaxSeg x kMaxSeg tiles and <= 65535 / C
+// lenses; every launch is checked as `what`
 template <class F>
-int for_chunks(const std::vector<Seg> &rows, const std::vector<Seg> &cols, int B, int C, F fn)
+int for_chunks(const std::vector<Seg> &rows, const std::vector<Seg> &cols, int B, int C, const char *what, F fn)
 {
     const int bmax = std::max(1, kMaxZ / C);
     Tiles tl;
@@ -419,12 +420,12 @@ int for_chunks(const std::vector<Seg> &rows, const std::vector<Seg> &cols, int B
                 tl.cols[k] = cols[cb + std::min(k, nc - 1)];
             }
             for (int b0 = 0; b0 < B; b0 += bmax) {
-                const int herr = fn(tl, (int)rb, (int)cb, nr, nc, b0, std::min(bmax, B - b0));
-                if (herr) return herr;
+                fn(tl, (int)rb, (int)cb, nr, nc, b0, std::min(bmax, B - b0));
+                if (const int rc = tl_host::launched(what)) return rc;
             }
         }
     }
-    return 0;
+    return TL_OK;
 }
 
 }  // namespace
@@ -445,16 +446,13 @@ int tl_svola_fwd(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, c
     const int rc = make_plan("tl_svola_fwd", g, r0, r1, c0, c1, pl);
     if (rc) return rc;
     if (!wr || !wc || !image || !psfs || !out) return tl_host::fail(TL_EINVAL, "tl_svola_fwd: wr, wc, image, psfs or out is NULL");
-    hipError_t e = hipSetDevice(g->device);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    if (const int rc = tl_host::use_device(g->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo q = make_geo(g);
-    const int herr = for_chunks(pl.rows, pl.cols, g->B, g->C, [&](const Tiles &tl, int, int, int nr, int nc, int b0, int nb) {
+    return for_chunks(pl.rows, pl.cols, g->B, g->C, "svola_fwd_kernel launch",
+                      [&](const Tiles &tl, int, int, int nr, int nc, int b0, int nb) {
         hipLaunchKernelGGL(svola_fwd_kernel, dim3(nc, nr, nb * g->C), dim3(kBlock), 0, st, q, tl, wr, wc, image, psfs, out, b0);
-        return (int)hipGetLastError();
     });
-    if (herr) return tl_host::hip_fail(herr, "svola_fwd_kernel launch");
-    return TL_OK;
 }
 
 int tl_svola_bwd_psf(const tl_svola_geom *g, const int32_t *r0, const int32_t *r1, const int32_t *c0, const int32_t *c1,
@@ -462,23 +460,22 @@ int tl_svola_bwd_psf(const tl_svola_geom *g, const int32_t *r0, const int32_t *r
                      void *workspace, size_t workspace_bytes, void *stream)
 {
     Plan pl;
-    const int rc = make_plan("tl_svola_bwd_psf", g, r0, r1, c0, c1, pl);
+    int rc = make_plan("tl_svola_bwd_psf", g, r0, r1, c0, c1, pl);
     if (rc) return rc;
     if (!wr || !wc || !image || !g_out || !g_psfs)
         return tl_host::fail(TL_EINVAL, "tl_svola_bwd_psf: wr, wc, image, g_out or g_psfs is NULL");
     if (!workspace || workspace_bytes < pl.psf_bytes) return tl_host::fail(TL_EWORKSPACE, "workspace too small for tl_svola_bwd_psf");
-    hipError_t e = hipSetDevice(g->device);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    if ((rc = tl_host::use_device(g->device))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo q = make_geo(g);
     float *part = (float *)workspace;
     const int slots = pl.slots_r * pl.slots_c;
-    int herr = for_chunks(pl.rows, pl.cols, g->B, g->C, [&](const Tiles &tl, int rb, int cb, int nr, int nc, int b0, int nb) {
+    rc = for_chunks(pl.rows, pl.cols, g->B, g->C, "svola_bwd_psf_kernel launch",
+                    [&](const Tiles &tl, int rb, int cb, int nr, int nc, int b0, int nb) {
         hipLaunchKernelGGL(svola_bwd_psf_kernel, dim3(nc, nr, nb * g->C), dim3(kBlock), 0, st, q, tl, pl.ps, wr, wc, image, g_out,
                            part, b0, rb, cb, pl.slots_c, slots);
-        return (int)hipGetLastError();
     });
-    if (herr) return tl_host::hip_fail(herr, "svola_bwd_psf_kernel launch");
+    if (rc) return rc;
     const int ntaps = g->kh * g->kw, N = g->gh * g->gw;
     const int bmax = std::max(1, kMaxZ / g->C);
     for (int bp0 = 0; bp0 < g->psf_batch; bp0 += bmax) {            // (a lens of the batch per z only when psfs are per lens)
@@ -486,8 +483,7 @@ int tl_svola_bwd_psf(const tl_svola_geom *g, const int32_t *r0, const int32_t *r
         hipLaunchKernelGGL(svola_psf_reduce_kernel, dim3((ntaps + 63) / 64, N, nb * g->C), dim3(64), 0, st, q, pl.ps,
                            (const float *)part + (size_t)bp0 * g->C * N * slots * ntaps,
                            g_psfs + (int64_t)bp0 * g->g_psfs_stride[0], pl.slots_c, slots);
-        herr = (int)hipGetLastError();
-        if (herr) return tl_host::hip_fail(herr, "svola_psf_reduce_kernel launch");
+        if ((rc = tl_host::launched("svola_psf_reduce_kernel launch"))) return rc;
     }
     return TL_OK;
 }
@@ -497,28 +493,25 @@ int tl_svola_bwd_image(const tl_svola_geom *g, const int32_t *r0, const int32_t 
                        void *workspace, size_t workspace_bytes, void *stream)
 {
     Plan pl;
-    const int rc = make_plan("tl_svola_bwd_image", g, r0, r1, c0, c1, pl);
+    int rc = make_plan("tl_svola_bwd_image", g, r0, r1, c0, c1, pl);
     if (rc) return rc;
     if (!wr || !wc || !psfs || !g_out || !g_image)
         return tl_host::fail(TL_EINVAL, "tl_svola_bwd_image: wr, wc, psfs, g_out or g_image is NULL");
     if (!workspace || workspace_bytes < pl.ext_bytes) return tl_host::fail(TL_EWORKSPACE, "workspace too small for tl_svola_bwd_image");
-    hipError_t e = hipSetDevice(g->device);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    if ((rc = tl_host::use_device(g->device))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo q = make_geo(g);
     float *ext = (float *)workspace;
-    int herr = for_chunks(pl.erows, pl.ecols, g->B, g->C, [&](const Tiles &tl, int, int, int nr, int nc, int b0, int nb) {
+    rc = for_chunks(pl.erows, pl.ecols, g->B, g->C, "svola_bwd_image_kernel launch",
+                    [&](const Tiles &tl, int, int, int nr, int nc, int b0, int nb) {
         hipLaunchKernelGGL(svola_bwd_image_kernel, dim3(nc, nr, nb * g->C), dim3(kBlock), 0, st, q, tl, wr, wc, psfs, g_out, ext, b0);
-        return (int)hipGetLastError();
     });
-    if (herr) return tl_host::hip_fail(herr, "svola_bwd_image_kernel launch");
+    if (rc) return rc;
     const size_t total = (size_t)g->B * g->H * g->W * g->C;
     const size_t blocks = (total + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffffu) return tl_host::fail(TL_EINVAL, "tl_svola_bwd_image: the image has too many elements");
     hipLaunchKernelGGL(svola_fold_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, q, (const float *)ext, g_image, total);
-    herr = (int)hipGetLastError();
-    if (herr) return tl_host::hip_fail(herr, "svola_fold_kernel launch");
-    return TL_OK;
+    return tl_host::launched("svola_fold_kernel launch");
 }
 
 }  // extern "C"

@@ -440,15 +440,13 @@ int tl_warp_fwd(const tl_warp_geom *g, const float *image, const float *x, const
     if (!image) return tl_host::fail(TL_EINVAL, "tl_warp_fwd: image is NULL");
     if (!x || !y) return tl_host::fail(TL_EINVAL, "tl_warp_fwd: x or y is NULL");
     if (!out) return tl_host::fail(TL_EINVAL, "tl_warp_fwd: out is NULL");
-    hipError_t e = hipSetDevice(g->device);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    if (const int rc = tl_host::use_device(g->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo q = make_geo(g);
     const unsigned blocks = (unsigned)(((int64_t)g->Ho * g->Wo + kBlock - 1) / kBlock);
     for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
         hipLaunchKernelGGL(warp_fwd_kernel, dim3(blocks, std::min(kMaxY, g->B - b0)), dim3(kBlock), 0, st, q, image, x, y, gain, out, b0);
-        const int herr = (int)hipGetLastError();
-        if (herr) return tl_host::hip_fail(herr, "warp_fwd_kernel launch");
+        if (const int rc = tl_host::launched("warp_fwd_kernel launch")) return rc;
     }
     return TL_OK;
 }
@@ -464,23 +462,19 @@ int tl_warp_bwd(const tl_warp_geom *g, const float *image, const float *x, const
     if ((g_x == nullptr) != (g_y == nullptr)) return tl_host::fail(TL_EINVAL, "tl_warp_bwd: g_x and g_y go together, one of them is NULL");
     if (!g_x && !g_gain) return tl_host::fail(TL_EINVAL, "tl_warp_bwd: g_x, g_y and g_gain are all NULL: nothing to compute");
     if (g_gain && !gain) return tl_host::fail(TL_EINVAL, "tl_warp_bwd: g_gain is asked for but gain is NULL");
-    hipError_t e = hipSetDevice(g->device);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    if (const int rc = tl_host::use_device(g->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo q = make_geo(g);
     const unsigned blocks = (unsigned)(((int64_t)g->Ho * g->Wo + kBlock - 1) / kBlock);
     const bool in_lane = g->B > 1 && ((g_x && g->coord_batch == 1) || (g_gain && g->gain_batch == 1));
     if (in_lane) {                                  // something is shared by the batch: the lane sums over the lenses
         hipLaunchKernelGGL(warp_bwd_kernel, dim3(blocks, 1), dim3(kBlock), 0, st, q, image, x, y, gain, g_out, g_x, g_y, g_gain, 0, g->B);
-        const int herr = (int)hipGetLastError();
-        if (herr) return tl_host::hip_fail(herr, "warp_bwd_kernel launch");
-        return TL_OK;
+        return tl_host::launched("warp_bwd_kernel launch");
     }
     for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
         hipLaunchKernelGGL(warp_bwd_kernel, dim3(blocks, std::min(kMaxY, g->B - b0)), dim3(kBlock), 0, st, q, image, x, y, gain, g_out,
                            g_x, g_y, g_gain, b0, 1);
-        const int herr = (int)hipGetLastError();
-        if (herr) return tl_host::hip_fail(herr, "warp_bwd_kernel launch");
+        if (const int rc = tl_host::launched("warp_bwd_kernel launch")) return rc;
     }
     return TL_OK;
 }
@@ -511,8 +505,7 @@ int tl_warp_bwd_image(const tl_warp_geom *g, const float *x, const float *y, con
         snprintf(msg, sizeof(msg), "tl_warp_bwd_image: work_bytes is %zu, tl_warp_bwd_image_work_bytes asks for %zu", work_bytes, need);
         return tl_host::fail(TL_EINVAL, msg);
     }
-    hipError_t e = hipSetDevice(g->device);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipSetDevice");
+    if (const int rc = tl_host::use_device(g->device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo q = make_geo(g);
     unsigned *m = (unsigned *)work;
@@ -521,27 +514,21 @@ int tl_warp_bwd_image(const tl_warp_geom *g, const float *x, const float *y, con
     const int64_t pixels = (int64_t)g->Ho * g->Wo;
     int Hb = 0;                                          // ceil(log2(16 Ho Wo)), in integers
     while (((int64_t)1 << Hb) < 16 * pixels) ++Hb;
-    e = hipMemsetAsync(work, 0, need, st);
+    const hipError_t e = hipMemsetAsync(work, 0, need, st);
     if (e != hipSuccess) return tl_host::hip_fail(e, "hipMemsetAsync of the warp image workspace");
     const unsigned tiles = (unsigned)((g->Wo + kTileX - 1) / kTileX) * (unsigned)((g->Ho + kTileY - 1) / kTileY);
-    {
-        const int64_t all = (int64_t)g->B * pixels;                   // <= 2^31 2^26
-        const unsigned mblocks = (unsigned)std::min<int64_t>((all + kBlock - 1) / kBlock, 2048);
-        hipLaunchKernelGGL(warp_image_max_kernel, dim3(mblocks), dim3(kBlock), 0, st, q, gain, g_out, m, all);
-        const int herr = (int)hipGetLastError();
-        if (herr) return tl_host::hip_fail(herr, "warp_image_max_kernel launch");
-    }
+    const int64_t all = (int64_t)g->B * pixels;                       // <= 2^31 2^26
+    const unsigned mblocks = (unsigned)std::min<int64_t>((all + kBlock - 1) / kBlock, 2048);
+    hipLaunchKernelGGL(warp_image_max_kernel, dim3(mblocks), dim3(kBlock), 0, st, q, gain, g_out, m, all);
+    if (const int rc = tl_host::launched("warp_image_max_kernel launch")) return rc;
     for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
         hipLaunchKernelGGL(warp_image_scatter_kernel, dim3(tiles, std::min(kMaxY, g->B - b0)), dim3(kBlock), 0, st, q, x, y, gain, g_out,
                            m, acc, marks, Hb, flags & 1, b0);
-        const int herr = (int)hipGetLastError();
-        if (herr) return tl_host::hip_fail(herr, "warp_image_scatter_kernel launch");
+        if (const int rc = tl_host::launched("warp_image_scatter_kernel launch")) return rc;
     }
     const unsigned fblocks = (unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)1 << 20);
     hipLaunchKernelGGL(warp_image_final_kernel, dim3(fblocks), dim3(kBlock), 0, st, q, m, acc, marks, g_image, Hb, n);
-    const int herr = (int)hipGetLastError();
-    if (herr) return tl_host::hip_fail(herr, "warp_image_final_kernel launch");
-    return TL_OK;
+    return tl_host::launched("warp_image_final_kernel launch");
 }
 
 }  // extern "C"

@@ -475,6 +475,39 @@ class SpotMomentsFunction(torch.autograd.Function):
 PSF_MAX_BINS = 32          # rows / columns of the half kernel tl_psf_accumulate takes (one 32x32 MFMA tile)
 
 
+def _psf_float32(**tensors):
+    """The device and dtype check of the fused PSF's tensor arguments, in the order given."""
+    for name, ten in tensors.items():
+        _require_device(ten, name)
+        if ten.dtype != torch.float32:
+            raise RuntimeError(f"torchoptics_amd: the fused PSF takes float32 tensors; `{name}` is {ten.dtype} "
+                               "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+
+
+def _psf_rays(x, y, weight):
+    """x, y [.., W, R] and the weights as tl_psf_accumulate and tl_psf_rot_accumulate take them: (x, y, wf, wb), rays
+    contiguous and one set of strides for all.  A strided view of x goes through in place, an expanded one is copied; y and
+    the weights are copied only where their strides differ from x's.  wf: float weights, wb: ok bytes, at most one of them."""
+    dev = x.device
+    if x.stride(2) != 1 or any(s == 0 for s in x.stride()[:2]):
+        x = x.contiguous()
+    if y.stride() != x.stride():
+        y = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev).copy_(y)
+    if weight is None:
+        return x, y, None, None
+    _require_device(weight, "weight")
+    as_bytes = weight.dtype in (torch.bool, torch.uint8)
+    if as_bytes:
+        wt = weight.view(torch.uint8) if weight.dtype == torch.bool else weight
+    else:
+        wt = weight.detach().to(torch.float32)
+    if wt.shape != x.shape:
+        raise ValueError("the fused PSF: weights must have the shape of x")
+    if wt.stride() != x.stride():
+        wt = torch.empty_strided(x.shape, x.stride(), dtype=wt.dtype, device=dev).copy_(wt)
+    return (x, y, None, wt) if as_bytes else (x, y, wt, None)
+
+
 class PsfAccumulateFunction(torch.autograd.Function):
     """hist [G,W,ny,nxh] = sum_r wt_r Gy_i(r) Gx_j(r): the un-mirrored, un-normalised half kernel of the soft-histogram PSF
     (tl_psf_accumulate / tl_psf_accumulate_bwd; metrics.compute_psf(fused=True)).
@@ -486,32 +519,12 @@ class PsfAccumulateFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, weight, x_pitch, y_pitch, y_centre, nxh, ny, x_first, y_first):
-        for name, ten in (("x", x), ("y", y), ("x_pitch", x_pitch), ("y_pitch", y_pitch), ("y_centre", y_centre)):
-            _require_device(ten, name)
-            if ten.dtype != torch.float32:
-                raise RuntimeError(f"torchoptics_amd: the fused PSF takes float32 tensors; `{name}` is {ten.dtype} "
-                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        _psf_float32(x=x, y=y, x_pitch=x_pitch, y_pitch=y_pitch, y_centre=y_centre)
         if not (1 <= nxh <= PSF_MAX_BINS and 1 <= ny <= PSF_MAX_BINS):
             raise ValueError(f"the fused PSF takes 1..{PSF_MAX_BINS} bins per axis of the half kernel (got {ny} x {nxh})")
         dev = x.device
         G, W, R = x.shape
-        if x.stride(2) != 1 or any(s == 0 for s in x.stride()[:2]):
-            x = x.contiguous()
-        if y.stride() != x.stride():
-            y = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev).copy_(y)
-        wf = wb = None
-        if weight is not None:
-            _require_device(weight, "weight")
-            if weight.dtype in (torch.bool, torch.uint8):
-                wb = weight.view(torch.uint8) if weight.dtype == torch.bool else weight
-            else:
-                wf = weight.detach().to(torch.float32)
-            wt = wb if wb is not None else wf
-            if wt.shape != x.shape:
-                raise ValueError("the fused PSF: weights must have the shape of x")
-            if wt.stride() != x.stride():
-                wt = torch.empty_strided(x.shape, x.stride(), dtype=wt.dtype, device=dev).copy_(wt)
-            wf, wb = (None, wt) if wb is not None else (wt, None)
+        x, y, wf, wb = _psf_rays(x, y, weight)
         xp, yp, yc = (a.detach().reshape(G).contiguous() for a in (x_pitch, y_pitch, y_centre))
         nbytes = _lib.lib().tl_psf_workspace_bytes(G, W, R, nxh, ny)
         ws = _workspace(nbytes, dev)
@@ -583,11 +596,7 @@ class PsfRotAccumulateFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, weight, grid, x_pitch, y_pitch, y_centre, nx, ny, x_first, y_first):
-        for name, ten in (("x", x), ("y", y), ("y_centre", y_centre)):
-            _require_device(ten, name)
-            if ten.dtype != torch.float32:
-                raise RuntimeError(f"torchoptics_amd: the fused PSF takes float32 tensors; `{name}` is {ten.dtype} "
-                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        _psf_float32(x=x, y=y, y_centre=y_centre)
         if not (1 <= nx <= PSF_MAX_BINS and 1 <= ny <= PSF_MAX_BINS):
             raise ValueError(f"the fused PSF takes 1..{PSF_MAX_BINS} bins per axis (got {ny} x {nx})")
         dev = x.device
@@ -597,23 +606,7 @@ class PsfRotAccumulateFunction(torch.autograd.Function):
             raise ValueError(f"the fused PSF grid was laid out for {grid.K} source fans, x holds {K}")
         if G * W > PSF_ROT_MAX_ROWS or K * W > PSF_ROT_MAX_ROWS:
             raise ValueError(f"the fused PSF grid takes at most {PSF_ROT_MAX_ROWS} (grid, channel) rows, got {G} x {W}")
-        if x.stride(2) != 1 or any(s == 0 for s in x.stride()[:2]):
-            x = x.contiguous()
-        if y.stride() != x.stride():
-            y = torch.empty_strided(x.shape, x.stride(), dtype=torch.float32, device=dev).copy_(y)
-        wf = wb = None
-        if weight is not None:
-            _require_device(weight, "weight")
-            if weight.dtype in (torch.bool, torch.uint8):
-                wb = weight.view(torch.uint8) if weight.dtype == torch.bool else weight
-            else:
-                wf = weight.detach().to(torch.float32)
-            wt = wb if wb is not None else wf
-            if wt.shape != x.shape:
-                raise ValueError("the fused PSF: weights must have the shape of x")
-            if wt.stride() != x.stride():
-                wt = torch.empty_strided(x.shape, x.stride(), dtype=wt.dtype, device=dev).copy_(wt)
-            wf, wb = (None, wt) if wb is not None else (wt, None)
+        x, y, wf, wb = _psf_rays(x, y, weight)
         pitch = lambda p: (p.detach().to(device=dev, dtype=torch.float32).reshape(G).contiguous() if torch.is_tensor(p)  # noqa: E731
                            else torch.full((G,), float(p), dtype=torch.float32, device=dev))
         xp, yp = pitch(x_pitch), pitch(y_pitch)
