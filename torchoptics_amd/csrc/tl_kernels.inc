@@ -1420,7 +1420,8 @@ __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
         a.cz = -b_dist * dist * inv_cz;
         if (PEN && !alive) { a.x = a.y = a.z = a.cx = a.cy = a.cz = 0.0f; }
         if (gopd) {
-            const float v = wave_sum_f32(go * dist);
+            // a select, not go * dist with go = 0: a dead lane's dist may be NaN (LEAN re-trace), and 0 * NaN is NaN
+            const float v = wave_sum_f32(alive ? go * dist : 0.0f);
             if ((tid & 63) == 0) sgn[S][tid >> 6] += v;
         }
         // ---- reverse sweep (dead lanes carry garbage, masked where it leaves the lane)
@@ -1456,7 +1457,7 @@ __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
                 }
                 if (PEN && !lk) { a.x = a.y = a.z = a.cx = a.cy = a.cz = 0.0f; }     // parked after k: nothing flows below
                 if (gopd) {
-                    const float v = wave_sum_f32(go * d_k);
+                    const float v = wave_sum_f32(alive ? go * d_k : 0.0f);     // (spherical and aspheric rows alike)
                     if ((tid & 63) == 0) sgn[k][tid >> 6] += v;
                 }
                 if (lk) {
@@ -2392,7 +2393,22 @@ static int launch_fwd(const tl_problem &p, const tl_rays &o, const tl_part &w, h
     else if (p.aggregate) TL_FWD(true, false, false);
     else if (asph && wopd) TL_FWD(false, true, true);
     else if (asph) TL_FWD(false, true, false);
+#if TL_FAST
+    else if (wopd) {
+        // All-spherical lens, fast mode: the ray outputs, flags and moments come from the kernel that a trace without OPD
+        // runs, so that asking for the OPD changes no bit of them (contraction fuses the two kernel bodies into different
+        // multiply-adds: up to 3e-6 mm in x, y otherwise); trace_fwd_kernel then writes the OPD alone.  Both decide `ok`
+        // for themselves.  (An optional path, not tuned: one more forward launch.)
+        hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part, w.R);
+        tl_problem q = p;
+        q.cond_flags = nullptr;
+        hipLaunchKernelGGL((trace_fwd_kernel<false, false, true>), grid, block, 0, st, q, (float *)nullptr, (float *)nullptr,
+                           (float *)nullptr, (float *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, o.opd, (float *)nullptr,
+                           (double *)nullptr, w.R);
+    }
+#else
     else if (wopd) TL_FWD(false, false, true);
+#endif
 #if TL_FAST
     // two rays per lane: -10 % in fast mode (latency-bound chains), +4 % in strict mode (issue-bound, fewer waves)
     else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part, w.R);
