@@ -904,6 +904,10 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
     float *__restrict__ ocy, uint8_t *__restrict__ ook, uint8_t *__restrict__ oback,
     float *__restrict__ oopd, float *__restrict__ stk, double *__restrict__ part, const int /*plan hint, unused*/)
 {
+    // Fast mode, all-spherical lens: this instantiation only ever writes the path length behind trace_fwd_plain_kernel
+    // (launch_fwd), and `ook` then holds that kernel's ok bytes, to be read: under contraction the two bodies round
+    // differently, and a ray within rounding of a miss must not be dead in `ok` and carry a path length.
+    constexpr bool kOkIn = TL_FAST && OPD && !ASPH && !PEN;
     TL_LENS_ROW(pa);
     TL_BLOCK_CHUNKS(p.P);
     const int S = p.S;
@@ -1037,10 +1041,13 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
             if (has(2u, oy != nullptr)) oy[o] = yo;
             if (has(4u, ocx != nullptr)) ocx[o] = ray.cx;
             if (has(8u, ocy != nullptr)) ocy[o] = ray.cy;
-            if (has(16u, ook != nullptr)) ook[o] = ok ? 1 : 0;
+            if (!kOkIn && has(16u, ook != nullptr)) ook[o] = ok ? 1 : 0;
             if (has(32u, oback != nullptr)) oback[o] = back ? 1 : 0;
             if (has(64u, p.cond_flags != nullptr)) p.cond_flags[o] = alive ? (min_cos2 < kCondThr ? 2 : 1) : 0;  // 2: the rays moment 9 counts
-            if (OPD && has(512u, oopd != nullptr)) oopd[o] = alive ? opd + uload(n_w, S) * dist : 0.0f;
+            // kOkIn: a ray that the kernel before this one gave up has no path length, whatever this one makes of it
+            // (a ray that only lost `ok` at the image plane, where backward rays are not allowed, keeps its own)
+            const bool path = (kOkIn && ook) ? alive && (ook[o] != 0 || (!allow_back && !ok)) : alive;
+            if (OPD && has(512u, oopd != nullptr)) oopd[o] = path ? opd + uload(n_w, S) * dist : 0.0f;
             if (has(128u, part != nullptr)) {
                 // (ok differs from alive only where backward rays are not allowed; the squares are exact in fp64)
                 const double yd = (double)yo, ykd = (double)(ok ? yo : 0.0f);
@@ -2397,14 +2404,14 @@ static int launch_fwd(const tl_problem &p, const tl_rays &o, const tl_part &w, h
     else if (wopd) {
         // All-spherical lens, fast mode: the ray outputs, flags and moments come from the kernel that a trace without OPD
         // runs, so that asking for the OPD changes no bit of them (contraction fuses the two kernel bodies into different
-        // multiply-adds: up to 3e-6 mm in x, y otherwise); trace_fwd_kernel then writes the OPD alone.  Both decide `ok`
-        // for themselves.  (An optional path, not tuned: one more forward launch.)
+        // multiply-adds: up to 3e-6 mm in x, y otherwise); trace_fwd_kernel then writes the OPD alone, and gives none to a ray
+        // that the first kernel's `ok` calls dead (kOkIn).  (An optional path, not tuned: one more forward launch.)
         hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part, w.R);
         tl_problem q = p;
         q.cond_flags = nullptr;
         hipLaunchKernelGGL((trace_fwd_kernel<false, false, true>), grid, block, 0, st, q, (float *)nullptr, (float *)nullptr,
-                           (float *)nullptr, (float *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, o.opd, (float *)nullptr,
-                           (double *)nullptr, w.R);
+                           (float *)nullptr, (float *)nullptr, o.ok /* read, not written */, (uint8_t *)nullptr, o.opd,
+                           (float *)nullptr, (double *)nullptr, w.R);
     }
 #else
     else if (wopd) TL_FWD(false, false, true);
