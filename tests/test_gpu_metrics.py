@@ -1,4 +1,5 @@
-"""Post-trace metrics (reference: unreachable TF text, parity unpinned) on the GPU: physical sanity."""
+"""Post-trace metrics (reference: unreachable TF text) on the GPU: physical sanity.  Their values and leaf gradients are
+held to the fp64 restatement of tests/metrics_ref.py by tests/test_gpu_metrics_matrix.py."""
 import numpy as np
 import pytest
 import torch

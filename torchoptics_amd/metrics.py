@@ -3,7 +3,9 @@ Image-quality metrics computed from a handful of traced rays: the step AFTER the
 
 In the reference these exist only as commented-out TensorFlow code (ray_tracing_lite.py:848-934;
 originals in ray_tracing.py:815-901) and are unreachable in its PyTorch port.  Written here from their
-stated intent on top of RayTracer.trace_rays (i.e. the HIP kernels); PARITY UNPINNED by the reference.
+stated intent on top of RayTracer.trace_rays (i.e. the HIP kernels).  The reference cannot pin them; distortion,
+relative illumination and the aiming error are held, values and leaf gradients, to the fp64 restatement of their
+definitions in tests/metrics_ref.py (cases and gates: tests/metrics_cases.py, tests/test_gpu_metrics_matrix.py).
 """
 from __future__ import annotations
 
@@ -18,10 +20,26 @@ def compute_distortion(specs, lens, relative_fields, default_device="cuda"):
 
     y_ref = EFL tan(field) corrected for the defocus of the image plane from the paraxial focus
     (last gap - BFL) along the traced chief-ray direction.  Field 0 gives 0/0 = NaN; pass fields > 0.
+
+    Accuracy: d is a difference of two heights that agree to 1e-5 .. 1e-1 of their size, so its error is ABSOLUTE, whatever
+    its value: measured 3.0e-7 at most from the fp64 restatement of this definition (tests/metrics_ref.py) in strict and
+    in fast mode, over singlet, doublet, Cooke triplet, Tessar, an aspheric double Gauss and a padded batch at 10 .. 25
+    degrees -- the fp32 evaluation of the same formulas on the CPU is 3.7e-7 off (profiles/metrics_accuracy.txt).  A
+    distortion of 1e-5 therefore carries about two digits, one of 1e-2 five.  EFL, BFL and y_ref come from the fp32 ABCD
+    product; nothing is gained by forming them in fp64 while y itself is an fp32 trace.
     """
     tr = RayTracer(mode='chief', n_rays=1, rel_fields=relative_fields, wavelengths=['d'], vig_fn=None,
                    default_device=default_device)
-    _, y, _, cy, *_ = tr.trace_rays(specs, lens)
+    # The chief ray's backward is the checkpoint kernel: with one ray per field the walk-back from the forward's outputs
+    # saves nothing, and d's gradient is a small difference of the gradients of y and y_ref, which amplifies the rounding
+    # of the walk-back's reconstructed states (strict mode, aspheric double Gauss: d/d poly 1.0e-5 rel-L2 from fp64 with
+    # the walk-back, 1.9e-6 with the checkpoint kernel; the choice is made at the forward and kept by its node).
+    algo = ops.get_backward_algorithm()
+    ops.set_backward_algorithm("checkpoint")
+    try:
+        _, y, _, cy, *_ = tr.trace_rays(specs, lens)
+    finally:
+        ops.set_backward_algorithm(algo)
     n_lens = len(specs)
     y, cy = y.reshape(n_lens, -1), cy.reshape(n_lens, -1)
     fields = torch.tensor(list(relative_fields), dtype=y.dtype, device=y.device)
