@@ -562,6 +562,59 @@ int tl_warp_bwd_image(const tl_warp_geom *g, const float *x, const float *y, con
                       float *g_image, void *work, size_t work_bytes, int flags, void *stream);
 
 /*
+ * Structural similarity of two images per lens under a separable Gaussian window, and its gradients to both images
+ * (imaging.ssim(fused=True); additive entry points, ABI unchanged).  a, b [B,H,W,C] floats, addressed through element strides
+ * (b, y, x, c).  With w the K window weights (odd K, 3..11; the caller normalises them), the VALID window w (x) w, Hm = H - K + 1,
+ * Wm = W - K + 1 and, per map pixel and channel,
+ *     mu_a = w*a,  mu_b = w*b,  va = w*a^2 - mu_a^2,  vb = w*b^2 - mu_b^2,  cab = w*ab - mu_a mu_b,
+ *     S = (2 mu_a mu_b + C1)(2 cab + C2) / ((mu_a^2 + mu_b^2 + C1)(va + vb + C2)),
+ *     value[b] = the mean of S over Hm x Wm x C                                              value [B] floats, contiguous.
+ * The gradient of sum_b g_value[b] value[b] to an image p (a or b; q is the other one) is
+ *     g_p[b,y,x,c] = g_value[b] / (Hm Wm C) sum_{i,j} w_i w_j (dm + 2 p[b,y,x,c] ds + q[b,y,x,c] dc)[b, y - i, x - j, c]
+ * over the map pixels that exist, with the partial maps  ds = dS/d va (= dS/d vb),  dc = dS/d cab,
+ * dm_p = dS/d mu_p - 2 mu_p ds - mu_q dc (the derivative to the window mean with the raw second moments held fixed).
+ * The maps are dense channels-last [B,Hm,Wm,C] floats of tl_ssim_maps_elems(g) elements each, stored unscaled: the
+ * forward does not depend on g_value.
+ *   tl_ssim_fwd   value, and the maps that `flags` asks for: bit 0 dm_a and ds_a, bit 1 dm_b and ds_b, dc with either bit; a
+ *                 map that is not asked for may be NULL and is not written.  One workgroup per tile of 32 x 16 map pixels and
+ *                 lens stages the tile plus halo of both images in LDS (whole row spans across the channels, in chunks of four
+ *                 channels: C has no upper limit), runs the window along the rows and then down the columns over the five
+ *                 products and writes ONE fp64 partial sum per (lens, tile) into `work`; a second kernel adds the tiles of a
+ *                 lens in fp64 in a fixed order.  Before squaring, each tile subtracts its own first pixel (per image and
+ *                 channel) and adds it back to the means: the variances are shift invariant, and the fp32 cancellation of
+ *                 w*a^2 - mu_a^2 against C2 shrinks with the tile's contrast instead of its brightness.
+ *   tl_ssim_bwd   g_p for ONE image, called once per image that needs a gradient with the roles set by the caller: p and q
+ *                 are read through a_stride and b_stride, g_p is written through g_stride, (dm, ds) are the maps of p.  One
+ *                 workgroup per tile of 32 x 16 image pixels gathers the three maps over the tile plus halo (zero outside the
+ *                 map).  No workspace.
+ * No atomics anywhere: both calls give the same bits on every run.  `work`: tl_ssim_work_bytes(g) bytes (0 for a geometry
+ * that is refused), aligned to 8; it holds nothing afterwards.  C is not a grid dimension; B is cut into launches of 65535
+ * lenses.  No host synchronisation, no allocation; the launches go on `stream`.
+ * TL_EINVAL before any HIP call, with the function's name and the argument in the message: a required pointer NULL, a size
+ * below 1, K even, below 3 or above 11, H or W below K or above 2^20 (or more than 2^22 tiles of 16 x 32 pixels in the
+ * image), unknown flag bits, a map that the flags ask for but that is NULL, and a workspace that is NULL, misaligned or
+ * too small.
+ */
+typedef struct tl_ssim_geom {
+    int32_t device;
+    int32_t B, H, W, C;               /* a, b [B,H,W,C] */
+    int32_t K;                        /* window taps per axis: odd, 3..11 */
+    float window[11];                 /* the first K are read */
+    float C1, C2;                     /* (k1 L)^2, (k2 L)^2 */
+    int32_t flags;                    /* tl_ssim_fwd: bit 0 the maps of a, bit 1 the maps of b are wanted */
+    int64_t a_stride[4];              /* elements: b, y, x, c; of p in tl_ssim_bwd */
+    int64_t b_stride[4];              /* of q in tl_ssim_bwd */
+    int64_t g_stride[4];              /* of g_p (tl_ssim_bwd) */
+} tl_ssim_geom;
+
+size_t tl_ssim_work_bytes(const tl_ssim_geom *g);
+size_t tl_ssim_maps_elems(const tl_ssim_geom *g);
+int tl_ssim_fwd(const tl_ssim_geom *g, const float *a, const float *b, float *value, float *dm_a, float *ds_a, float *dm_b,
+                float *ds_b, float *dc, void *work, size_t work_bytes, void *stream);
+int tl_ssim_bwd(const tl_ssim_geom *g, const float *p, const float *q, const float *dm, const float *ds, const float *dc,
+                const float *g_value, float *g_p, void *stream);
+
+/*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of
  * `mode` use.  Strict mode promises the correctly rounded (IEEE) results on the operand ranges of the trace, from shorter
  * instruction sequences than the compiler's general ones: tests/test_gpu_arith.py holds it to that, bit for bit.

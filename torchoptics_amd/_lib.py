@@ -84,6 +84,12 @@ class tl_warp_geom(C.Structure):
                 ("g_gain_stride", C.c_int64 * 4)]
 
 
+class tl_ssim_geom(C.Structure):
+    _fields_ = [("device", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("K", C.c_int32), ("window", C.c_float * 11), ("C1", C.c_float), ("C2", C.c_float), ("flags", C.c_int32),
+                ("a_stride", C.c_int64 * 4), ("b_stride", C.c_int64 * 4), ("g_stride", C.c_int64 * 4)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -136,6 +142,12 @@ _SIGNATURES = {
     # geom | x, y, gain | g_out | g_image | work, work_bytes | flags (bit 0: direct atomics, no LDS box) | stream
     "tl_warp_bwd_image_work_bytes": (C.c_size_t, [C.POINTER(tl_warp_geom)]),
     "tl_warp_bwd_image": (C.c_int, [C.POINTER(tl_warp_geom)] + [_VP] * 3 + [_VP] + [_VP] + [_VP, C.c_size_t] + [C.c_int] + [_VP]),
+    "tl_ssim_work_bytes": (C.c_size_t, [C.POINTER(tl_ssim_geom)]),
+    "tl_ssim_maps_elems": (C.c_size_t, [C.POINTER(tl_ssim_geom)]),
+    # geom | a, b | value | dm_a, ds_a, dm_b, ds_b, dc | work, work_bytes | stream
+    "tl_ssim_fwd": (C.c_int, [C.POINTER(tl_ssim_geom)] + [_VP] * 2 + [_VP] + [_VP] * 5 + [_VP, C.c_size_t] + [_VP]),
+    # geom | p, q | dm, ds, dc | g_value | g_p | stream
+    "tl_ssim_bwd": (C.c_int, [C.POINTER(tl_ssim_geom)] + [_VP] * 2 + [_VP] * 3 + [_VP] + [_VP] + [_VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -43,6 +43,7 @@ UNITS = {
     "tl_psf.hip": [],          # the PSF soft histogram (fp32 MFMA forward, per-ray backward)
     "tl_svola.hip": [],        # the spatially varying PSF convolution of an image and its adjoints
     "tl_warp.hip": [],         # the bicubic image warp (distortion, relative illumination) and its coordinate / gain gradients
+    "tl_ssim.hip": [],         # the SSIM of two images under a Gaussian window and its gradients to both
 }
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 

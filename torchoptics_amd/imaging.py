@@ -3,7 +3,9 @@ Rendering an image through the lens.  First, the spatially varying overlap-add c
 reference's `svola_convolution`, image_ops.py:6-98, which cannot run as written: `fft` is undefined, `F.pad(mode='symmetric')`
 and `torch.nn.functional.resize_with_crop_or_pad` do not exist in torch, and it transforms over (C, H) instead of (H, W)).
 
-The definition implemented here is the evident intent of that text; see `svola_convolution`.
+The definition implemented here is the evident intent of that text; see `svola_convolution`.  Behind it: the PSF grid over the
+image, the bicubic warp for distortion and relative illumination, and the metrics the reference's renderer reports on the
+result, `ssim` and `psnr`.
 """
 import ctypes as C
 import functools
@@ -507,3 +509,98 @@ def distortion_grid(d, fields, out_size, aspect=None):
     D = radial_map(d, fields, out_size, 0.0, aspect)[..., 0]
     xn, yn, _ = _pixel_axes(out_size, aspect, d.dtype, d.device)
     return xn[None, None, :] / (1 + D), yn[None, :, None] / (1 + D)
+
+
+def ssim_window(filter_size, filter_sigma, dtype=torch.float64):
+    """The 1-D Gaussian window of ssim: w[i] ~ exp(-(i - (K - 1)/2)^2 / (2 sigma^2)), normalised to sum 1 in float64 and rounded
+    once to `dtype` (a CPU tensor of K weights).  The 2-D window is its outer product with itself."""
+    K = int(filter_size)
+    i = np.arange(K, dtype=np.float64) - (K - 1) / 2.0
+    w = np.exp(-(i * i) / (2.0 * float(filter_sigma) ** 2))
+    return torch.from_numpy(w / w.sum()).to(dtype)
+
+
+def _ssim_torch(a, b, max_value, filter_size, filter_sigma, k1, k2):
+    """The definition of ssim in plain torch ops (any device, any float dtype; autograd does the rest): two 1-D grouped
+    conv2d calls per moment.  Returns (ssim [B], S [B, Hm, Wm, C]).
+
+    The moments are taken about each image's own mean per lens and channel (a constant to autograd), which is added back to
+    the window means: variances and covariance are shift invariant, and without the shift w*a^2 - mu_a^2 subtracts two numbers
+    of size mu^2 to get one of size C2 -- on two nearly equal flat images that costs even float64 four digits of the gradient."""
+    Cc = a.shape[3]
+    w = ssim_window(filter_size, filter_sigma, a.dtype).to(a.device)
+    w_row = w.reshape(1, 1, 1, -1).expand(Cc, 1, 1, -1)
+    w_col = w.reshape(1, 1, -1, 1).expand(Cc, 1, -1, 1)
+    blur = lambda t: F.conv2d(F.conv2d(t, w_row, groups=Cc), w_col, groups=Cc)         # noqa: E731
+    x, y = a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)
+    x0, y0 = x.detach().mean(dim=(2, 3), keepdim=True), y.detach().mean(dim=(2, 3), keepdim=True)
+    x, y = x - x0, y - y0
+    m_a, m_b = blur(x), blur(y)
+    va, vb, cab = blur(x * x) - m_a * m_a, blur(y * y) - m_b * m_b, blur(x * y) - m_a * m_b
+    mu_a, mu_b = m_a + x0, m_b + y0
+    c1, c2 = (k1 * max_value) ** 2, (k2 * max_value) ** 2
+    S = ((2 * mu_a * mu_b + c1) * (2 * cab + c2)) / ((mu_a * mu_a + mu_b * mu_b + c1) * (va + vb + c2))
+    return S.mean(dim=(1, 2, 3)), S.permute(0, 2, 3, 1)
+
+
+def ssim(a, b, max_value=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, fused=None, return_map=False):
+    """The mean structural similarity of two images per lens (the reference scores its rendered image with `tf.image.ssim`,
+    optics_simulator_lite.py's commented-out apply_optics_model; the defaults are tf.image.ssim's).
+
+    a, b [B, H, W, C] of one shape.  Returns ssim [B]; with `return_map=True`, (ssim, S [B, Hm, Wm, C]).
+
+    The 1-D window is w[i] ~ exp(-(i - (K - 1)/2)^2 / (2 sigma^2)), K = filter_size, normalised to sum 1 in float64 and rounded
+    once to the working precision; the 2-D window is its outer product and the convolution is VALID, so the map has
+    Hm = H - K + 1 rows and Wm = W - K + 1 columns.  With L = max_value, C1 = (k1 L)^2, C2 = (k2 L)^2:
+        mu_a = w*a,  mu_b = w*b,  va = w*a^2 - mu_a^2,  vb = w*b^2 - mu_b^2,  cab = w*ab - mu_a mu_b
+        S = (2 mu_a mu_b + C1)(2 cab + C2) / ((mu_a^2 + mu_b^2 + C1)(va + vb + C2)),   ssim[b] = mean of S over Hm x Wm x C.
+
+    `fused=False`: the definition in plain torch ops -- any device, any float dtype, autograd does the rest.  `fused=True`: the
+    HIP kernels of csrc/tl_ssim.hip (ops.SsimFunction): float32 tensors on one GPU, filter_size odd in 3..11, no map; one launch
+    (plus a tiny reduction) forward and one launch backward per image that needs a gradient, no atomics, the same bits on every
+    run; it keeps 4 bytes per map element per stored partial map (three maps for one gradient, five for both).  Anything else
+    raises a ValueError that names the reason (there is no CPU fallback).  `fused=None` (default): the kernels when they
+    apply, torch otherwise.  Both paths take the second moments about a constant (the torch path about each image's mean, the
+    kernels about each tile's first pixel) and add it back to the means: the fp32 variances then lose digits with the local
+    contrast, not with the brightness."""
+    if a.dim() != 4 or b.dim() != 4:
+        raise ValueError(f"ssim: a and b must be [B, H, W, C], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape != b.shape:
+        raise ValueError(f"ssim: a and b must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    K = int(filter_size)
+    B, H, W, Cc = a.shape
+    if K < 1 or min(B, Cc) < 1:
+        raise ValueError(f"ssim: filter_size and every size must be at least 1, got filter_size {K} and {tuple(a.shape)}")
+    if H < K or W < K:
+        raise ValueError(f"ssim: H and W must be at least filter_size = {K} (the window is valid only), got {H} x {W}")
+    why_not = None
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        why_not = f"dtype: a is {a.dtype}, b is {b.dtype}; the kernels are float32"
+    elif not a.is_cuda or b.device != a.device:
+        why_not = f"device: a is on {a.device}, b on {b.device}; the kernels run on one AMD GPU (there is no CPU fallback)"
+    elif K % 2 == 0 or K < 3 or K > ops.SSIM_MAX_TAPS:
+        why_not = f"K: filter_size must be odd, 3 <= filter_size <= {ops.SSIM_MAX_TAPS}, got {K}"
+    elif max(H, W) > 1 << 20 or ((H + 15) // 16) * ((W + 31) // 32) > 1 << 22:
+        why_not = f"size: {H} x {W} pixels are more than the kernels tile"
+    if fused is None:
+        fused = why_not is None and not return_map
+    if not fused:
+        value, S = _ssim_torch(a, b, float(max_value), K, float(filter_sigma), float(k1), float(k2))
+        return (value, S) if return_map else value
+    if return_map:
+        raise ValueError("ssim(fused=True, return_map=True): the kernels do not keep the map S; use fused=False")
+    if why_not is not None:
+        raise ValueError(f"ssim(fused=True) does not apply -- {why_not}: use fused=False")
+    window = tuple(float(v) for v in ssim_window(K, filter_sigma, torch.float32))
+    c1, c2 = (float(k1) * float(max_value)) ** 2, (float(k2) * float(max_value)) ** 2
+    return ops.SsimFunction.apply(a, b, window, c1, c2)
+
+
+def psnr(a, b, max_value=1.0):
+    """The peak signal-to-noise ratio per image, 10 log10(L^2 / mse) with mse the mean of (a - b)^2 over everything but the
+    first axis and L = max_value (the other half of the reference's pair, `tf.image.psnr`).  a, b [B, ...] of one shape;
+    returns [B].  Plain torch ops."""
+    if a.shape != b.shape or a.dim() < 2:
+        raise ValueError(f"psnr: a and b must have one shape [B, ...], got {tuple(a.shape)} and {tuple(b.shape)}")
+    mse = ((a - b) ** 2).reshape(a.shape[0], -1).mean(dim=1)
+    return 10.0 * torch.log10(float(max_value) ** 2 / mse)

@@ -816,6 +816,79 @@ class WarpFunction(torch.autograd.Function):
         return (g_image, g_x if need_x else None, g_y if need_y else None, g_gain) + none
 
 
+SSIM_MAX_TAPS = 11        # the window of the tl_ssim_* kernels: odd, 3 .. 11 taps per axis
+
+# C-ABI calls of SsimFunction since import (tests: the backward runs once per image that needs a gradient), and the pointers
+# the last forward handed to the kernel (strided views go through as they are: no copy)
+_ssim_calls = {"fwd": 0, "bwd": 0, "a_ptr": None, "b_ptr": None}
+
+
+def ssim_counts() -> dict:
+    """{'fwd': n, 'bwd': n, 'a_ptr', 'b_ptr': data pointers of the last forward's images}."""
+    return dict(_ssim_calls)
+
+
+class SsimFunction(torch.autograd.Function):
+    """ssim [B] = the mean structural similarity of a and b [B,H,W,C] under the separable window `window` (K floats, odd K in
+    3..11, already normalised) with the constants c1 = (k1 L)^2, c2 = (k2 L)^2 (tl_ssim_fwd / tl_ssim_bwd; imaging.ssim(fused=True),
+    which checks the arguments).
+
+    float32 on one GPU; both images are taken with the strides they have.  The forward stores the partial maps only of the
+    images that need a gradient (4 bytes per map element each: three maps for one gradient, five for both, none without);
+    the backward is one launch per image that needs a gradient."""
+
+    @staticmethod
+    def _geom(a, b, window, c1, c2, flags=0, g=None):
+        B, H, W, Cc = a.shape
+        q = _lib.tl_ssim_geom(device=a.device.index, B=B, H=H, W=W, C=Cc, K=len(window), C1=c1, C2=c2, flags=flags)
+        q.window[:len(window)] = window
+        q.a_stride[:] = a.stride()
+        q.b_stride[:] = b.stride()
+        q.g_stride[:] = (g if g is not None else a).stride()
+        return q
+
+    @staticmethod
+    def forward(ctx, a, b, window, c1, c2):
+        ctx.set_materialize_grads(False)
+        dev = a.device
+        need_a, need_b = ctx.needs_input_grad[:2]
+        q = SsimFunction._geom(a, b, window, c1, c2, flags=int(need_a) | 2 * int(need_b))
+        n = _lib.lib().tl_ssim_maps_elems(C.byref(q))
+        nbytes = _lib.lib().tl_ssim_work_bytes(C.byref(q))
+        maps = [torch.empty(n, dtype=torch.float32, device=dev) if want else None
+                for want in (need_a, need_a, need_b, need_b, need_a or need_b)]
+        value = torch.empty(a.shape[0], dtype=torch.float32, device=dev)
+        ws = _workspace(nbytes, dev)
+        _call("tl_ssim_fwd", dev, C.byref(q), a, b, value, *maps, ws, ws.numel())
+        _ssim_calls["fwd"] += 1
+        _ssim_calls.update(a_ptr=a.data_ptr(), b_ptr=b.data_ptr())
+        ctx.save_for_backward(a, b, *[m for m in maps if m is not None])
+        ctx.args = (window, c1, c2)
+        return value
+
+    @staticmethod
+    def backward(ctx, g_value):
+        need_a, need_b = ctx.needs_input_grad[:2]
+        if g_value is None or not (need_a or need_b):
+            return None, None, None, None, None
+        a, b, *maps = ctx.saved_tensors
+        dc = maps.pop()
+        dev = a.device
+        g_value = g_value.to(torch.float32).contiguous()
+        grads = []
+        for need, p, q_ in ((need_a, a, b), (need_b, b, a)):
+            if not need:
+                grads.append(None)
+                continue
+            dm, ds = maps.pop(0), maps.pop(0)
+            g_p = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            q = SsimFunction._geom(p, q_, *ctx.args, g=g_p)
+            _call("tl_ssim_bwd", dev, C.byref(q), p, q_, dm, ds, dc, g_value, g_p)
+            _ssim_calls["bwd"] += 1
+            grads.append(g_p)
+        return grads[0], grads[1], None, None, None
+
+
 class PupilPositionFunction(torch.autograd.Function):
     """z [B] = paraxial entrance-pupil position from the rows in front of the stop: c, t [B,K], n [B,K+1]
     (tl_pupil_position: one tiny kernel forward, one backward, one thread per lens; mode 'strict': the value is the
