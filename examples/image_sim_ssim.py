@@ -11,9 +11,10 @@ ending in the structural similarity as the merit function,  loss = 1 - imaging.s
 steps on the curvatures and thicknesses of the Cooke triplet.  SSIM and PSNR are printed before and after.  The focal length is
 free to drift (no constraint term): the point is the chain and its gradient, not a design.
 
-    python examples/image_sim_ssim.py --steps 10 [--log2-pupil 12] [--pixel 0.004] [--torch]
+    python examples/image_sim_ssim.py --steps 10 [--log2-pupil 12] [--pixel 0.004] [--torch] [--merit ms-ssim]
 
---torch takes the plain torch formulations of the convolution, the warp and the SSIM instead of the kernels.
+--merit ms-ssim minimises 1 - imaging.ms_ssim instead (tf's weights over as many levels as the chart carries with the 11-tap
+window: three for 96 x 64) and prints the MS-SSIM next to SSIM and PSNR.  --torch takes the plain torch formulations of the convolution, the warp and the SSIM instead of the kernels.
 """
 import argparse
 import json
@@ -28,8 +29,20 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
 
 
+def ms_ssim_weights(size, filter_size=11):
+    """tf's power factors for as many levels as the chart carries with the window (every level at least filter_size on both
+    sides), normalised to sum 1."""
+    from torchoptics_amd import imaging
+    h, w = size
+    m = 0
+    while m < len(imaging.MS_SSIM_POWER_FACTORS) and min(h, w) >= filter_size:
+        h, w, m = (h + 1) // 2, (w + 1) // 2, m + 1
+    p = imaging.MS_SSIM_POWER_FACTORS[:m]
+    return tuple(v / sum(p) for v in p)
+
+
 def run(steps=10, lr=2e-4, log2_pupil=12, pixel=0.004, n_fields=5, size=(96, 64), n_bins=(9, 9), fused=True, device="cuda:0",
-        verbose=False):
+        verbose=False, merit="ssim"):
     import yaml_free_lenses as L
     import torchoptics_amd as ta
     from image_sim import chart
@@ -44,7 +57,8 @@ def run(steps=10, lr=2e-4, log2_pupil=12, pixel=0.004, n_fields=5, size=(96, 64)
     nd, v = leaves["nd"].detach(), leaves["v"].detach()
     opt = torch.optim.Adam([leaves["c"], leaves["t"]], lr=lr)
     target = chart(*size, device)
-    ssims, psnrs = [], []
+    ssims, psnrs, merits = [], [], []
+    weights = ms_ssim_weights(target.shape[1:3]) if merit == "ms-ssim" else None
     for _ in range(steps + 1):
         opt.zero_grad(set_to_none=True)
         lens = ta.Lens(structure, leaves["c"], leaves["t"], nd, v)
@@ -58,7 +72,12 @@ def run(steps=10, lr=2e-4, log2_pupil=12, pixel=0.004, n_fields=5, size=(96, 64)
         blurred = imaging.svola_convolution(target, 8, psfs, (n_fields, 1), "hann", fused=fused)
         rendered = imaging.warp_bicubic(blurred, x, y, gain, fused=None if fused else False, image_grad="fused")
         value = imaging.ssim(rendered, target, fused=None if fused else False)
-        loss = 1 - value.mean()
+        if merit == "ms-ssim":
+            ms = imaging.ms_ssim(rendered, target, power_factors=weights, fused=None if fused else False)
+            merits.append(ms.detach().mean())
+            loss = 1 - ms.mean()
+        else:
+            loss = 1 - value.mean()
         loss.backward()
         opt.step()
         ssims.append(value.detach().mean())
@@ -67,6 +86,9 @@ def run(steps=10, lr=2e-4, log2_pupil=12, pixel=0.004, n_fields=5, size=(96, 64)
     out = dict(workload="cooke", chart=list(size), fields=n_fields, rays_per_step=n_fields * 3 << log2_pupil, steps=steps,
                fused=bool(fused), pixel_mm=pixel, ssim_initial=ssims[0], ssim_final=ssims[-1], psnr_initial=psnrs[0],
                psnr_final=psnrs[-1])
+    if merit == "ms-ssim":
+        merits = torch.stack(merits).cpu().tolist()
+        out.update(merit="ms-ssim", levels=len(weights), ms_ssim_initial=merits[0], ms_ssim_final=merits[-1])
     if verbose:
         print(json.dumps(out))
     return out, ssims
@@ -79,10 +101,17 @@ def main():
     ap.add_argument("--log2-pupil", type=int, default=12)
     ap.add_argument("--pixel", type=float, default=0.004, help="pixel size in mm")
     ap.add_argument("--torch", action="store_true", help="the plain torch formulations of the convolution, the warp and the SSIM")
+    ap.add_argument("--merit", choices=("ssim", "ms-ssim"), default="ssim",
+                    help="the merit function Adam minimises 1 minus: imaging.ssim or imaging.ms_ssim (as many of tf's levels as the chart carries)")
     a = ap.parse_args()
-    out, _ = run(a.steps, a.lr, a.log2_pupil, a.pixel, fused=not a.torch, verbose=True)
+    out, _ = run(a.steps, a.lr, a.log2_pupil, a.pixel, fused=not a.torch, verbose=True, merit=a.merit)
+    if a.merit == "ms-ssim":
+        print(f"MS-SSIM ({out['levels']} levels) {out['ms_ssim_initial']:.6f} -> {out['ms_ssim_final']:.6f}")
     print(f"SSIM {out['ssim_initial']:.6f} -> {out['ssim_final']:.6f}, PSNR {out['psnr_initial']:.3f} dB -> {out['psnr_final']:.3f} dB")
-    if not out["ssim_final"] > out["ssim_initial"]:
+    if a.merit == "ms-ssim":
+        if not out["ms_ssim_final"] > out["ms_ssim_initial"]:
+            raise SystemExit("the MS-SSIM did not rise")
+    elif not out["ssim_final"] > out["ssim_initial"]:
         raise SystemExit("the SSIM did not rise")
 
 

@@ -615,6 +615,57 @@ int tl_ssim_bwd(const tl_ssim_geom *g, const float *p, const float *q, const flo
                 const float *g_value, float *g_p, void *stream);
 
 /*
+ * Multi-scale structural similarity (what tf.image.ssim_multiscale computes) and its gradients to both images
+ * (imaging.ms_ssim(fused=True); additive entry points, ABI unchanged).  a, b [B,H,W,C] floats through element strides, window,
+ * K, C1, C2 as in tl_ssim_geom.  With M = levels (1..8) and p = power:
+ *     level 0 is the images; level k + 1 is the 2 x 2 mean of level k with stride 2, ceil(H_k / 2) x ceil(W_k / 2), the last row
+ *     or column of an odd side counted twice:  pooled[y', x'] = 1/4 sum_{dy,dx in {0,1}} img[min(2y' + dy, H_k - 1), min(2x' + dx, W_k - 1)]
+ *     cs_k[b,c]   = mean over level k's valid map of (2 cab + C2) / (va + vb + C2),   ssim_k[b,c] = mean over the map of S
+ *     v_k = cs_k for k < M - 1,  v_{M-1} = ssim_{M-1}                                  terms [B,C,M] floats, contiguous
+ *     ms[b,c] = prod_k max(v_k, 0)^p_k,   value[b] = mean_c ms[b,c]                     value [B] floats, contiguous
+ *     d ms / d v_k = p_k ms / v_k where every term of (b, c) is > 0, and exactly 0 for all k otherwise.
+ *   tl_ms_ssim_fwd   one call for the whole pyramid: per level a pooling launch (both images at once; level 0 is read through the
+ *                    caller's strides, the pooled levels are dense channels-last in `keep`) and the term forward -- tl_ssim_fwd's
+ *                    kernel summing CS or S into one fp64 partial per (lens, tile, channel) -- and ONE finish launch that adds
+ *                    the partials in a fixed order and forms terms, value and the factors d ms / d v_k in fp64.  `flags` bit 0 /
+ *                    bit 1: keep the partial maps for the gradient to a / to b.
+ *   tl_ms_ssim_bwd   g_p for ONE image (which = 0: p is a, 1: p is b; the caller swaps p, q and their strides as for tl_ssim_bwd;
+ *                    `flags` as in the forward).  Per level from the coarsest to the finest tl_ssim_bwd's kernel with the seed
+ *                    g_value[b] / C  d ms / d v_k / (Hm_k Wm_k) per channel, adding in its store the adjoint of the pooling of
+ *                    the level above: 1/4 g_{k+1}[y / 2, x / 2], times 2 per axis on which the pixel is the doubled last one.
+ * `keep`: tl_ms_ssim_keep_elems(g) floats, aligned to 8 bytes, written by the forward and read by the backward: B C M doubles
+ * (the factors), the pooled levels of both images, and per level dm_a (bit 0), dm_b (bit 1), ds, dc (either bit) -- 4 bytes per
+ * map element each.  `work`: tl_ms_ssim_work_bytes(g) bytes, aligned to 8; it holds nothing between the calls (the forward's tile
+ * partials; the backward's gradients to the pooled levels).  Both planners give 0 for a geometry that is refused.
+ * No atomics: the same bits on every run.  B is cut into launches of 65535 lenses inside the call; every launch goes on `stream`
+ * back to back, no host synchronisation, no allocation.
+ * TL_EINVAL before any HIP call, with the function's name and the argument in the message: a required pointer NULL, a size below
+ * 1, K even, below 3 or above 11, levels outside 1..8, a level with a side below K (the message names the level and its size),
+ * H or W above 2^20 (or H W C >= 2^31), unknown flag bits, `which` not 0 or 1 or naming an image whose maps the flags do not
+ * keep, and keep or work NULL, misaligned or too small.
+ */
+typedef struct tl_ms_ssim_geom {
+    int32_t device;
+    int32_t B, H, W, C;               /* a, b [B,H,W,C] */
+    int32_t K;                        /* window taps per axis: odd, 3..11 */
+    float window[11];                 /* the first K are read */
+    float C1, C2;                     /* (k1 L)^2, (k2 L)^2 */
+    int32_t levels;                   /* M: 1..8 */
+    float power[8];                   /* the first M are read */
+    int32_t flags;                    /* bit 0 the maps of a, bit 1 the maps of b are kept */
+    int64_t a_stride[4];              /* elements: b, y, x, c; of p in tl_ms_ssim_bwd */
+    int64_t b_stride[4];              /* of q in tl_ms_ssim_bwd */
+    int64_t g_stride[4];              /* of g_p (tl_ms_ssim_bwd) */
+} tl_ms_ssim_geom;
+
+size_t tl_ms_ssim_work_bytes(const tl_ms_ssim_geom *g);
+size_t tl_ms_ssim_keep_elems(const tl_ms_ssim_geom *g);
+int tl_ms_ssim_fwd(const tl_ms_ssim_geom *g, const float *a, const float *b, float *value, float *terms, float *keep,
+                   size_t keep_elems, void *work, size_t work_bytes, void *stream);
+int tl_ms_ssim_bwd(const tl_ms_ssim_geom *g, const float *p, const float *q, const float *keep, size_t keep_elems,
+                   const float *g_value, float *g_p, int which, void *work, size_t work_bytes, void *stream);
+
+/*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of
  * `mode` use.  Strict mode promises the correctly rounded (IEEE) results on the operand ranges of the trace, from shorter
  * instruction sequences than the compiler's general ones: tests/test_gpu_arith.py holds it to that, bit for bit.

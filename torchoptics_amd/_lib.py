@@ -90,6 +90,13 @@ class tl_ssim_geom(C.Structure):
                 ("a_stride", C.c_int64 * 4), ("b_stride", C.c_int64 * 4), ("g_stride", C.c_int64 * 4)]
 
 
+class tl_ms_ssim_geom(C.Structure):
+    _fields_ = [("device", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+                ("K", C.c_int32), ("window", C.c_float * 11), ("C1", C.c_float), ("C2", C.c_float), ("levels", C.c_int32),
+                ("power", C.c_float * 8), ("flags", C.c_int32),
+                ("a_stride", C.c_int64 * 4), ("b_stride", C.c_int64 * 4), ("g_stride", C.c_int64 * 4)]
+
+
 _lock = threading.Lock()
 _lib = None
 
@@ -148,6 +155,13 @@ _SIGNATURES = {
     "tl_ssim_fwd": (C.c_int, [C.POINTER(tl_ssim_geom)] + [_VP] * 2 + [_VP] + [_VP] * 5 + [_VP, C.c_size_t] + [_VP]),
     # geom | p, q | dm, ds, dc | g_value | g_p | stream
     "tl_ssim_bwd": (C.c_int, [C.POINTER(tl_ssim_geom)] + [_VP] * 2 + [_VP] * 3 + [_VP] + [_VP] + [_VP]),
+    "tl_ms_ssim_work_bytes": (C.c_size_t, [C.POINTER(tl_ms_ssim_geom)]),
+    "tl_ms_ssim_keep_elems": (C.c_size_t, [C.POINTER(tl_ms_ssim_geom)]),
+    # geom | a, b | value, terms | keep, keep_elems | work, work_bytes | stream
+    "tl_ms_ssim_fwd": (C.c_int, [C.POINTER(tl_ms_ssim_geom)] + [_VP] * 2 + [_VP] * 2 + [_VP, C.c_size_t] + [_VP, C.c_size_t] + [_VP]),
+    # geom | p, q | keep, keep_elems | g_value | g_p | which | work, work_bytes | stream
+    "tl_ms_ssim_bwd": (C.c_int, [C.POINTER(tl_ms_ssim_geom)] + [_VP] * 2 + [_VP, C.c_size_t] + [_VP] + [_VP] + [C.c_int]
+                       + [_VP, C.c_size_t] + [_VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

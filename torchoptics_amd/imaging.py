@@ -596,6 +596,108 @@ def ssim(a, b, max_value=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03
     return ops.SsimFunction.apply(a, b, window, c1, c2)
 
 
+MS_SSIM_POWER_FACTORS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)        # tf.image.ssim_multiscale's defaults
+
+
+def _ms_ssim_torch(a, b, max_value, power_factors, filter_size, filter_sigma, k1, k2):
+    """The definition of ms_ssim in plain torch ops (any device, any float dtype; autograd does the rest).  Returns
+    (ms_ssim [B], terms [B, C, M]).  Per level the moments are taken as in _ssim_torch, about each image's detached mean."""
+    Cc, M = a.shape[3], len(power_factors)
+    w = ssim_window(filter_size, filter_sigma, a.dtype).to(a.device)
+    w_row = w.reshape(1, 1, 1, -1).expand(Cc, 1, 1, -1)
+    w_col = w.reshape(1, 1, -1, 1).expand(Cc, 1, -1, 1)
+    blur = lambda t: F.conv2d(F.conv2d(t, w_row, groups=Cc), w_col, groups=Cc)         # noqa: E731
+    c1, c2 = (k1 * max_value) ** 2, (k2 * max_value) ** 2
+    x, y = a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)
+    terms = []
+    for k in range(M):
+        if k:          # the 2 x 2 mean with stride 2; the last row / column of an odd side is counted twice
+            pad = (0, x.shape[3] % 2, 0, x.shape[2] % 2)
+            x, y = F.avg_pool2d(F.pad(x, pad, mode="replicate"), 2), F.avg_pool2d(F.pad(y, pad, mode="replicate"), 2)
+        x0, y0 = x.detach().mean(dim=(2, 3), keepdim=True), y.detach().mean(dim=(2, 3), keepdim=True)
+        xc, yc = x - x0, y - y0
+        m_a, m_b = blur(xc), blur(yc)
+        va, vb, cab = blur(xc * xc) - m_a * m_a, blur(yc * yc) - m_b * m_b, blur(xc * yc) - m_a * m_b
+        q = (2 * cab + c2) / (va + vb + c2)
+        if k == M - 1:
+            mu_a, mu_b = m_a + x0, m_b + y0
+            q = q * (2 * mu_a * mu_b + c1) / (mu_a * mu_a + mu_b * mu_b + c1)
+        terms.append(q.mean(dim=(2, 3)))
+    v = torch.stack(terms, dim=2)                                                      # [B, C, M]
+    p = torch.tensor(power_factors, dtype=a.dtype, device=a.device)
+    # where any term of a (lens, channel) is <= 0 the product is 0 and so are all its gradients: the power is taken of 1
+    # there (a finite derivative, which the `where` then multiplies by 0), never of 0
+    positive = (v > 0).all(dim=2, keepdim=True)
+    ms = torch.where(positive[..., 0], (torch.where(positive, v, torch.ones_like(v)) ** p).prod(dim=2),
+                     (v.detach().clamp(min=0) ** p).prod(dim=2))
+    return ms.mean(dim=1), v.detach()
+
+
+def ms_ssim_level_sizes(H, W, levels):
+    """[(H_k, W_k)] of the pyramid: each level halves the one below, rounding up."""
+    out = []
+    for _ in range(levels):
+        out.append((H, W))
+        H, W = (H + 1) // 2, (W + 1) // 2
+    return out
+
+
+def ms_ssim(a, b, max_value=1.0, power_factors=MS_SSIM_POWER_FACTORS, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03,
+            fused=None, return_terms=False):
+    """The multi-scale structural similarity of two images per lens, as `tf.image.ssim_multiscale` computes it (the defaults
+    are its defaults).  a, b [B, H, W, C] of one shape; M = len(power_factors), 1 <= M <= 8.  Returns ms_ssim [B]; with
+    `return_terms=True`, (ms_ssim, v [B, C, M]) with v detached (a diagnostic: which level is off).
+
+    Level 0 is the images; level k + 1 is the 2 x 2 mean of level k with stride 2, ceil(H_k / 2) x ceil(W_k / 2), the last row or
+    column of an odd side counted twice.  Every level must have both sides >= filter_size (ValueError otherwise).  Per level,
+    lens and channel, with window, VALID convolution, C1 and C2 as in `ssim`:
+        cs_k = mean over the level's map of (2 cab + C2) / (va + vb + C2),   ssim_k = mean over the map of S
+        v_k = cs_k for k < M - 1,  v_{M-1} = ssim_{M-1},   ms[b,c] = prod_k max(v_k, 0)^p_k,   ms_ssim[b] = mean_c ms[b,c].
+    d ms / d v_k = p_k ms / v_k where every term of that (b, c) is > 0; if any term is <= 0, ms is 0 and all its gradients are
+    exactly 0 (finite: never the NaN / inf of relu().pow() at 0).  Both paths implement this rule.
+
+    `fused=False`: plain torch ops, any device and float dtype.  `fused=True`: the HIP kernels (ops.MsSsimFunction): float32
+    tensors on one GPU, filter_size odd in 3..11; ONE C-ABI call forward for the whole pyramid and one backward per image that
+    needs a gradient, no atomics, the same bits on every run.  Anything else raises a ValueError that names the reason (there
+    is no CPU fallback).  `fused=None` (default): the kernels when they apply, torch otherwise."""
+    if a.dim() != 4 or b.dim() != 4:
+        raise ValueError(f"ms_ssim: a and b must be [B, H, W, C], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape != b.shape:
+        raise ValueError(f"ms_ssim: a and b must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    K = int(filter_size)
+    power = tuple(float(p) for p in power_factors)
+    M = len(power)
+    B, H, W, Cc = a.shape
+    if not 1 <= M <= ops.MS_SSIM_MAX_LEVELS:
+        raise ValueError(f"ms_ssim: levels: power_factors must hold 1 .. {ops.MS_SSIM_MAX_LEVELS} weights, got {M}")
+    if K < 1 or min(B, Cc) < 1:
+        raise ValueError(f"ms_ssim: filter_size and every size must be at least 1, got filter_size {K} and {tuple(a.shape)}")
+    for k, (h, w) in enumerate(ms_ssim_level_sizes(H, W, M)):
+        if h < K or w < K:
+            raise ValueError(f"ms_ssim: level {k} is {h} x {w}: every level must be at least filter_size = {K} on both sides "
+                             f"(the window is valid only); {H} x {W} carries fewer than {M} levels")
+    why_not = None
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        why_not = f"dtype: a is {a.dtype}, b is {b.dtype}; the kernels are float32"
+    elif not a.is_cuda or b.device != a.device:
+        why_not = f"device: a is on {a.device}, b on {b.device}; the kernels run on one AMD GPU (there is no CPU fallback)"
+    elif K % 2 == 0 or K < 3 or K > ops.SSIM_MAX_TAPS:
+        why_not = f"K: filter_size must be odd, 3 <= filter_size <= {ops.SSIM_MAX_TAPS}, got {K}"
+    elif max(H, W) > 1 << 20 or ((H + 15) // 16) * ((W + 31) // 32) > 1 << 22 or H * W * Cc >= 1 << 31:
+        why_not = f"size: {H} x {W} x {Cc} are more than the kernels tile"
+    if fused is None:
+        fused = why_not is None
+    if not fused:
+        value, v = _ms_ssim_torch(a, b, float(max_value), power, K, float(filter_sigma), float(k1), float(k2))
+    else:
+        if why_not is not None:
+            raise ValueError(f"ms_ssim(fused=True) does not apply -- {why_not}: use fused=False")
+        window = tuple(float(t) for t in ssim_window(K, filter_sigma, torch.float32))
+        c1, c2 = (float(k1) * float(max_value)) ** 2, (float(k2) * float(max_value)) ** 2
+        value, v = ops.MsSsimFunction.apply(a, b, window, c1, c2, power)
+    return (value, v) if return_terms else value
+
+
 def psnr(a, b, max_value=1.0):
     """The peak signal-to-noise ratio per image, 10 log10(L^2 / mse) with mse the mean of (a - b)^2 over everything but the
     first axis and L = max_value (the other half of the reference's pair, `tf.image.psnr`).  a, b [B, ...] of one shape;

@@ -889,6 +889,79 @@ class SsimFunction(torch.autograd.Function):
         return grads[0], grads[1], None, None, None
 
 
+MS_SSIM_MAX_LEVELS = 8    # the levels of the tl_ms_ssim_* pyramid
+
+# C-ABI calls of MsSsimFunction since import and the pointers the last forward handed in (ssim_counts() does not move)
+_ms_ssim_calls = {"fwd": 0, "bwd": 0, "a_ptr": None, "b_ptr": None}
+
+
+def ms_ssim_counts() -> dict:
+    """{'fwd': n, 'bwd': n, 'a_ptr', 'b_ptr': data pointers of the last forward's images}."""
+    return dict(_ms_ssim_calls)
+
+
+class MsSsimFunction(torch.autograd.Function):
+    """(ms_ssim [B], terms [B,C,M]) of a and b [B,H,W,C]: the multi-scale structural similarity over M = len(power) levels of
+    2 x 2 mean pooling (tl_ms_ssim_fwd / tl_ms_ssim_bwd; imaging.ms_ssim(fused=True), which checks the arguments).  `terms`
+    (cs of the levels below the top, ssim of the top one, per lens and channel) is a diagnostic and carries no gradient.
+
+    float32 on one GPU; both images are taken with the strides they have.  One C-ABI call forward for the whole pyramid and
+    one backward per image that needs a gradient; the forward allocates one workspace and one keep buffer (the pooled levels
+    of both images and, per level, three partial maps for one gradient, four for both)."""
+
+    @staticmethod
+    def _geom(a, b, window, c1, c2, power, flags, g=None):
+        B, H, W, Cc = a.shape
+        q = _lib.tl_ms_ssim_geom(device=a.device.index, B=B, H=H, W=W, C=Cc, K=len(window), C1=c1, C2=c2,
+                                 levels=len(power), flags=flags)
+        q.window[:len(window)] = window
+        q.power[:len(power)] = power
+        q.a_stride[:] = a.stride()
+        q.b_stride[:] = b.stride()
+        q.g_stride[:] = (g if g is not None else a).stride()
+        return q
+
+    @staticmethod
+    def forward(ctx, a, b, window, c1, c2, power):
+        ctx.set_materialize_grads(False)
+        dev = a.device
+        need_a, need_b = ctx.needs_input_grad[:2]
+        flags = int(need_a) | 2 * int(need_b)
+        q = MsSsimFunction._geom(a, b, window, c1, c2, power, flags)
+        keep = torch.empty(_lib.lib().tl_ms_ssim_keep_elems(C.byref(q)), dtype=torch.float32, device=dev)
+        ws = _workspace(_lib.lib().tl_ms_ssim_work_bytes(C.byref(q)), dev)
+        value = torch.empty(a.shape[0], dtype=torch.float32, device=dev)
+        terms = torch.empty((a.shape[0], a.shape[3], len(power)), dtype=torch.float32, device=dev)
+        _call("tl_ms_ssim_fwd", dev, C.byref(q), a, b, value, terms, keep, keep.numel(), ws, ws.numel())
+        _ms_ssim_calls["fwd"] += 1
+        _ms_ssim_calls.update(a_ptr=a.data_ptr(), b_ptr=b.data_ptr())
+        ctx.save_for_backward(a, b, keep)
+        ctx.args = (window, c1, c2, power, flags)
+        ctx.mark_non_differentiable(terms)
+        return value, terms
+
+    @staticmethod
+    def backward(ctx, g_value, _g_terms):
+        need_a, need_b = ctx.needs_input_grad[:2]
+        if g_value is None or not (need_a or need_b):
+            return (None,) * 6
+        a, b, keep = ctx.saved_tensors
+        dev = a.device
+        g_value = g_value.to(torch.float32).contiguous()
+        grads = []
+        for which, (need, p, q_) in enumerate(((need_a, a, b), (need_b, b, a))):
+            if not need:
+                grads.append(None)
+                continue
+            g_p = torch.empty(p.shape, dtype=torch.float32, device=dev)
+            q = MsSsimFunction._geom(p, q_, *ctx.args, g=g_p)
+            ws = _workspace(_lib.lib().tl_ms_ssim_work_bytes(C.byref(q)), dev)
+            _call("tl_ms_ssim_bwd", dev, C.byref(q), p, q_, keep, keep.numel(), g_value, g_p, which, ws, ws.numel())
+            _ms_ssim_calls["bwd"] += 1
+            grads.append(g_p)
+        return grads[0], grads[1], None, None, None, None
+
+
 class PupilPositionFunction(torch.autograd.Function):
     """z [B] = paraxial entrance-pupil position from the rows in front of the stop: c, t [B,K], n [B,K+1]
     (tl_pupil_position: one tiny kernel forward, one backward, one thread per lens; mode 'strict': the value is the
