@@ -1,5 +1,12 @@
 // tl_ssim.hip -- the structural similarity of two images under a separable Gaussian window, per lens, and its gradients to both
-// images (tl_ssim_fwd, tl_ssim_bwd of include/tl_trace.h; imaging.ssim(fused=True) stands on them).
+// images (tl_ssim_fwd, tl_ssim_bwd of include/tl_trace.h; imaging.ssim(fused=True) stands on them), and the multi-scale pyramid
+// of it (tl_ms_ssim_fwd, tl_ms_ssim_bwd; imaging.ms_ssim(fused=True)).
+//
+// LAYOUT.  The kernels come first: ssim_fwd_kernel<K, Q> and ssim_bwd_kernel<K, MS> serve both pairs of entry points, the finish,
+// pooling and pyramid-finish kernels one each.  Below them ONE host path: both public geometries are read into one description
+// (Desc; `pyramid` marks the multi-scale calls, the single scale is not a pyramid of one level), over which stand one fault
+// function, one maker of a level's Geo, one buffer check and, per direction, one helper that cuts B into launches, dispatches
+// on K and checks each launch.  The four entry points differ in what they check and in the levels they walk, not in how they launch.
 //
 //   mu_a = w*a,  mu_b = w*b,  va = w*a^2 - mu_a^2,  vb = w*b^2 - mu_b^2,  cab = w*ab - mu_a mu_b      (valid window, w (x) w)
 //   S = (2 mu_a mu_b + C1)(2 cab + C2) / ((mu_a^2 + mu_b^2 + C1)(va + vb + C2)),   ssim[b] = mean of S over Hm x Wm x C
@@ -410,133 +417,7 @@ __global__ __launch_bounds__(kBlock) void ssim_bwd_kernel(const Geo g, const flo
     }
 }
 
-int64_t tiles_of(int n_y, int n_x) { return (int64_t)((n_y + kTY - 1) / kTY) * ((n_x + kTX - 1) / kTX); }
-
-// Everything about the geometry that can be refused without a HIP call; nullptr when it is fine.
-const char *geom_fault(const tl_ssim_geom *g)
-{
-    if (!g) return "g is NULL";
-    if (g->B < 1 || g->H < 1 || g->W < 1 || g->C < 1) return "B, H, W, C must be >= 1";
-    if (g->K < 3 || g->K > kMaxK || g->K % 2 == 0) return "K must be odd, 3 <= K <= 11";
-    if (g->H < g->K || g->W < g->K) return "H and W must be >= K (the window is valid only)";
-    if (g->H > kMaxEdge || g->W > kMaxEdge) return "H and W must be <= 2^20";
-    if (tiles_of(g->H, g->W) > kMaxTiles) return "H W must fit 2^22 tiles of 16 x 32 pixels";
-    if (g->flags & ~3) return "flags has bits other than bit 0 (maps of a) and bit 1 (maps of b) set";
-    return nullptr;
-}
-
-int refuse(const char *fn, const char *what)
-{
-    static thread_local char msg[256];
-    snprintf(msg, sizeof(msg), "%s: %s", fn, what);
-    return tl_host::fail(TL_EINVAL, msg);
-}
-
-size_t work_bytes(const tl_ssim_geom *g)
-{
-    const size_t raw = (size_t)g->B * (size_t)tiles_of(g->H - g->K + 1, g->W - g->K + 1) * sizeof(double);
-    return (raw + 255) / 256 * 256;
-}
-
-// n_x: the columns that the launch tiles (of the map in the forward, of the image in the backward)
-Geo make_geo(const tl_ssim_geom *g, int n_x)
-{
-    Geo q;
-    q.B = g->B; q.H = g->H; q.W = g->W; q.C = g->C;
-    q.Hm = g->H - g->K + 1; q.Wm = g->W - g->K + 1;
-    q.tiles_x = (n_x + kTX - 1) / kTX;
-    for (int k = 0; k < kMaxK; ++k) q.w[k] = k < g->K ? g->window[k] : 0.f;
-    q.C1 = g->C1; q.C2 = g->C2;
-    for (int k = 0; k < 4; ++k) { q.a_s[k] = g->a_stride[k]; q.b_s[k] = g->b_stride[k]; q.g_s[k] = g->g_stride[k]; }
-    return q;
-}
-
-template <typename F>
-void for_k(int K, F &&f)
-{
-    switch (K) {
-    case 3: f(std::integral_constant<int, 3>()); break;
-    case 5: f(std::integral_constant<int, 5>()); break;
-    case 7: f(std::integral_constant<int, 7>()); break;
-    case 9: f(std::integral_constant<int, 9>()); break;
-    default: f(std::integral_constant<int, 11>()); break;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------- the multi-scale pyramid
-//
-// tl_ms_ssim_fwd: per level k = 0 .. M - 1, [pool level k - 1 -> k for both images], the term forward of level k (kCsChan
-// below the top, kSsimChan on it); then ONE finish launch.  tl_ms_ssim_bwd: per level from the coarsest to the finest one
-// ssim_bwd_kernel<K, true>, which adds the unpooled gradient of the level above in its store.  Every launch goes on the stream
-// back to back.  KEEP (floats): [ factor: B C M doubles | pooled a, levels 1 .. M - 1 | pooled b | the maps dm_a (flags bit
-// 0), dm_b (bit 1), ds, dc (either bit), each all levels one after the other ], every image and map dense channels-last.
-// WORK: forward, the tile partials, one double per (level, lens, tile, channel); backward, the gradients to the pooled
-// images of levels 1 .. M - 1.
 constexpr int kMaxLevels = 8;
-
-struct Level {
-    int H, W, Hm, Wm;
-    int64_t tiles;                                  // of the map
-    size_t part_at, image_at, map_at;               // doubles into the partials; floats into one pooled pyramid / one map
-};
-struct Plan {
-    int M, n_maps;
-    Level lv[kMaxLevels];
-    size_t part_doubles, image_floats, map_floats, factor_floats, keep_floats, work_bytes;
-};
-
-const char *ms_geom_fault(const tl_ms_ssim_geom *g)
-{
-    static thread_local char msg[160];
-    if (!g) return "g is NULL";
-    if (g->B < 1 || g->H < 1 || g->W < 1 || g->C < 1) return "B, H, W, C must be >= 1";
-    if (g->K < 3 || g->K > kMaxK || g->K % 2 == 0) return "K must be odd, 3 <= K <= 11";
-    if (g->levels < 1 || g->levels > kMaxLevels) return "levels must be 1 .. 8";
-    if (g->H > kMaxEdge || g->W > kMaxEdge) return "H and W must be <= 2^20";
-    if (tiles_of(g->H, g->W) > kMaxTiles) return "H W must fit 2^22 tiles of 16 x 32 pixels";
-    if ((int64_t)g->H * g->W * g->C >= ((int64_t)1 << 31)) return "H W C must be below 2^31";
-    if (g->flags & ~3) return "flags has bits other than bit 0 (maps of a) and bit 1 (maps of b) set";
-    int h = g->H, w = g->W;
-    for (int k = 0; k < g->levels; ++k, h = (h + 1) / 2, w = (w + 1) / 2)
-        if (h < g->K || w < g->K) {
-            snprintf(msg, sizeof(msg), "level %d is %d x %d, every level must be >= K = %d on both sides", k, h, w, g->K);
-            return msg;
-        }
-    return nullptr;
-}
-
-Plan make_plan(const tl_ms_ssim_geom *g)
-{
-    Plan p{};
-    p.M = g->levels;
-    p.n_maps = (g->flags & 3) == 3 ? 4 : (g->flags & 3) ? 3 : 0;
-    int h = g->H, w = g->W;
-    for (int k = 0; k < p.M; ++k, h = (h + 1) / 2, w = (w + 1) / 2) {
-        Level &l = p.lv[k];
-        l.H = h; l.W = w; l.Hm = h - g->K + 1; l.Wm = w - g->K + 1;
-        l.tiles = tiles_of(l.Hm, l.Wm);
-        l.part_at = p.part_doubles; l.image_at = p.image_floats; l.map_at = p.map_floats;
-        p.part_doubles += (size_t)g->B * (size_t)l.tiles * (size_t)g->C;
-        if (k > 0) p.image_floats += (size_t)g->B * h * w * g->C;
-        p.map_floats += (size_t)g->B * l.Hm * l.Wm * g->C;
-    }
-    p.factor_floats = 2 * (size_t)g->B * g->C * p.M;
-    p.keep_floats = p.factor_floats + 2 * p.image_floats + (size_t)p.n_maps * p.map_floats;
-    p.work_bytes = (std::max(p.part_doubles * sizeof(double), p.image_floats * sizeof(float)) + 255) / 256 * 256;
-    return p;
-}
-
-Geo level_geo(const tl_ms_ssim_geom *g, const Level &l, int n_x)
-{
-    Geo q;
-    q.B = g->B; q.H = l.H; q.W = l.W; q.C = g->C; q.Hm = l.Hm; q.Wm = l.Wm;
-    q.tiles_x = (n_x + kTX - 1) / kTX;
-    for (int k = 0; k < kMaxK; ++k) q.w[k] = k < g->K ? g->window[k] : 0.f;
-    q.C1 = g->C1; q.C2 = g->C2;
-    const int64_t dense[4] = {(int64_t)l.H * l.W * g->C, (int64_t)l.W * g->C, g->C, 1};
-    for (int k = 0; k < 4; ++k) q.a_s[k] = q.b_s[k] = q.g_s[k] = dense[k];
-    return q;
-}
 
 // The 2 x 2 mean with stride 2 of both images in one launch: out[y', x'] = 1/4 sum in[min(2y' + dy, H - 1), min(2x' + dx, W - 1)]
 // (the last row or column of an odd side counts twice).  grid (blocks over the Ho Wo C elements of a pooled image, lenses of this
@@ -613,185 +494,320 @@ __global__ __launch_bounds__(kBlock) void ms_finish_kernel(const FinishPlan f, c
     if (threadIdx.x == 0) value[lens] = (float)(total / (double)f.C);
 }
 
+// ------------------------------------------------------------------------------------------------------------------- host
+//
+// What both public geometries come to (two adapters fill it; the members keep the callers' meaning).  `pyramid` marks
+// tl_ms_ssim_*: the single scale is NOT a pyramid of one level -- that sums per channel, clamps a negative mean and seeds
+// and stores differently -- so everything below asks `pyramid`, never `levels == 1`.
+struct Desc {
+    bool given, pyramid;                            // given: the caller's g was not NULL
+    int device, B, H, W, C, K, flags, levels;
+    float C1, C2;
+    const float *window, *power;
+    const int64_t *a_s, *b_s, *g_s;
+};
+template <typename G>
+Desc desc_of(const G *g, bool pyramid)
+{
+    Desc d{};
+    d.pyramid = pyramid;
+    if (!g) return d;
+    d.given = true; d.device = g->device; d.B = g->B; d.H = g->H; d.W = g->W; d.C = g->C; d.K = g->K; d.flags = g->flags;
+    d.C1 = g->C1; d.C2 = g->C2; d.window = g->window;
+    d.a_s = g->a_stride; d.b_s = g->b_stride; d.g_s = g->g_stride;
+    return d;
+}
+Desc desc_of(const tl_ssim_geom *g) { return desc_of(g, false); }
+Desc desc_of(const tl_ms_ssim_geom *g)
+{
+    Desc d = desc_of(g, true);
+    if (g) { d.levels = g->levels; d.power = g->power; }
+    return d;
+}
+
+int64_t tiles_of(int n_y, int n_x) { return (int64_t)((n_y + kTY - 1) / kTY) * ((n_x + kTX - 1) / kTX); }
+
+thread_local char t_what[160];                      // a fault that carries numbers; refuse() copies it before the next one
+
+// Everything about the geometry that can be refused without a HIP call, in the order each entry point documents; nullptr
+// when it is fine.
+const char *geom_fault(const Desc &d)
+{
+    if (!d.given) return "g is NULL";
+    if (d.B < 1 || d.H < 1 || d.W < 1 || d.C < 1) return "B, H, W, C must be >= 1";
+    if (d.K < 3 || d.K > kMaxK || d.K % 2 == 0) return "K must be odd, 3 <= K <= 11";
+    if (d.pyramid && (d.levels < 1 || d.levels > kMaxLevels)) return "levels must be 1 .. 8";
+    if (!d.pyramid && (d.H < d.K || d.W < d.K)) return "H and W must be >= K (the window is valid only)";
+    if (d.H > kMaxEdge || d.W > kMaxEdge) return "H and W must be <= 2^20";
+    if (tiles_of(d.H, d.W) > kMaxTiles) return "H W must fit 2^22 tiles of 16 x 32 pixels";
+    if (d.pyramid && (int64_t)d.H * d.W * d.C >= ((int64_t)1 << 31)) return "H W C must be below 2^31";
+    if (d.flags & ~3) return "flags has bits other than bit 0 (maps of a) and bit 1 (maps of b) set";
+    int h = d.H, w = d.W;
+    for (int k = 0; k < d.levels; ++k, h = (h + 1) / 2, w = (w + 1) / 2)           // no level without a pyramid
+        if (h < d.K || w < d.K) {
+            snprintf(t_what, sizeof(t_what), "level %d is %d x %d, every level must be >= K = %d on both sides", k, h, w, d.K);
+            return t_what;
+        }
+    return nullptr;
+}
+
+// `name` (work, keep) NULL, misaligned, or its size `size_name` below what `planner` asks; nullptr when it is fine
+const char *buffer_fault(const char *name, const void *at, const char *size_name, size_t given, const char *planner, size_t need)
+{
+    if (!at)
+        snprintf(t_what, sizeof(t_what), "%s is NULL", name);
+    else if ((uintptr_t)at % 8)
+        snprintf(t_what, sizeof(t_what), "%s must be aligned to 8 bytes", name);
+    else if (given < need)
+        snprintf(t_what, sizeof(t_what), "%s is %zu, %s asks for %zu", size_name, given, planner, need);
+    else
+        return nullptr;
+    return t_what;
+}
+
+int refuse(const char *fn, const char *what)
+{
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+    return tl_host::fail(TL_EINVAL, msg);
+}
+
+// the single scale's workspace: one double per (lens, tile of the map)
+size_t work_bytes(const Desc &d)
+{
+    const size_t raw = (size_t)d.B * (size_t)tiles_of(d.H - d.K + 1, d.W - d.K + 1) * sizeof(double);
+    return (raw + 255) / 256 * 256;
+}
+
+// The pyramid.  tl_ms_ssim_fwd: per level k = 0 .. M - 1, [pool level k - 1 -> k for both images], the term forward of level
+// k (kCsChan below the top, kSsimChan on it); then ONE finish launch.  tl_ms_ssim_bwd: per level from the coarsest to the
+// finest one ssim_bwd_kernel<K, true>, which adds the unpooled gradient of the level above in its store.  Every launch goes
+// on the stream back to back.  KEEP (floats): [ factor: B C M doubles | pooled a, levels 1 .. M - 1 | pooled b | the maps
+// dm_a (flags bit 0), dm_b (bit 1), ds, dc (either bit), each all levels one after the other ], every image and map dense
+// channels-last.  WORK: forward, the tile partials, one double per (level, lens, tile, channel); backward, the gradients to
+// the pooled images of levels 1 .. M - 1.
+struct Level {
+    int H, W, Hm, Wm;
+    int64_t tiles;                                  // of the map
+    size_t part_at, image_at, map_at;               // doubles into the partials; floats into one pooled pyramid / one map
+};
+struct Plan {
+    int M, n_maps;
+    Level lv[kMaxLevels];
+    size_t part_doubles, image_floats, map_floats, factor_floats, keep_floats, work_bytes;
+};
+Plan make_plan(const Desc &d)
+{
+    Plan p{};
+    p.M = d.levels;
+    p.n_maps = (d.flags & 3) == 3 ? 4 : (d.flags & 3) ? 3 : 0;
+    int h = d.H, w = d.W;
+    for (int k = 0; k < p.M; ++k, h = (h + 1) / 2, w = (w + 1) / 2) {
+        Level &l = p.lv[k];
+        l.H = h; l.W = w; l.Hm = h - d.K + 1; l.Wm = w - d.K + 1;
+        l.tiles = tiles_of(l.Hm, l.Wm);
+        l.part_at = p.part_doubles; l.image_at = p.image_floats; l.map_at = p.map_floats;
+        p.part_doubles += (size_t)d.B * (size_t)l.tiles * (size_t)d.C;
+        if (k > 0) p.image_floats += (size_t)d.B * h * w * d.C;
+        p.map_floats += (size_t)d.B * l.Hm * l.Wm * d.C;
+    }
+    p.factor_floats = 2 * (size_t)d.B * d.C * p.M;
+    p.keep_floats = p.factor_floats + 2 * p.image_floats + (size_t)p.n_maps * p.map_floats;
+    p.work_bytes = (std::max(p.part_doubles * sizeof(double), p.image_floats * sizeof(float)) + 255) / 256 * 256;
+    return p;
+}
+
 // the slots of the maps in KEEP after the factors and the two pooled pyramids: dm_a, dm_b (as far as kept), ds, dc
 struct Maps { float *dm_a, *dm_b, *ds, *dc; };
-Maps maps_of(const tl_ms_ssim_geom *g, const Plan &p, float *keep)
+Maps maps_of(const Desc &d, const Plan &p, float *keep)
 {
     float *at = keep + p.factor_floats + 2 * p.image_floats;
     Maps m{nullptr, nullptr, nullptr, nullptr};
-    if (g->flags & 1) { m.dm_a = at; at += p.map_floats; }
-    if (g->flags & 2) { m.dm_b = at; at += p.map_floats; }
-    if (g->flags & 3) { m.ds = at; m.dc = at + p.map_floats; }
+    if (d.flags & 1) { m.dm_a = at; at += p.map_floats; }
+    if (d.flags & 2) { m.dm_b = at; at += p.map_floats; }
+    if (d.flags & 3) { m.ds = at; m.dc = at + p.map_floats; }
     return m;
+}
+
+// The Geo of one level of h x w pixels.  n_x: the columns that the launch tiles (of the map in the forward, of the image in
+// the backward).  callers: the images are the caller's and lie at its strides (level 0); otherwise dense channels-last.
+Geo make_geo(const Desc &d, int h, int w, int n_x, bool callers)
+{
+    Geo q;
+    q.B = d.B; q.H = h; q.W = w; q.C = d.C; q.Hm = h - d.K + 1; q.Wm = w - d.K + 1;
+    q.tiles_x = (n_x + kTX - 1) / kTX;
+    for (int k = 0; k < kMaxK; ++k) q.w[k] = k < d.K ? d.window[k] : 0.f;
+    q.C1 = d.C1; q.C2 = d.C2;
+    const int64_t dense[4] = {(int64_t)h * w * d.C, (int64_t)w * d.C, d.C, 1};
+    const int64_t *a_s = callers ? d.a_s : dense, *b_s = callers ? d.b_s : dense, *g_s = callers ? d.g_s : dense;
+    for (int k = 0; k < 4; ++k) { q.a_s[k] = a_s[k]; q.b_s[k] = b_s[k]; q.g_s[k] = g_s[k]; }
+    return q;
+}
+
+template <typename F>
+void for_k(int K, F &&f)
+{
+    switch (K) {
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 5: f(std::integral_constant<int, 5>()); break;
+    case 7: f(std::integral_constant<int, 7>()); break;
+    case 9: f(std::integral_constant<int, 9>()); break;
+    default: f(std::integral_constant<int, 11>()); break;
+    }
+}
+
+// B cut into launches of at most 65535 lenses: launch(first lens, lenses), checked under the name `what`; the first launch
+// that fails ends it.
+template <typename F>
+int for_lens_chunks(int B, const char *what, F &&launch)
+{
+    for (int b0 = 0; b0 < B; b0 += kMaxY) {
+        launch(b0, (unsigned)std::min(kMaxY, B - b0));
+        if (const int rc = tl_host::launched(what)) return rc;
+    }
+    return TL_OK;
+}
+
+// The forward of one level over all lenses, summing `what`.  A NULL map is not written.
+struct FwdOut { float *dm_a, *ds_a, *dm_b, *ds_b, *dc; double *part; };
+int launch_fwd(const Desc &d, const Geo &q, Quantity what, const float *a, const float *b, const FwdOut &o, const char *name, hipStream_t st)
+{
+    const unsigned tiles = (unsigned)tiles_of(q.Hm, q.Wm);
+    const size_t lds = (size_t)fwd_lds_floats(std::min(d.C, kCh)) * sizeof(float);
+    return for_lens_chunks(d.B, name, [&](int b0, unsigned lenses) {
+        for_k(d.K, [&](auto kk) {
+            constexpr int K = decltype(kk)::value;
+            auto *kernel = what == kSsimAll ? ssim_fwd_kernel<K, kSsimAll> : what == kCsChan ? ssim_fwd_kernel<K, kCsChan> : ssim_fwd_kernel<K, kSsimChan>;
+            hipLaunchKernelGGL(kernel, dim3(tiles, lenses), dim3(kBlock), lds, st, q, a, b, o.dm_a, o.ds_a, o.dm_b, o.ds_b, o.dc, o.part, b0);
+        });
+    });
+}
+
+// The backward of one level over all lenses: of the single scale (ms false, pyr unused) or of a level of the pyramid.
+int launch_bwd(const Desc &d, const Geo &q, bool ms, const Pyramid &pyr, const float *p, const float *q_image, const float *dm,
+               const float *ds, const float *dc, const float *g_value, float *g_p, const char *name, hipStream_t st)
+{
+    const unsigned tiles = (unsigned)tiles_of(q.H, q.W);
+    const size_t lds = (size_t)bwd_lds_floats(std::min(d.C, kCh)) * sizeof(float);
+    return for_lens_chunks(d.B, name, [&](int b0, unsigned lenses) {
+        for_k(d.K, [&](auto kk) {
+            constexpr int K = decltype(kk)::value;
+            auto *kernel = ms ? ssim_bwd_kernel<K, true> : ssim_bwd_kernel<K, false>;
+            hipLaunchKernelGGL(kernel, dim3(tiles, lenses), dim3(kBlock), lds, st, q, p, q_image, dm, ds, dc, g_value, g_p, b0, pyr);
+        });
+    });
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t tl_ssim_work_bytes(const tl_ssim_geom *g) { return geom_fault(g) ? 0 : work_bytes(g); }
+size_t tl_ssim_work_bytes(const tl_ssim_geom *g) { const Desc d = desc_of(g); return geom_fault(d) ? 0 : work_bytes(d); }
 
 size_t tl_ssim_maps_elems(const tl_ssim_geom *g)
 {
-    return geom_fault(g) ? 0 : (size_t)g->B * (size_t)(g->H - g->K + 1) * (size_t)(g->W - g->K + 1) * (size_t)g->C;
+    return geom_fault(desc_of(g)) ? 0 : (size_t)g->B * (size_t)(g->H - g->K + 1) * (size_t)(g->W - g->K + 1) * (size_t)g->C;
 }
 
 int tl_ssim_fwd(const tl_ssim_geom *g, const float *a, const float *b, float *value, float *dm_a, float *ds_a, float *dm_b,
                 float *ds_b, float *dc, void *work, size_t work_bytes_given, void *stream)
 {
-    if (const char *what = geom_fault(g)) return refuse("tl_ssim_fwd", what);
-    if (!a) return refuse("tl_ssim_fwd", "a is NULL");
-    if (!b) return refuse("tl_ssim_fwd", "b is NULL");
-    if (!value) return refuse("tl_ssim_fwd", "value is NULL");
-    if ((g->flags & 1) && !dm_a) return refuse("tl_ssim_fwd", "flags bit 0 asks for the maps of a, dm_a is NULL");
-    if ((g->flags & 1) && !ds_a) return refuse("tl_ssim_fwd", "flags bit 0 asks for the maps of a, ds_a is NULL");
-    if ((g->flags & 2) && !dm_b) return refuse("tl_ssim_fwd", "flags bit 1 asks for the maps of b, dm_b is NULL");
-    if ((g->flags & 2) && !ds_b) return refuse("tl_ssim_fwd", "flags bit 1 asks for the maps of b, ds_b is NULL");
-    if ((g->flags & 3) && !dc) return refuse("tl_ssim_fwd", "flags asks for partial maps, dc is NULL");
-    const size_t need = work_bytes(g);
-    if (!work) return refuse("tl_ssim_fwd", "work is NULL");
-    if ((uintptr_t)work % 8) return refuse("tl_ssim_fwd", "work must be aligned to 8 bytes");
-    if (work_bytes_given < need) {
-        char what[128];
-        snprintf(what, sizeof(what), "work_bytes is %zu, tl_ssim_work_bytes asks for %zu", work_bytes_given, need);
-        return refuse("tl_ssim_fwd", what);
-    }
-    if (const int rc = tl_host::use_device(g->device)) return rc;
+    const char *fn = "tl_ssim_fwd";
+    const Desc d = desc_of(g);
+    if (const char *what = geom_fault(d)) return refuse(fn, what);
+    if (!a) return refuse(fn, "a is NULL");
+    if (!b) return refuse(fn, "b is NULL");
+    if (!value) return refuse(fn, "value is NULL");
+    if ((d.flags & 1) && !dm_a) return refuse(fn, "flags bit 0 asks for the maps of a, dm_a is NULL");
+    if ((d.flags & 1) && !ds_a) return refuse(fn, "flags bit 0 asks for the maps of a, ds_a is NULL");
+    if ((d.flags & 2) && !dm_b) return refuse(fn, "flags bit 1 asks for the maps of b, dm_b is NULL");
+    if ((d.flags & 2) && !ds_b) return refuse(fn, "flags bit 1 asks for the maps of b, ds_b is NULL");
+    if ((d.flags & 3) && !dc) return refuse(fn, "flags asks for partial maps, dc is NULL");
+    if (const char *what = buffer_fault("work", work, "work_bytes", work_bytes_given, "tl_ssim_work_bytes", work_bytes(d)))
+        return refuse(fn, what);
+    if (const int rc = tl_host::use_device(d.device)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int Hm = g->H - g->K + 1, Wm = g->W - g->K + 1;
-    const Geo q = make_geo(g, Wm);
-    const unsigned tiles = (unsigned)tiles_of(Hm, Wm);
-    const size_t lds = (size_t)fwd_lds_floats(std::min(g->C, kCh)) * sizeof(float);
+    const Geo q = make_geo(d, d.H, d.W, d.W - d.K + 1, true);
     // a map that the flags do not ask for is not written, whatever its pointer
-    float *ma = (g->flags & 1) ? dm_a : nullptr, *sa = (g->flags & 1) ? ds_a : nullptr;
-    float *mb = (g->flags & 2) ? dm_b : nullptr, *sb = (g->flags & 2) ? ds_b : nullptr;
-    float *cc = (g->flags & 3) ? dc : nullptr;
-    double *part = (double *)work;
-    int rc = TL_OK;
-    for (int b0 = 0; b0 < g->B && rc == TL_OK; b0 += kMaxY) {
-        const dim3 grid(tiles, std::min(kMaxY, g->B - b0));
-        for_k(g->K, [&](auto k) {
-            hipLaunchKernelGGL((ssim_fwd_kernel<decltype(k)::value, kSsimAll>), grid, dim3(kBlock), lds, st, q, a, b, ma, sa, mb, sb, cc, part, b0);
-        });
-        rc = tl_host::launched("ssim_fwd_kernel launch");
-    }
-    if (rc) return rc;
-    hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)g->B), dim3(kBlock), 0, st, part, value, (int)tiles,
-                       (double)Hm * (double)Wm * (double)g->C);
+    const FwdOut out{(d.flags & 1) ? dm_a : nullptr, (d.flags & 1) ? ds_a : nullptr, (d.flags & 2) ? dm_b : nullptr,
+                     (d.flags & 2) ? ds_b : nullptr, (d.flags & 3) ? dc : nullptr, (double *)work};
+    if (const int rc = launch_fwd(d, q, kSsimAll, a, b, out, "ssim_fwd_kernel launch", st)) return rc;
+    hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)d.B), dim3(kBlock), 0, st, out.part, value, (int)tiles_of(q.Hm, q.Wm),
+                       (double)q.Hm * (double)q.Wm * (double)d.C);
     return tl_host::launched("ssim_finish_kernel launch");
 }
 
 int tl_ssim_bwd(const tl_ssim_geom *g, const float *p, const float *q, const float *dm, const float *ds, const float *dc,
                 const float *g_value, float *g_p, void *stream)
 {
-    if (const char *what = geom_fault(g)) return refuse("tl_ssim_bwd", what);
-    if (!p) return refuse("tl_ssim_bwd", "p is NULL");
-    if (!q) return refuse("tl_ssim_bwd", "q is NULL");
-    if (!dm) return refuse("tl_ssim_bwd", "dm is NULL");
-    if (!ds) return refuse("tl_ssim_bwd", "ds is NULL");
-    if (!dc) return refuse("tl_ssim_bwd", "dc is NULL");
-    if (!g_value) return refuse("tl_ssim_bwd", "g_value is NULL");
-    if (!g_p) return refuse("tl_ssim_bwd", "g_p is NULL");
-    if (const int rc = tl_host::use_device(g->device)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Geo geo = make_geo(g, g->W);
-    const unsigned tiles = (unsigned)tiles_of(g->H, g->W);
-    const size_t lds = (size_t)bwd_lds_floats(std::min(g->C, kCh)) * sizeof(float);
-    for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
-        const dim3 grid(tiles, std::min(kMaxY, g->B - b0));
-        for_k(g->K, [&](auto k) {
-            hipLaunchKernelGGL((ssim_bwd_kernel<decltype(k)::value, false>), grid, dim3(kBlock), lds, st, geo, p, q, dm, ds, dc, g_value, g_p, b0,
-                               Pyramid{});
-        });
-        if (const int rc = tl_host::launched("ssim_bwd_kernel launch")) return rc;
-    }
-    return TL_OK;
+    const char *fn = "tl_ssim_bwd";
+    const Desc d = desc_of(g);
+    if (const char *what = geom_fault(d)) return refuse(fn, what);
+    if (!p) return refuse(fn, "p is NULL");
+    if (!q) return refuse(fn, "q is NULL");
+    if (!dm) return refuse(fn, "dm is NULL");
+    if (!ds) return refuse(fn, "ds is NULL");
+    if (!dc) return refuse(fn, "dc is NULL");
+    if (!g_value) return refuse(fn, "g_value is NULL");
+    if (!g_p) return refuse(fn, "g_p is NULL");
+    if (const int rc = tl_host::use_device(d.device)) return rc;
+    return launch_bwd(d, make_geo(d, d.H, d.W, d.W, true), false, Pyramid{}, p, q, dm, ds, dc, g_value, g_p, "ssim_bwd_kernel launch",
+                      (hipStream_t)stream);
 }
 
-size_t tl_ms_ssim_work_bytes(const tl_ms_ssim_geom *g) { return ms_geom_fault(g) ? 0 : make_plan(g).work_bytes; }
+size_t tl_ms_ssim_work_bytes(const tl_ms_ssim_geom *g) { const Desc d = desc_of(g); return geom_fault(d) ? 0 : make_plan(d).work_bytes; }
 
-size_t tl_ms_ssim_keep_elems(const tl_ms_ssim_geom *g) { return ms_geom_fault(g) ? 0 : make_plan(g).keep_floats; }
-
-static const char *ms_buffers_fault(const Plan &plan, const void *keep, size_t keep_elems, const void *work, size_t work_bytes_given,
-                                    const char *planner_keep, const char *planner_work)
-{
-    static thread_local char what[160];
-    if (!keep) return "keep is NULL";
-    if ((uintptr_t)keep % 8) return "keep must be aligned to 8 bytes";
-    if (keep_elems < plan.keep_floats) {
-        snprintf(what, sizeof(what), "keep_elems is %zu, %s asks for %zu", keep_elems, planner_keep, plan.keep_floats);
-        return what;
-    }
-    if (!work) return "work is NULL";
-    if ((uintptr_t)work % 8) return "work must be aligned to 8 bytes";
-    if (work_bytes_given < plan.work_bytes) {
-        snprintf(what, sizeof(what), "work_bytes is %zu, %s asks for %zu", work_bytes_given, planner_work, plan.work_bytes);
-        return what;
-    }
-    return nullptr;
-}
+size_t tl_ms_ssim_keep_elems(const tl_ms_ssim_geom *g) { const Desc d = desc_of(g); return geom_fault(d) ? 0 : make_plan(d).keep_floats; }
 
 int tl_ms_ssim_fwd(const tl_ms_ssim_geom *g, const float *a, const float *b, float *value, float *terms, float *keep,
                    size_t keep_elems, void *work, size_t work_bytes_given, void *stream)
 {
     const char *fn = "tl_ms_ssim_fwd";
-    if (const char *what = ms_geom_fault(g)) return refuse(fn, what);
+    const Desc d = desc_of(g);
+    if (const char *what = geom_fault(d)) return refuse(fn, what);
     if (!a) return refuse(fn, "a is NULL");
     if (!b) return refuse(fn, "b is NULL");
     if (!value) return refuse(fn, "value is NULL");
     if (!terms) return refuse(fn, "terms is NULL");
-    const Plan plan = make_plan(g);
-    if (const char *what = ms_buffers_fault(plan, keep, keep_elems, work, work_bytes_given, "tl_ms_ssim_keep_elems", "tl_ms_ssim_work_bytes"))
+    const Plan plan = make_plan(d);
+    if (const char *what = buffer_fault("keep", keep, "keep_elems", keep_elems, "tl_ms_ssim_keep_elems", plan.keep_floats))
         return refuse(fn, what);
-    if (const int rc = tl_host::use_device(g->device)) return rc;
+    if (const char *what = buffer_fault("work", work, "work_bytes", work_bytes_given, "tl_ms_ssim_work_bytes", plan.work_bytes))
+        return refuse(fn, what);
+    if (const int rc = tl_host::use_device(d.device)) return rc;
     hipStream_t st = (hipStream_t)stream;
     double *factor = (double *)keep, *part = (double *)work;
     float *pool_a = keep + plan.factor_floats, *pool_b = pool_a + plan.image_floats;
-    const Maps maps = maps_of(g, plan, keep);
-    const size_t lds = (size_t)fwd_lds_floats(std::min(g->C, kCh)) * sizeof(float);
+    const Maps maps = maps_of(d, plan, keep);
     FinishPlan fin{};
-    fin.M = plan.M; fin.C = g->C;
+    fin.M = plan.M; fin.C = d.C;
     for (int k = 0; k < plan.M; ++k) {
         const Level &l = plan.lv[k];
         fin.tiles[k] = (int)l.tiles; fin.part_at[k] = l.part_at;
-        fin.count[k] = (double)l.Hm * (double)l.Wm; fin.power[k] = (double)g->power[k];
-        Geo q = level_geo(g, l, l.Wm);
-        const float *pa = pool_a + l.image_at, *pb = pool_b + l.image_at;          // levels >= 1: dense, in KEEP
-        if (k == 0) {
-            pa = a; pb = b;
-            for (int d = 0; d < 4; ++d) { q.a_s[d] = g->a_stride[d]; q.b_s[d] = g->b_stride[d]; }
-        } else {                                                                   // level k - 1 -> level k
+        fin.count[k] = (double)l.Hm * (double)l.Wm; fin.power[k] = (double)d.power[k];
+        const float *pa = k ? pool_a + l.image_at : a, *pb = k ? pool_b + l.image_at : b;      // levels >= 1: dense, in KEEP
+        if (k) {                                                                   // level k - 1 -> level k
             const Level &from = plan.lv[k - 1];
-            PoolGeo pg{from.H, from.W, g->C, l.H, l.W, {}, {}};
-            const int64_t dense[4] = {(int64_t)from.H * from.W * g->C, (int64_t)from.W * g->C, g->C, 1};
-            for (int d = 0; d < 4; ++d) { pg.a_s[d] = k == 1 ? g->a_stride[d] : dense[d]; pg.b_s[d] = k == 1 ? g->b_stride[d] : dense[d]; }
+            const Geo src = make_geo(d, from.H, from.W, from.W, k == 1);               // for the strides of level k - 1
+            PoolGeo pg{from.H, from.W, d.C, l.H, l.W, {}, {}};
+            for (int i = 0; i < 4; ++i) { pg.a_s[i] = src.a_s[i]; pg.b_s[i] = src.b_s[i]; }
             const float *src_a = k == 1 ? a : pool_a + from.image_at, *src_b = k == 1 ? b : pool_b + from.image_at;
-            const unsigned blocks = (unsigned)(((size_t)l.H * l.W * g->C + kBlock - 1) / kBlock);
-            for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
-                hipLaunchKernelGGL(ms_pool_kernel, dim3(blocks, std::min(kMaxY, g->B - b0)), dim3(kBlock), 0, st, pg, src_a, src_b,
-                                   pool_a + l.image_at, pool_b + l.image_at, b0);
-                if (const int rc = tl_host::launched("ms_pool_kernel launch")) return rc;
-            }
+            const unsigned blocks = (unsigned)(((size_t)l.H * l.W * d.C + kBlock - 1) / kBlock);
+            const int rc = for_lens_chunks(d.B, "ms_pool_kernel launch", [&](int b0, unsigned lenses) {
+                hipLaunchKernelGGL(ms_pool_kernel, dim3(blocks, lenses), dim3(kBlock), 0, st, pg, src_a, src_b, pool_a + l.image_at,
+                                   pool_b + l.image_at, b0);
+            });
+            if (rc) return rc;
         }
         // ds is kept once: the kernel writes it through ds_a when a's maps are kept, through ds_b otherwise
         float *dm_a = maps.dm_a ? maps.dm_a + l.map_at : nullptr, *dm_b = maps.dm_b ? maps.dm_b + l.map_at : nullptr;
         float *ds = maps.ds ? maps.ds + l.map_at : nullptr, *dc = maps.dc ? maps.dc + l.map_at : nullptr;
-        float *ds_a = dm_a ? ds : nullptr, *ds_b = dm_a ? nullptr : ds;
-        for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
-            const dim3 grid((unsigned)l.tiles, std::min(kMaxY, g->B - b0));
-            for_k(g->K, [&](auto kk) {
-                constexpr int K = decltype(kk)::value;
-                if (k < plan.M - 1)
-                    hipLaunchKernelGGL((ssim_fwd_kernel<K, kCsChan>), grid, dim3(kBlock), lds, st, q, pa, pb, dm_a, ds_a, dm_b, ds_b, dc,
-                                       part + l.part_at, b0);
-                else
-                    hipLaunchKernelGGL((ssim_fwd_kernel<K, kSsimChan>), grid, dim3(kBlock), lds, st, q, pa, pb, dm_a, ds_a, dm_b, ds_b, dc,
-                                       part + l.part_at, b0);
-            });
-            if (const int rc = tl_host::launched("ssim_fwd_kernel launch (pyramid)")) return rc;
-        }
+        const FwdOut out{dm_a, dm_a ? ds : nullptr, dm_b, dm_a ? nullptr : ds, dc, part + l.part_at};
+        if (const int rc = launch_fwd(d, make_geo(d, l.H, l.W, l.Wm, k == 0), k < plan.M - 1 ? kCsChan : kSsimChan, pa, pb, out,
+                                      "ssim_fwd_kernel launch (pyramid)", st))
+            return rc;
     }
-    hipLaunchKernelGGL(ms_finish_kernel, dim3((unsigned)g->B), dim3(kBlock), 0, st, fin, part, value, terms, factor);
+    hipLaunchKernelGGL(ms_finish_kernel, dim3((unsigned)d.B), dim3(kBlock), 0, st, fin, part, value, terms, factor);
     return tl_host::launched("ms_finish_kernel launch");
 }
 
@@ -799,47 +815,36 @@ int tl_ms_ssim_bwd(const tl_ms_ssim_geom *g, const float *p, const float *q, con
                    const float *g_value, float *g_p, int which, void *work, size_t work_bytes_given, void *stream)
 {
     const char *fn = "tl_ms_ssim_bwd";
-    if (const char *what = ms_geom_fault(g)) return refuse(fn, what);
+    const Desc d = desc_of(g);
+    if (const char *what = geom_fault(d)) return refuse(fn, what);
     if (!p) return refuse(fn, "p is NULL");
     if (!q) return refuse(fn, "q is NULL");
     if (!g_value) return refuse(fn, "g_value is NULL");
     if (!g_p) return refuse(fn, "g_p is NULL");
     if (which != 0 && which != 1) return refuse(fn, "which must be 0 (p is a) or 1 (p is b)");
-    if (!(g->flags & (1 << which))) return refuse(fn, "which names an image whose maps flags did not keep");
-    const Plan plan = make_plan(g);
-    if (const char *what = ms_buffers_fault(plan, keep, keep_elems, work, work_bytes_given, "tl_ms_ssim_keep_elems", "tl_ms_ssim_work_bytes"))
+    if (!(d.flags & (1 << which))) return refuse(fn, "which names an image whose maps flags did not keep");
+    const Plan plan = make_plan(d);
+    if (const char *what = buffer_fault("keep", keep, "keep_elems", keep_elems, "tl_ms_ssim_keep_elems", plan.keep_floats))
         return refuse(fn, what);
-    if (const int rc = tl_host::use_device(g->device)) return rc;
-    hipStream_t st = (hipStream_t)stream;
+    if (const char *what = buffer_fault("work", work, "work_bytes", work_bytes_given, "tl_ms_ssim_work_bytes", plan.work_bytes))
+        return refuse(fn, what);
+    if (const int rc = tl_host::use_device(d.device)) return rc;
     const float *pool_a = keep + plan.factor_floats, *pool_b = pool_a + plan.image_floats;
     const float *pool_p = which ? pool_b : pool_a, *pool_q = which ? pool_a : pool_b;
-    const Maps maps = maps_of(g, plan, const_cast<float *>(keep));
+    const Maps maps = maps_of(d, plan, const_cast<float *>(keep));
     const float *dm = which ? maps.dm_b : maps.dm_a;
     float *grads = (float *)work;                                                  // of the pooled images, levels 1 .. M - 1
-    const size_t lds = (size_t)bwd_lds_floats(std::min(g->C, kCh)) * sizeof(float);
     for (int k = plan.M - 1; k >= 0; --k) {
         const Level &l = plan.lv[k];
-        Geo geo = level_geo(g, l, l.W);
-        const float *pp = pool_p + l.image_at, *qq = pool_q + l.image_at;
-        float *out = grads + l.image_at;
-        if (k == 0) {
-            pp = p; qq = q; out = g_p;
-            for (int d = 0; d < 4; ++d) { geo.a_s[d] = g->a_stride[d]; geo.b_s[d] = g->b_stride[d]; geo.g_s[d] = g->g_stride[d]; }
-        }
         Pyramid pyr{(const double *)keep, nullptr, k, plan.M, 0, 0};
         if (k < plan.M - 1) {
             pyr.coarse = grads + plan.lv[k + 1].image_at;
             pyr.Hc = plan.lv[k + 1].H; pyr.Wc = plan.lv[k + 1].W;
         }
-        const unsigned tiles = (unsigned)tiles_of(l.H, l.W);
-        for (int b0 = 0; b0 < g->B; b0 += kMaxY) {
-            const dim3 grid(tiles, std::min(kMaxY, g->B - b0));
-            for_k(g->K, [&](auto kk) {
-                hipLaunchKernelGGL((ssim_bwd_kernel<decltype(kk)::value, true>), grid, dim3(kBlock), lds, st, geo, pp, qq, dm + l.map_at,
-                                   maps.ds + l.map_at, maps.dc + l.map_at, g_value, out, b0, pyr);
-            });
-            if (const int rc = tl_host::launched("ssim_bwd_kernel launch (pyramid)")) return rc;
-        }
+        const int rc = launch_bwd(d, make_geo(d, l.H, l.W, l.W, k == 0), true, pyr, k ? pool_p + l.image_at : p, k ? pool_q + l.image_at : q,
+                                  dm + l.map_at, maps.ds + l.map_at, maps.dc + l.map_at, g_value, k ? grads + l.image_at : g_p,
+                                  "ssim_bwd_kernel launch (pyramid)", (hipStream_t)stream);
+        if (rc) return rc;
     }
     return TL_OK;
 }

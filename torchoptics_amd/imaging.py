@@ -520,27 +520,65 @@ def ssim_window(filter_size, filter_sigma, dtype=torch.float64):
     return torch.from_numpy(w / w.sum()).to(dtype)
 
 
-def _ssim_torch(a, b, max_value, filter_size, filter_sigma, k1, k2):
-    """The definition of ssim in plain torch ops (any device, any float dtype; autograd does the rest): two 1-D grouped
-    conv2d calls per moment.  Returns (ssim [B], S [B, Hm, Wm, C]).
-
-    The moments are taken about each image's own mean per lens and channel (a constant to autograd), which is added back to
-    the window means: variances and covariance are shift invariant, and without the shift w*a^2 - mu_a^2 subtracts two numbers
-    of size mu^2 to get one of size C2 -- on two nearly equal flat images that costs even float64 four digits of the gradient."""
-    Cc = a.shape[3]
-    w = ssim_window(filter_size, filter_sigma, a.dtype).to(a.device)
+def _ssim_blur(Cc, filter_size, filter_sigma, dtype, device):
+    """t [B, C, H, W] -> its VALID convolution with the 2-D window, as two 1-D grouped conv2d calls."""
+    w = ssim_window(filter_size, filter_sigma, dtype).to(device)
     w_row = w.reshape(1, 1, 1, -1).expand(Cc, 1, 1, -1)
     w_col = w.reshape(1, 1, -1, 1).expand(Cc, 1, -1, 1)
-    blur = lambda t: F.conv2d(F.conv2d(t, w_row, groups=Cc), w_col, groups=Cc)         # noqa: E731
-    x, y = a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)
+    return lambda t: F.conv2d(F.conv2d(t, w_row, groups=Cc), w_col, groups=Cc)
+
+
+def _ssim_moments(x, y, blur):
+    """(x0, y0, m_a, m_b, va, vb, cab) of one level x, y [B, C, H, W]: the window means m of the centred images, the
+    variances and the covariance.
+
+    The moments are taken about each image's own mean x0, y0 per lens and channel (a constant to autograd), which the caller
+    adds back to the window means: variances and covariance are shift invariant, and without the shift w*a^2 - mu_a^2
+    subtracts two numbers of size mu^2 to get one of size C2 -- on two nearly equal flat images that costs even float64 four
+    digits of the gradient."""
     x0, y0 = x.detach().mean(dim=(2, 3), keepdim=True), y.detach().mean(dim=(2, 3), keepdim=True)
     x, y = x - x0, y - y0
     m_a, m_b = blur(x), blur(y)
     va, vb, cab = blur(x * x) - m_a * m_a, blur(y * y) - m_b * m_b, blur(x * y) - m_a * m_b
+    return x0, y0, m_a, m_b, va, vb, cab
+
+
+def _ssim_torch(a, b, max_value, filter_size, filter_sigma, k1, k2):
+    """The definition of ssim in plain torch ops (any device, any float dtype; autograd does the rest).  Returns
+    (ssim [B], S [B, Hm, Wm, C])."""
+    blur = _ssim_blur(a.shape[3], filter_size, filter_sigma, a.dtype, a.device)
+    x0, y0, m_a, m_b, va, vb, cab = _ssim_moments(a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2), blur)
     mu_a, mu_b = m_a + x0, m_b + y0
     c1, c2 = (k1 * max_value) ** 2, (k2 * max_value) ** 2
     S = ((2 * mu_a * mu_b + c1) * (2 * cab + c2)) / ((mu_a * mu_a + mu_b * mu_b + c1) * (va + vb + c2))
     return S.mean(dim=(1, 2, 3)), S.permute(0, 2, 3, 1)
+
+
+def _ssim_arguments(fn, a, b, filter_size, first=None, too_large=None):
+    """The argument checks that ssim and ms_ssim (`fn` in the messages) share.  Returns (K, why_not): why_not names why the
+    kernels do not apply, or is None.  first: the message of a fault of the caller's own that is reported before the sizes
+    (ms_ssim's levels).  too_large(H, W, C): a further size that the kernels do not take; with one, the message names C."""
+    if a.dim() != 4 or b.dim() != 4:
+        raise ValueError(f"{fn}: a and b must be [B, H, W, C], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape != b.shape:
+        raise ValueError(f"{fn}: a and b must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if first is not None:
+        raise ValueError(first)
+    K = int(filter_size)
+    B, H, W, Cc = a.shape
+    if K < 1 or min(B, Cc) < 1:
+        raise ValueError(f"{fn}: filter_size and every size must be at least 1, got filter_size {K} and {tuple(a.shape)}")
+    why_not = None
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        why_not = f"dtype: a is {a.dtype}, b is {b.dtype}; the kernels are float32"
+    elif not a.is_cuda or b.device != a.device:
+        why_not = f"device: a is on {a.device}, b on {b.device}; the kernels run on one AMD GPU (there is no CPU fallback)"
+    elif K % 2 == 0 or K < 3 or K > ops.SSIM_MAX_TAPS:
+        why_not = f"K: filter_size must be odd, 3 <= filter_size <= {ops.SSIM_MAX_TAPS}, got {K}"
+    elif max(H, W) > 1 << 20 or ((H + 15) // 16) * ((W + 31) // 32) > 1 << 22 or (too_large is not None and too_large(H, W, Cc)):
+        size = f"{H} x {W} pixels" if too_large is None else f"{H} x {W} x {Cc}"
+        why_not = f"size: {size} are more than the kernels tile"
+    return K, why_not
 
 
 def ssim(a, b, max_value=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, fused=None, return_map=False):
@@ -563,25 +601,10 @@ def ssim(a, b, max_value=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03
     apply, torch otherwise.  Both paths take the second moments about a constant (the torch path about each image's mean, the
     kernels about each tile's first pixel) and add it back to the means: the fp32 variances then lose digits with the local
     contrast, not with the brightness."""
-    if a.dim() != 4 or b.dim() != 4:
-        raise ValueError(f"ssim: a and b must be [B, H, W, C], got {tuple(a.shape)} and {tuple(b.shape)}")
-    if a.shape != b.shape:
-        raise ValueError(f"ssim: a and b must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
-    K = int(filter_size)
-    B, H, W, Cc = a.shape
-    if K < 1 or min(B, Cc) < 1:
-        raise ValueError(f"ssim: filter_size and every size must be at least 1, got filter_size {K} and {tuple(a.shape)}")
+    K, why_not = _ssim_arguments("ssim", a, b, filter_size)
+    H, W = a.shape[1:3]
     if H < K or W < K:
         raise ValueError(f"ssim: H and W must be at least filter_size = {K} (the window is valid only), got {H} x {W}")
-    why_not = None
-    if a.dtype != torch.float32 or b.dtype != torch.float32:
-        why_not = f"dtype: a is {a.dtype}, b is {b.dtype}; the kernels are float32"
-    elif not a.is_cuda or b.device != a.device:
-        why_not = f"device: a is on {a.device}, b on {b.device}; the kernels run on one AMD GPU (there is no CPU fallback)"
-    elif K % 2 == 0 or K < 3 or K > ops.SSIM_MAX_TAPS:
-        why_not = f"K: filter_size must be odd, 3 <= filter_size <= {ops.SSIM_MAX_TAPS}, got {K}"
-    elif max(H, W) > 1 << 20 or ((H + 15) // 16) * ((W + 31) // 32) > 1 << 22:
-        why_not = f"size: {H} x {W} pixels are more than the kernels tile"
     if fused is None:
         fused = why_not is None and not return_map
     if not fused:
@@ -602,11 +625,8 @@ MS_SSIM_POWER_FACTORS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)        # tf.ima
 def _ms_ssim_torch(a, b, max_value, power_factors, filter_size, filter_sigma, k1, k2):
     """The definition of ms_ssim in plain torch ops (any device, any float dtype; autograd does the rest).  Returns
     (ms_ssim [B], terms [B, C, M]).  Per level the moments are taken as in _ssim_torch, about each image's detached mean."""
-    Cc, M = a.shape[3], len(power_factors)
-    w = ssim_window(filter_size, filter_sigma, a.dtype).to(a.device)
-    w_row = w.reshape(1, 1, 1, -1).expand(Cc, 1, 1, -1)
-    w_col = w.reshape(1, 1, -1, 1).expand(Cc, 1, -1, 1)
-    blur = lambda t: F.conv2d(F.conv2d(t, w_row, groups=Cc), w_col, groups=Cc)         # noqa: E731
+    M = len(power_factors)
+    blur = _ssim_blur(a.shape[3], filter_size, filter_sigma, a.dtype, a.device)
     c1, c2 = (k1 * max_value) ** 2, (k2 * max_value) ** 2
     x, y = a.permute(0, 3, 1, 2), b.permute(0, 3, 1, 2)
     terms = []
@@ -614,10 +634,7 @@ def _ms_ssim_torch(a, b, max_value, power_factors, filter_size, filter_sigma, k1
         if k:          # the 2 x 2 mean with stride 2; the last row / column of an odd side is counted twice
             pad = (0, x.shape[3] % 2, 0, x.shape[2] % 2)
             x, y = F.avg_pool2d(F.pad(x, pad, mode="replicate"), 2), F.avg_pool2d(F.pad(y, pad, mode="replicate"), 2)
-        x0, y0 = x.detach().mean(dim=(2, 3), keepdim=True), y.detach().mean(dim=(2, 3), keepdim=True)
-        xc, yc = x - x0, y - y0
-        m_a, m_b = blur(xc), blur(yc)
-        va, vb, cab = blur(xc * xc) - m_a * m_a, blur(yc * yc) - m_b * m_b, blur(xc * yc) - m_a * m_b
+        x0, y0, m_a, m_b, va, vb, cab = _ssim_moments(x, y, blur)
         q = (2 * cab + c2) / (va + vb + c2)
         if k == M - 1:
             mu_a, mu_b = m_a + x0, m_b + y0
@@ -660,31 +677,18 @@ def ms_ssim(a, b, max_value=1.0, power_factors=MS_SSIM_POWER_FACTORS, filter_siz
     tensors on one GPU, filter_size odd in 3..11; ONE C-ABI call forward for the whole pyramid and one backward per image that
     needs a gradient, no atomics, the same bits on every run.  Anything else raises a ValueError that names the reason (there
     is no CPU fallback).  `fused=None` (default): the kernels when they apply, torch otherwise."""
-    if a.dim() != 4 or b.dim() != 4:
-        raise ValueError(f"ms_ssim: a and b must be [B, H, W, C], got {tuple(a.shape)} and {tuple(b.shape)}")
-    if a.shape != b.shape:
-        raise ValueError(f"ms_ssim: a and b must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
-    K = int(filter_size)
     power = tuple(float(p) for p in power_factors)
     M = len(power)
-    B, H, W, Cc = a.shape
+    levels_fault = None
     if not 1 <= M <= ops.MS_SSIM_MAX_LEVELS:
-        raise ValueError(f"ms_ssim: levels: power_factors must hold 1 .. {ops.MS_SSIM_MAX_LEVELS} weights, got {M}")
-    if K < 1 or min(B, Cc) < 1:
-        raise ValueError(f"ms_ssim: filter_size and every size must be at least 1, got filter_size {K} and {tuple(a.shape)}")
+        levels_fault = f"ms_ssim: levels: power_factors must hold 1 .. {ops.MS_SSIM_MAX_LEVELS} weights, got {M}"
+    K, why_not = _ssim_arguments("ms_ssim", a, b, filter_size, first=levels_fault,
+                                 too_large=lambda H, W, Cc: H * W * Cc >= 1 << 31)
+    H, W = a.shape[1:3]
     for k, (h, w) in enumerate(ms_ssim_level_sizes(H, W, M)):
         if h < K or w < K:
             raise ValueError(f"ms_ssim: level {k} is {h} x {w}: every level must be at least filter_size = {K} on both sides "
                              f"(the window is valid only); {H} x {W} carries fewer than {M} levels")
-    why_not = None
-    if a.dtype != torch.float32 or b.dtype != torch.float32:
-        why_not = f"dtype: a is {a.dtype}, b is {b.dtype}; the kernels are float32"
-    elif not a.is_cuda or b.device != a.device:
-        why_not = f"device: a is on {a.device}, b on {b.device}; the kernels run on one AMD GPU (there is no CPU fallback)"
-    elif K % 2 == 0 or K < 3 or K > ops.SSIM_MAX_TAPS:
-        why_not = f"K: filter_size must be odd, 3 <= filter_size <= {ops.SSIM_MAX_TAPS}, got {K}"
-    elif max(H, W) > 1 << 20 or ((H + 15) // 16) * ((W + 31) // 32) > 1 << 22 or H * W * Cc >= 1 << 31:
-        why_not = f"size: {H} x {W} x {Cc} are more than the kernels tile"
     if fused is None:
         fused = why_not is None
     if not fused:

@@ -817,15 +817,57 @@ class WarpFunction(torch.autograd.Function):
 
 
 SSIM_MAX_TAPS = 11        # the window of the tl_ssim_* kernels: odd, 3 .. 11 taps per axis
+MS_SSIM_MAX_LEVELS = 8    # the levels of the tl_ms_ssim_* pyramid
 
-# C-ABI calls of SsimFunction since import (tests: the backward runs once per image that needs a gradient), and the pointers
-# the last forward handed to the kernel (strided views go through as they are: no copy)
+# C-ABI calls of SsimFunction / of MsSsimFunction since import (tests: the backward runs once per image that needs a gradient;
+# neither moves under the other function), and the pointers the last forward handed to the kernel (strided views go through
+# as they are: no copy)
 _ssim_calls = {"fwd": 0, "bwd": 0, "a_ptr": None, "b_ptr": None}
+_ms_ssim_calls = dict(_ssim_calls)
 
 
 def ssim_counts() -> dict:
     """{'fwd': n, 'bwd': n, 'a_ptr', 'b_ptr': data pointers of the last forward's images}."""
     return dict(_ssim_calls)
+
+
+def ms_ssim_counts() -> dict:
+    """{'fwd': n, 'bwd': n, 'a_ptr', 'b_ptr': data pointers of the last forward's images}."""
+    return dict(_ms_ssim_calls)
+
+
+def _ssim_geom(struct, a, b, window, c1, c2, flags, g, **more):
+    """tl_ssim_geom or tl_ms_ssim_geom (`struct`; `more`: the members only the latter has) of a and b with the strides they
+    have; g: the tensor the gradient is written to (a's strides without one)."""
+    B, H, W, Cc = a.shape
+    q = struct(device=a.device.index, B=B, H=H, W=W, C=Cc, K=len(window), C1=c1, C2=c2, flags=flags, **more)
+    q.window[:len(window)] = window
+    q.a_stride[:] = a.stride()
+    q.b_stride[:] = b.stride()
+    q.g_stride[:] = (g if g is not None else a).stride()
+    return q
+
+
+def _ssim_backward(fn, calls, ctx, g_value):
+    """The backward of SsimFunction and MsSsimFunction (`fn`, counting in `calls`): per image that needs a gradient, with the
+    roles and strides swapped (p the image, q_ the other one), fn._bwd(which, geometry, p, q_, kept, g_value, g_p) fills g_p
+    from `kept`, what the forward saved after the images."""
+    need_a, need_b = ctx.needs_input_grad[:2]
+    rest = (None,) * (len(ctx.needs_input_grad) - 2)
+    if g_value is None or not (need_a or need_b):
+        return (None, None) + rest
+    a, b, *kept = ctx.saved_tensors
+    g_value = g_value.to(torch.float32).contiguous()
+    grads = []
+    for which, (need, p, q_) in enumerate(((need_a, a, b), (need_b, b, a))):
+        if not need:
+            grads.append(None)
+            continue
+        g_p = torch.empty(p.shape, dtype=torch.float32, device=a.device)
+        fn._bwd(which, fn._geom(p, q_, *ctx.args, g=g_p), p, q_, kept, g_value, g_p)
+        calls["bwd"] += 1
+        grads.append(g_p)
+    return (grads[0], grads[1]) + rest
 
 
 class SsimFunction(torch.autograd.Function):
@@ -839,13 +881,7 @@ class SsimFunction(torch.autograd.Function):
 
     @staticmethod
     def _geom(a, b, window, c1, c2, flags=0, g=None):
-        B, H, W, Cc = a.shape
-        q = _lib.tl_ssim_geom(device=a.device.index, B=B, H=H, W=W, C=Cc, K=len(window), C1=c1, C2=c2, flags=flags)
-        q.window[:len(window)] = window
-        q.a_stride[:] = a.stride()
-        q.b_stride[:] = b.stride()
-        q.g_stride[:] = (g if g is not None else a).stride()
-        return q
+        return _ssim_geom(_lib.tl_ssim_geom, a, b, window, c1, c2, flags, g)
 
     @staticmethod
     def forward(ctx, a, b, window, c1, c2):
@@ -867,37 +903,13 @@ class SsimFunction(torch.autograd.Function):
         return value
 
     @staticmethod
+    def _bwd(which, q, p, q_, kept, g_value, g_p):
+        dm, ds = kept[-3:-1] if which else kept[:2]         # kept: (dm, ds) of a, then of b, as far as stored, then dc
+        _call("tl_ssim_bwd", p.device, C.byref(q), p, q_, dm, ds, kept[-1], g_value, g_p)
+
+    @staticmethod
     def backward(ctx, g_value):
-        need_a, need_b = ctx.needs_input_grad[:2]
-        if g_value is None or not (need_a or need_b):
-            return None, None, None, None, None
-        a, b, *maps = ctx.saved_tensors
-        dc = maps.pop()
-        dev = a.device
-        g_value = g_value.to(torch.float32).contiguous()
-        grads = []
-        for need, p, q_ in ((need_a, a, b), (need_b, b, a)):
-            if not need:
-                grads.append(None)
-                continue
-            dm, ds = maps.pop(0), maps.pop(0)
-            g_p = torch.empty(p.shape, dtype=torch.float32, device=dev)
-            q = SsimFunction._geom(p, q_, *ctx.args, g=g_p)
-            _call("tl_ssim_bwd", dev, C.byref(q), p, q_, dm, ds, dc, g_value, g_p)
-            _ssim_calls["bwd"] += 1
-            grads.append(g_p)
-        return grads[0], grads[1], None, None, None
-
-
-MS_SSIM_MAX_LEVELS = 8    # the levels of the tl_ms_ssim_* pyramid
-
-# C-ABI calls of MsSsimFunction since import and the pointers the last forward handed in (ssim_counts() does not move)
-_ms_ssim_calls = {"fwd": 0, "bwd": 0, "a_ptr": None, "b_ptr": None}
-
-
-def ms_ssim_counts() -> dict:
-    """{'fwd': n, 'bwd': n, 'a_ptr', 'b_ptr': data pointers of the last forward's images}."""
-    return dict(_ms_ssim_calls)
+        return _ssim_backward(SsimFunction, _ssim_calls, ctx, g_value)
 
 
 class MsSsimFunction(torch.autograd.Function):
@@ -911,14 +923,8 @@ class MsSsimFunction(torch.autograd.Function):
 
     @staticmethod
     def _geom(a, b, window, c1, c2, power, flags, g=None):
-        B, H, W, Cc = a.shape
-        q = _lib.tl_ms_ssim_geom(device=a.device.index, B=B, H=H, W=W, C=Cc, K=len(window), C1=c1, C2=c2,
-                                 levels=len(power), flags=flags)
-        q.window[:len(window)] = window
+        q = _ssim_geom(_lib.tl_ms_ssim_geom, a, b, window, c1, c2, flags, g, levels=len(power))
         q.power[:len(power)] = power
-        q.a_stride[:] = a.stride()
-        q.b_stride[:] = b.stride()
-        q.g_stride[:] = (g if g is not None else a).stride()
         return q
 
     @staticmethod
@@ -941,25 +947,14 @@ class MsSsimFunction(torch.autograd.Function):
         return value, terms
 
     @staticmethod
+    def _bwd(which, q, p, q_, kept, g_value, g_p):
+        keep, = kept
+        ws = _workspace(_lib.lib().tl_ms_ssim_work_bytes(C.byref(q)), p.device)
+        _call("tl_ms_ssim_bwd", p.device, C.byref(q), p, q_, keep, keep.numel(), g_value, g_p, which, ws, ws.numel())
+
+    @staticmethod
     def backward(ctx, g_value, _g_terms):
-        need_a, need_b = ctx.needs_input_grad[:2]
-        if g_value is None or not (need_a or need_b):
-            return (None,) * 6
-        a, b, keep = ctx.saved_tensors
-        dev = a.device
-        g_value = g_value.to(torch.float32).contiguous()
-        grads = []
-        for which, (need, p, q_) in enumerate(((need_a, a, b), (need_b, b, a))):
-            if not need:
-                grads.append(None)
-                continue
-            g_p = torch.empty(p.shape, dtype=torch.float32, device=dev)
-            q = MsSsimFunction._geom(p, q_, *ctx.args, g=g_p)
-            ws = _workspace(_lib.lib().tl_ms_ssim_work_bytes(C.byref(q)), dev)
-            _call("tl_ms_ssim_bwd", dev, C.byref(q), p, q_, keep, keep.numel(), g_value, g_p, which, ws, ws.numel())
-            _ms_ssim_calls["bwd"] += 1
-            grads.append(g_p)
-        return grads[0], grads[1], None, None, None, None
+        return _ssim_backward(MsSsimFunction, _ms_ssim_calls, ctx, g_value)
 
 
 class PupilPositionFunction(torch.autograd.Function):
