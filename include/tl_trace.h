@@ -6,7 +6,8 @@
  * stands in for (file:line under torchlens/); the Python host in torchoptics_amd/
  * mirrors the reference signatures on top of these.  The image side (image_ops.py) is here
  * too: tl_svola_* blurs an image with the lens's PSFs, tl_warp_* resamples it through the
- * distortion map and multiplies the relative illumination in.
+ * distortion map and multiplies the relative illumination in.  tl_focus_* sums the through-focus
+ * moments of a traced fan (best focus, tangential / sagittal foci, axial colour).
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless marked "host";
@@ -664,6 +665,37 @@ int tl_ms_ssim_fwd(const tl_ms_ssim_geom *g, const float *a, const float *b, flo
                    size_t keep_elems, void *work, size_t work_bytes, void *stream);
 int tl_ms_ssim_bwd(const tl_ms_ssim_geom *g, const float *p, const float *q, const float *keep, size_t keep_elems,
                    const float *g_value, float *g_p, int which, void *work, size_t work_bytes, void *stream);
+
+/*
+ * Through-focus spot moments (extension; metrics.focus_moments / metrics.through_focus stand on them).  Behind the last surface a
+ * ray is a straight line: at a plane shifted by d along +z it lands at (x + d u, y + d v), u = cx / cz, v = cy / cz, so the mean
+ * square radius of a spot is a parabola in d whose coefficients are second moments of (x, y, u, v).
+ *
+ * x, y, cx, cy (float) and ok (bytes) are [F, P, W] tensors that share ONE stride triple s_f, s_p, s_w (elements); a row is one
+ * (f, w).  A ray is LIVE iff ok != 0 and s = 1 - cx^2 - cy^2 > 0; then cz = sqrt(s).  Per row
+ *   moments[f, w, 0..10] = sum over live rays of (1, x, y, u, v, x^2, y^2, u^2, v^2, x u, y v)
+ * with every product, quotient, root and sum in fp64 from the fp32 inputs.  A dead ray adds exactly 0 whatever its coordinates hold
+ * (NaN, inf, cx^2 + cy^2 >= 1).  One partial per block goes to the workspace, a second kernel adds the partials of a row in a
+ * fixed order: no atomics, the same bits on every run.  F W < 2^31 rows are taken (the grid's y dimension is cut into launches of
+ * 65535 rows inside the call, all on `stream`, back to back), P < 2^31.  Where s_p = 1 and a row's five base addresses are aligned
+ * (16 bytes the floats, 4 the flags) a lane takes four consecutive rays with 16-byte loads, otherwise one ray at a time.
+ *
+ * tl_focus_seed: d(sum g_moments . moments) / d(x, y, cx, cy), per ray in fp64, rounded once to float, written with the inputs'
+ * strides into those of gx, gy, gcx, gcy that are not NULL (at least one):
+ *   gx = g1 + 2 x g5 + u g9,   gy = g2 + 2 y g6 + v g10,   gu = g3 + 2 u g7 + x g9,   gv = g4 + 2 v g8 + y g10,
+ *   gcx = (gu (1 - cy^2) + gv cx cy) / cz^3,   gcy = (gu cx cy + gv (1 - cx^2)) / cz^3;          a dead ray gets zeros.
+ *
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, F, P or W below 1, F W or P at
+ * or above 2^31, every output of the seed NULL.  TL_EWORKSPACE: workspace NULL or below tl_focus_workspace_bytes(F, P, W) (0 for
+ * sizes that are refused).
+ */
+size_t tl_focus_workspace_bytes(int64_t F, int64_t P, int64_t W);
+int tl_focus_moments(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const float *cx,
+                     const float *cy, const uint8_t *ok, int64_t s_f, int64_t s_p, int64_t s_w, double *moments /* [F,W,11] */,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int tl_focus_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const float *cx,
+                  const float *cy, const uint8_t *ok, int64_t s_f, int64_t s_p, int64_t s_w, const double *g_moments /* [F,W,11] */,
+                  float *gx, float *gy, float *gcx, float *gcy, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

@@ -162,6 +162,11 @@ _SIGNATURES = {
     # geom | p, q | keep, keep_elems | g_value | g_p | which | work, work_bytes | stream
     "tl_ms_ssim_bwd": (C.c_int, [C.POINTER(tl_ms_ssim_geom)] + [_VP] * 2 + [_VP, C.c_size_t] + [_VP] + [_VP] + [C.c_int]
                        + [_VP, C.c_size_t] + [_VP]),
+    "tl_focus_workspace_bytes": (C.c_size_t, [C.c_int64] * 3),
+    # device, F, P, W | x, y, cx, cy, ok | s_f, s_p, s_w | moments | workspace, bytes | stream
+    "tl_focus_moments": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 5 + [C.c_int64] * 3 + [_VP] + _WS),
+    # ... | g_moments | gx, gy, gcx, gcy | stream
+    "tl_focus_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 5 + [C.c_int64] * 3 + [_VP] + [_VP] * 4 + [_VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

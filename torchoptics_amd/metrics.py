@@ -9,10 +9,12 @@ definitions in tests/metrics_ref.py (cases and gates: tests/metrics_cases.py, te
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import ops, paraxial
-from .ray_tracing import RayTracer, apply_vignetting
+from .ray_tracing import RayTracer, _root_of_variance, apply_vignetting
 
 
 def compute_distortion(specs, lens, relative_fields, default_device="cuda"):
@@ -212,3 +214,129 @@ def psf_from_trace(x, y, ray_ok=None, n_bins=(21, 21), increment=None, y_target=
         w = ray_ok.permute(0, 1, 3, 2)
     return compute_psf(xt, yt, n_bins=n_bins, increment=increment, y_target=y_target, weights=w, y_extent=y_extent,
                        fused=fused)
+
+
+# ---------------------------------------------------------------------------- through-focus spot moments
+class ThroughFocus(NamedTuple):
+    """What through_focus returns; every member is [B, F, W] less the pooled dimensions."""
+    n: torch.Tensor                 # live rays
+    rms: torch.Tensor               # RMS spot radius at the plane the rays were traced to
+    best_focus: torch.Tensor        # shift of the image plane along +z that minimises it
+    rms_best: torch.Tensor          # RMS spot radius there
+    focus_t: torch.Tensor           # tangential focus: the shift that minimises the y extent
+    focus_s: torch.Tensor           # sagittal focus: the shift that minimises the x extent
+    a: torch.Tensor                 # R^2(d) = a + 2 b d + c d^2
+    b: torch.Tensor
+    c: torch.Tensor
+
+
+FOCUS_SLOPE_FLOOR = 2.0 ** -40      # a centred slope sum at or below this share of its raw sum is rounding noise: no focus
+
+
+def _focus_uses_kernels(fused, tensors, where):
+    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
+               and all(t.dtype == torch.float32 for t in tensors[:4]))
+    if fused and not applies:
+        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the focus kernels run only "
+                           "on float32 tensors on one AMD GPU (there is no CPU fallback): use fused=False")
+    return applies if fused is None else bool(fused)
+
+
+def _focus_moments_torch(x, y, cx, cy, ray_ok):
+    """The definition of focus_moments in torch ops, in float64."""
+    x, y, cx, cy = (t.to(torch.float64) for t in (x, y, cx, cy))
+    live = (ray_ok != 0) & (1 - cx * cx - cy * cy > 0)                # (NaN > 0 is false)
+    zero = x.new_zeros(())
+    # a dead ray is the ray (0, 0, 0, 0) that is not counted: nothing of what it holds reaches a sum or a gradient
+    x, y, cx, cy = (torch.where(live, t, zero) for t in (x, y, cx, cy))
+    cz = torch.sqrt(1 - cx * cx - cy * cy)
+    u, v = cx / cz, cy / cz
+    terms = (live.to(torch.float64), x, y, u, v, x * x, y * y, u * u, v * v, x * u, y * v)
+    return torch.stack([t.sum(dim=2) for t in terms], dim=-1)
+
+
+def focus_moments(x, y, cx, cy, ray_ok, fused=None):
+    """The eleven through-focus moments M [B, F, W, 11] (float64) of a traced fan: per row (lens, field, wavelength)
+
+        M[row, 0..10] = sum over the live rays of (1, x, y, u, v, x^2, y^2, u^2, v^2, x u, y v),   u = cx / cz, v = cy / cz.
+
+    x, y, cx, cy, ray_ok: [B, F, P, W] as RayTracer.trace_rays returns them, broadcastable.  A ray is live iff ray_ok != 0 and
+    s = 1 - cx^2 - cy^2 > 0; then cz = sqrt(s).  A dead ray adds exactly 0 to every moment and receives exactly 0 gradient,
+    whatever its coordinates hold (NaN, +-inf, 1e30, cx^2 + cy^2 >= 1).  Differentiable in x, y, cx, cy.
+    `fused`: False -- these sums in torch ops, upcast to float64, on any device and float dtype; True -- the HIP kernels
+    (ops.FocusMomentsFunction: float32 tensors on one AMD GPU, anything else raises); None -- the kernels where they apply.
+    Either way every product and sum is in float64: the raw second moment of y is ~4e5 times the variance taken from it."""
+    use = _focus_uses_kernels(fused, (x, y, cx, cy, ray_ok), "focus_moments")
+    x, y, cx, cy, ray_ok = torch.broadcast_tensors(x, y, cx, cy, ray_ok)
+    if x.dim() != 4:
+        raise ValueError(f"focus_moments takes [B, F, P, W] tensors, got {tuple(x.shape)}")
+    if use:
+        return ops.FocusMomentsFunction.apply(x, y, cx, cy, ray_ok)
+    return _focus_moments_torch(x, y, cx, cy, ray_ok)
+
+
+def _quotient(num, den, raw):
+    """num / den where den > 2^-40 raw, else 0 with zero gradient (the rule of _root_of_variance for a quotient)."""
+    good = den > FOCUS_SLOPE_FLOOR * raw
+    return torch.where(good, num / torch.where(good, den, torch.ones_like(den)), torch.zeros_like(den))
+
+
+def through_focus_from_moments(M, common=("wavelength",), centroid="row", dtype=None):
+    """The finish of through_focus on the moments M [B, F, W, 11] of focus_moments: plain torch in float64, differentiable."""
+    common = tuple(common)
+    if any(c not in ("field", "wavelength") for c in common):
+        raise ValueError("common must be a subset of ('field', 'wavelength')")
+    if centroid not in ("row", "field"):
+        raise ValueError("centroid must be 'row' or 'field'")
+    if centroid == "field" and "wavelength" not in common:
+        raise ValueError("centroid='field' sums the moments over wavelengths first: 'wavelength' must be in common")
+    dtype = dtype or M.dtype
+    M = M.to(torch.float64)
+    if centroid == "field":
+        M = M.sum(dim=2, keepdim=True)
+    n = M[..., 0]
+    n1 = n.clamp(min=1.0)                       # (a row with n = 0 has M = 0: it adds nothing)
+
+    def centred(q, s, qq, ss, qs):
+        return (M[..., qq] - M[..., q] * M[..., q] / n1, M[..., qs] - M[..., q] * M[..., s] / n1,
+                M[..., ss] - M[..., s] * M[..., s] / n1)
+    Ax, Bx, Cx = centred(1, 3, 5, 7, 9)
+    Ay, By, Cy = centred(2, 4, 6, 8, 10)
+    raw_x, raw_y = M[..., 7], M[..., 8]
+    dims = [d for d, name in ((1, "field"), (2, "wavelength")) if name in common]
+    if dims:
+        n, Ax, Ay, Bx, By, Cx, Cy, raw_x, raw_y = (t.sum(dim=dims) for t in (n, Ax, Ay, Bx, By, Cx, Cy, raw_x, raw_y))
+    A, B, C = Ax + Ay, Bx + By, Cx + Cy
+    n1 = n.clamp(min=1.0)
+    q = _quotient(B, C, raw_x + raw_y)
+    out = ThroughFocus(n=n, rms=_root_of_variance(A / n1), best_focus=-q, rms_best=_root_of_variance((A - B * q) / n1),
+                       focus_t=-_quotient(By, Cy, raw_y), focus_s=-_quotient(Bx, Cx, raw_x), a=A / n1, b=B / n1, c=C / n1)
+    return ThroughFocus(*(t.to(dtype) for t in out))
+
+
+def through_focus(x, y, cx, cy, ray_ok, common=("wavelength",), centroid="row", fused=None):
+    """Best focus, tangential / sagittal foci and the RMS spot radius through focus, from the rays as they stand.
+
+    Behind the last surface a ray is a straight line: at an image plane shifted by d along +z (the sign of adding d to the
+    last thickness) it lands at (x + d u, y + d v), u = cx / cz, v = cy / cz.  The mean square radius of a spot about its
+    centroid is therefore a parabola R^2(d) = a + 2 b d + c d^2 whose coefficients are second moments of (x, y, u, v).
+
+    x, y, cx, cy, ray_ok: [B, F, P, W] as RayTracer.trace_rays returns them, broadcastable.  A ROW is one (lens, field,
+    wavelength); its eleven moments M (focus_moments; live rays only) give, for n = M0 > 0, the centred sums
+        Ax = M5 - M1^2 / n,   Bx = M9 - M1 M3 / n,   Cx = M7 - M3^2 / n,      Ay, By, Cy likewise from columns 2, 4, 6, 8, 10.
+    Rows are pooled over the dimensions named in `common` (a subset of ("field", "wavelength"), possibly empty) by adding
+    n, Ax, Ay, Bx, By, Cx, Cy: ONE focal plane for the pooled rays, each row about its own centroid.  centroid="field" sums
+    the raw M over wavelengths first -- one centroid per field, so lateral colour counts as spot size (needs "wavelength" in
+    `common`).  Over a pooled set, with A = Ax + Ay, B = Bx + By, C = Cx + Cy:
+        a = A / n, b = B / n, c = C / n          rms = sqrt(a)                    best_focus = -B / C
+        rms_best = sqrt((A - B^2 / C) / n)       focus_t = -By / Cy               focus_s = -Bx / Cx
+    Degenerate cases: the square root of a value <= 0 is 0 with zero gradient; a quotient whose denominator D (C, Cx, Cy) is
+    <= 2^-40 times its raw second moment (M7 + M8, M7, M8) is 0 with zero gradient, and then rms_best = rms.  fp32 slopes
+    carry relative errors of 2^-24, so a relative slope variance near 2^-48 is the inputs' rounding noise; 2^-40 is that with a
+    margin of 256.  This covers n <= 1, a collimated bundle and a purely meridional fan (no sagittal focus).
+
+    Returns ThroughFocus(n, rms, best_focus, rms_best, focus_t, focus_s, a, b, c), each [B, F, W] with the pooled dimensions
+    removed, in the dtype of x; differentiable in x, y, cx, cy.  `fused`: as for focus_moments (the kernels form M; this
+    finish is plain float64 torch on tiny tensors either way)."""
+    M = focus_moments(x, y, cx, cy, ray_ok, fused=fused)
+    return through_focus_from_moments(M, common, centroid, dtype=x.dtype)

@@ -117,12 +117,14 @@ _ws_cache = {}
 
 # optional live timing of the C-ABI calls with events on the launch stream (bench.py)
 _timing = None
+_timing_named = None       # the same for calls that are not the trace's, under their entry point's name (named_timing_ms)
 
 
 def enable_timing(on: bool = True) -> None:
     """Record a (start, stop) event pair around every tl_trace_fwd / tl_trace_bwd call."""
-    global _timing
+    global _timing, _timing_named
     _timing = {"fwd": [], "bwd": []} if on else None
+    _timing_named = {} if on else None
     if _ext() is not None:
         _ext().enable_timing(bool(on))
 
@@ -146,6 +148,13 @@ def timing_ms() -> dict:
     return out
 
 
+def named_timing_ms() -> dict:
+    """Mean GPU milliseconds per call, by entry point, of the timed calls outside the trace (tl_focus_moments, tl_focus_seed)
+    since enable_timing(); synchronises the device."""
+    torch.cuda.synchronize()
+    return {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in (_timing_named or {}).items()}
+
+
 class _Timed:
     def __init__(self, key, dev):
         self.key, self.dev = key, dev
@@ -159,7 +168,7 @@ class _Timed:
     def __exit__(self, *exc):
         if _timing is not None:
             self.b.record(torch.cuda.current_stream(self.dev))
-            _timing[self.key].append((self.a, self.b))
+            (_timing[self.key] if self.key in _timing else _timing_named.setdefault(self.key, [])).append((self.a, self.b))
 
 
 class _NoCtx:
@@ -181,7 +190,8 @@ def _on_device(dev):
 def _call(name, dev, *args, timed=None):
     """Call the launching C-ABI entry `name` on the current stream of `dev`: tensors go as their device pointers (None ->
     NULL), everything else (ints, floats, byref structs, pointer blocks) as it is, the stream last.  `timed`: 'fwd' /
-    'bwd' records the call for timing_ms() while enable_timing() is on.  A non-zero return code raises."""
+    'bwd' records the call for timing_ms() while enable_timing() is on, any other name for named_timing_ms().  A non-zero
+    return code raises."""
     with _on_device(dev), (_Timed(timed, dev) if timed is not None else _NO_CTX):
         rc = getattr(_lib.lib(), name)(*[_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in args],
                                        _stream_ptr(dev))
@@ -470,6 +480,77 @@ class SpotMomentsFunction(torch.autograd.Function):
         _call("tl_spot_seed", dev, dev.index, F, P, W, xs if ctx.has_x else None, y, oks, y.stride(1), y.stride(2),
               y.stride(3), gm, gx, gy)
         return gx, gy, None
+
+
+FOCUS_NMOM = 11            # per (field, wavelength): sums of 1, x, y, u, v, x^2, y^2, u^2, v^2, x u, y v over the live rays
+
+
+def _same_layout(t, shape, stride):
+    """Whether t's elements sit at the given strides (the stride of a dimension of size 1 addresses nothing)."""
+    return all(n == 1 or a == b for n, a, b in zip(shape, t.stride(), stride))
+
+
+def _focus_layout(tensors):
+    """The stride quadruple [B,F,P,W] the focus kernels read all five arrays with: that of the first float32 tensor that is
+    not expanded and whose lenses fold into its fields (B = 1, F = 1, or stride(0) = F stride(1)) -- the tracer's [1,F,P,W]
+    views of [F,W,P] memory are -- or the tracer's own layout."""
+    shape = tensors[0].shape
+    B, F = shape[0], shape[1]
+    for t in tensors:
+        st = t.stride()
+        if (t.dtype == torch.float32 and all(n == 1 or s > 0 for n, s in zip(shape, st))
+                and (B == 1 or F == 1 or st[0] == F * st[1])):
+            return st
+    B, F, P, W = shape
+    return (F * W * P, W * P, 1, P)
+
+
+class FocusMomentsFunction(torch.autograd.Function):
+    """moments [B, F, W, FOCUS_NMOM] (float64) of per-ray tensors x, y, cx, cy, ok, all of ONE shape [B, F, P, W] (the caller
+    broadcasts, under autograd): tl_focus_moments forward, tl_focus_seed backward.  The five arrays are brought to one common
+    stride quadruple -- the tracer's [1,F,P,W] views of [F,W,P] memory are read in place, only what is expanded or strided
+    differently is copied -- and B is folded into F."""
+
+    @staticmethod
+    def forward(ctx, x, y, cx, cy, ok):
+        rays = {"x": x, "y": y, "cx": cx, "cy": cy}
+        for name, t in rays.items():
+            _require_device(t, name)
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"torchoptics_amd: the focus kernels take float32 tensors; `{name}` is {t.dtype} "
+                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        _require_device(ok, "ray_ok")
+        dev, shape = x.device, x.shape
+        B, F, P, W = shape
+        st = _focus_layout((x, y, cx, cy))
+
+        def placed(t):
+            return t if _same_layout(t, shape, st) else torch.empty_strided(shape, st, dtype=t.dtype, device=dev).copy_(t)
+        x, y, cx, cy = (placed(t) for t in (x, y, cx, cy))
+        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
+        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
+        moments = torch.empty((B, F, W, FOCUS_NMOM), dtype=torch.float64, device=dev)
+        ws = _workspace(_lib.lib().tl_focus_workspace_bytes(B * F, P, W), dev)
+        _call("tl_focus_moments", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], moments, ws, ws.numel(),
+              timed="tl_focus_moments")
+        ctx.save_for_backward(x, y, cx, cy, oks)
+        ctx.layout = (st, s_f)
+        return moments
+
+    @staticmethod
+    def backward(ctx, gmom):
+        x, y, cx, cy, oks = ctx.saved_tensors
+        dev, shape = x.device, x.shape
+        B, F, P, W = shape
+        st, s_f = ctx.layout
+        gm = gmom.to(torch.float64).contiguous()
+        outs = [torch.empty_strided(shape, st, dtype=torch.float32, device=dev) if need else None
+                for need in ctx.needs_input_grad[:4]]
+        if all(o is None for o in outs):
+            return (None,) * 5
+        _call("tl_focus_seed", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], gm, *outs,
+              timed="tl_focus_seed")
+        return (*outs, None)
 
 
 PSF_MAX_BINS = 32          # rows / columns of the half kernel tl_psf_accumulate takes (one 32x32 MFMA tile)
