@@ -121,7 +121,7 @@ struct Layout {
     size_t mom, ck, inv, inv_fb;  // bytes of the partial arrays: the first three start at 0, the fallback's at `inv`
     size_t scan, total;
 
-    tl_part part(void *ws, const Plan &pl, size_t off = 0) const { return {(double *)((char *)ws + off), pl.nbx, pl.R}; }
+    tl_part part(void *ws, const Plan &pl, size_t off = 0) const { return {(double *)((char *)ws + off), pl.nbx}; }
     unsigned *poison(void *ws) const { return (unsigned *)((char *)ws + total - 64); }
 };
 

@@ -41,10 +41,10 @@ struct tl_fallback {
     const uint8_t *dead_ok;
 };
 
-// One array of block partials in the workspace and the plan of the launch that fills it: nbx blocks per grid row, each
-// thread tracing up to R rays.  What tl_walkback carries down to a walk-back launch: its own partials, those of the
-// checkpoint launch queued behind it, and the poison word / token that tell the two apart (see tl_fallback).
-struct tl_part { double *part; int nbx, R; };
+// One array of block partials in the workspace and the grid of the launch that fills it: nbx blocks per grid row (rays
+// per thread follow from the grid: TL_BLOCK_CHUNKS).  What tl_walkback carries down to a walk-back launch: its own partials,
+// those of the checkpoint launch queued behind it, and the poison word / token that tell the two apart (see tl_fallback).
+struct tl_part { double *part; int nbx; };
 struct tl_walkback {
     tl_part inv, ck;
     unsigned *poison;

@@ -880,6 +880,32 @@ __device__ __forceinline__ tl_problem lens_view(tl_problem p, const int b)
     const int lens_ = gf / (PA_).F, f = gf - lens_ * (PA_).F;                                       \
     const tl_problem p = lens_view(PA_, lens_)
 
+// ------------------------------------------------------------------ block stages shared by the trace kernels
+// A stage that several kernels have is written once where every instantiation keeps the instruction stream it had with
+// the stage in place (tools/isa_compare.py; record: profiles/kernels_shared_stages.txt).  An inline function is simplified
+// on its own before it is inlined, so that holds for few of them: store_moment_partials here; the walk-backs' shared
+// stages are macros (in front of trace_bwd_inv_kernel).  The field-row prologue (z0 .. yoff), the forward's image plane
+// and the backward's moment seeds moved instructions in every shared form and stay written out per kernel.
+
+// Epilogue of the forward kernels: the lane sums of a block -> its row of moment partials, stored [column][block].
+__device__ __forceinline__ void store_moment_partials(const double (&m)[TL_NMOM], double *__restrict__ part, const int fw)
+{
+    __shared__ double red[kWaves][TL_NMOM];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < TL_NMOM; ++j) {
+        const double v = wave_sum(m[j]);
+        if (lane == 0) red[wv][j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < TL_NMOM) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < kWaves; ++q) s += red[q][threadIdx.x];
+        part[(size_t)threadIdx.x * ((size_t)gridDim.y * gridDim.x) + ((size_t)fw * gridDim.x + blockIdx.x)] = s;   // [column][block]
+    }
+}
+
 // ------------------------------------------------------------------ forward kernel
 // grid (NBX, F*W), block kBlock; each thread traces R rays.
 // part : [gridDim.y * gridDim.x][TL_NMOM] per-block moment partials (or nullptr)
@@ -902,7 +928,7 @@ template <bool PEN, bool ASPH, bool OPD>
 __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
     const tl_problem pa, float *__restrict__ ox, float *__restrict__ oy, float *__restrict__ ocx,
     float *__restrict__ ocy, uint8_t *__restrict__ ook, uint8_t *__restrict__ oback,
-    float *__restrict__ oopd, float *__restrict__ stk, double *__restrict__ part, const int /*plan hint, unused*/)
+    float *__restrict__ oopd, float *__restrict__ stk, double *__restrict__ part)
 {
     // Fast mode, all-spherical lens: this instantiation only ever writes the path length behind trace_fwd_plain_kernel
     // (launch_fwd), and `ook` then holds that kernel's ok bytes, to be read: under contraction the two bodies round
@@ -1067,20 +1093,7 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_kernel(
     }
     if (part) {
         m[3] = (double)n_ok; m[7] = (double)n_back; m[9] = (double)n_ill;
-        __shared__ double red[kWaves][TL_NMOM];
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int j = 0; j < TL_NMOM; ++j) {
-            const double v = wave_sum(m[j]);
-            if (lane == 0) red[wv][j] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < TL_NMOM) {
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < kWaves; ++q) s += red[q][threadIdx.x];
-            part[(size_t)threadIdx.x * ((size_t)gridDim.y * gridDim.x) + ((size_t)fw * gridDim.x + blockIdx.x)] = s;   // [column][block]
-        }
+        store_moment_partials(m, part, fw);
     }
 }
 
@@ -1093,7 +1106,7 @@ template <int RPL>
 __global__ __launch_bounds__(kBlock) void trace_fwd_plain_kernel(
     const tl_problem pa, float *__restrict__ ox, float *__restrict__ oy, float *__restrict__ ocx,
     float *__restrict__ ocy, uint8_t *__restrict__ ook, uint8_t *__restrict__ oback,
-    double *__restrict__ part, const int /*plan hint, unused*/)
+    double *__restrict__ part)
 {
     TL_LENS_ROW(pa);
     TL_BLOCK_CHUNKS(p.P);
@@ -1197,20 +1210,7 @@ __global__ __launch_bounds__(kBlock) void trace_fwd_plain_kernel(
     }
     if (part) {
         m[3] = (double)n_ok; m[7] = (double)n_back; m[9] = (double)n_ill;
-        __shared__ double red[kWaves][TL_NMOM];
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int j = 0; j < TL_NMOM; ++j) {
-            const double v = wave_sum(m[j]);
-            if (lane == 0) red[wv][j] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < TL_NMOM) {
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < kWaves; ++q) s += red[q][threadIdx.x];
-            part[(size_t)threadIdx.x * ((size_t)gridDim.y * gridDim.x) + ((size_t)fw * gridDim.x + blockIdx.x)] = s;   // [column][block]
-        }
+        store_moment_partials(m, part, fw);
     }
 }
 
@@ -1240,7 +1240,7 @@ template <int NS, bool ASPH, int PEN>
 __global__ __launch_bounds__(kBlock, TL_BWD_WAVES(NS)) void trace_bwd_kernel(
     const tl_problem pa, const float *__restrict__ gx, const float *__restrict__ gy,
     const float *__restrict__ gcx, const float *__restrict__ gcy, const double *__restrict__ gmom,
-    float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part, const int /*plan hint, unused*/,
+    float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part,
     const double *__restrict__ fb_mom, const unsigned *__restrict__ fb_poison, const unsigned fb_token,
     const float *__restrict__ gopd, const uint8_t *__restrict__ dead_ok, const float *__restrict__ gstk)
 {
@@ -1542,6 +1542,71 @@ __device__ __forceinline__ double uniform_f64(const double v)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+// ------------------------------------------------------------------ stages shared by the two walk-back kernels
+// Macros: as inline functions each of them changed the register assignment or the instruction order of walk-back
+// instantiations (profiles/kernels_shared_stages.txt); expanded in place they are the code that was there.
+// TL_HIT: intersect the line (q, d) with a sphere of curvature c whose vertex is the origin (closed form of
+// find_marching_distance_spherical; the signed distance DB is negative when walking against d); COS = cosine between d
+// and the normal at the hit, RCOS its reciprocal.  AFTER_COS_ names what else is formed from the intermediates:
+// TL_HIT_PLAIN nothing, TL_HIT_S2T the caller's `s2t` (PEN: sin^2 on the refraction side, see
+// trace_bwd_inv_unrolled_kernel).
+#define TL_HIT_PLAIN(c_, ddx, ddy, tmp_)
+#define TL_HIT_S2T(c_, ddx, ddy, tmp_) if (PEN) s2t = ((ddx) * (ddx) + (ddy) * (ddy)) + (c_) * tmp_;
+#define TL_HIT(AFTER_COS_, c_, qx_, qy_, qz_, ddx, ddy, ddz, HX, HY, HZ, COS, RCOS, DB)  \
+        {                                                                                \
+            const float e_ = -(((qx_) * (ddx) + (qy_) * (ddy)) + (qz_) * (ddz));         \
+            const float mz_ = (qz_) + e_ * (ddz);                                        \
+            const float m2_ = (((qx_) * (qx_) + (qy_) * (qy_)) + (qz_) * (qz_)) - e_ * e_; \
+            const float tmp_ = (c_) * m2_ - 2.0f * mz_;                                  \
+            const float cos2_ = (ddz) * (ddz) - (c_) * tmp_;                             \
+            tl_rsq_sqrt(cos2_, RCOS, COS);                                               \
+            AFTER_COS_(c_, ddx, ddy, tmp_)                                               \
+            DB = e_ + tmp_ * tl_rcp((ddz) + COS);                                        \
+            HX = (qx_) + DB * (ddx); HY = (qy_) + DB * (ddy); HZ = (qz_) + DB * (ddz);   \
+        }
+
+// TL_WALK_ENTRANCE_SUMS declares the entrance adjoints of a lane, summed over its rays in fp64 (see trace_bwd_kernel):
+// acc_z, acc_cx, acc_cy.  The cz term is folded into cx and cy per ray (cz0 = sqrt(1 - cx0^2 - cy0^2): d cz0 / d cx0 =
+// -cx0 / cz0), which saves a fourth fp64 sum; k_cx, k_cy are wave-uniform: moved to SGPRs, they cost no vector register.
+#define TL_WALK_ENTRANCE_SUMS(cx0_, cy0_)                                                                            \
+    const double rcz0_ = 1.0 / sqrt((1.0 - (double)(cx0_) * (double)(cx0_)) - (double)(cy0_) * (double)(cy0_));      \
+    const double k_cx = uniform_f64(-(double)(cx0_) * rcz0_), k_cy = uniform_f64(-(double)(cy0_) * rcz0_);           \
+    double acc_z = 0.0, acc_cx = 0.0, acc_cy = 0.0
+// TL_WALK_ENTRANCE_ADD: one ray's adjoint `a` at the entrance.  Every term of the sweep is linear in the adjoint, so
+// anything non-finite on the way (cannot happen for a ray the forward kept and called well-conditioned, short of a
+// pathological prescription) is still there: flag it, and the checkpoint kernel redoes the launch bit-faithfully.
+// (A plain store: an atomic here makes the compiler treat every later load of the prescription as clobbered and turn
+// the per-surface scalar loads into vector loads, +4 % on the whole kernel.)
+#define TL_WALK_ENTRANCE_ADD(a_)                                                                                     \
+        const float fin_ = (((a_).x + (a_).y) + ((a_).z + (a_).cz)) + ((a_).cx + (a_).cy);                           \
+        if (!(fin_ - fin_ == 0.0f)) *poison = token;                                                                 \
+        acc_z += (double)(a_).z;                                                                                     \
+        acc_cx += (double)(a_).cx + k_cx * (double)(a_).cz;                                                          \
+        acc_cy += (double)(a_).cy + k_cy * (double)(a_).cz
+
+// TL_WALK_STORE_PARTIALS: block reduction of the walk-backs (fixed order).  The entrance sums go through `red`; of the
+// quad-transposed rows sacc_dyn[ROWS_][kBlock] (lane q of a quad holds term q: g_c, g_t, g_mu) wave wv reduces rows wv,
+// wv+4, ...: lane, lane+64, ... hold the same term (64 = 0 mod 4), the butterfly over lane bits 2..5 leaves each lane
+// with the total of its own term.  Declares `row`, this block's row of partials, and `nrows_`: partials are stored
+// [column][block] (the reduction kernels then read each column as one contiguous run).  Reads `lane`, `wv`, `tid`.
+#define TL_WALK_STORE_PARTIALS(ROWS_)                                                                                \
+    {                                                                                                                \
+        const double a0 = wave_sum(acc_z), a1 = wave_sum(acc_cx), a2 = wave_sum(acc_cy);                             \
+        if (lane == 0) { red[wv][0] = a0; red[wv][1] = a1; red[wv][2] = a2; }                                        \
+    }                                                                                                                \
+    __syncthreads();                                                                                                 \
+    const size_t nrows_ = (size_t)gridDim.y * gridDim.x;                                                             \
+    double *row = part + ((size_t)fw * gridDim.x + blockIdx.x);                                                      \
+    for (int k = wv; k < (ROWS_); k += kWaves) {                                                                     \
+        const float *q = sacc_dyn + (size_t)k * kBlock;                                                              \
+        double v = (double)q[lane] + (double)q[lane + 64];                                                           \
+        v += (double)q[lane + 128];                                                                                  \
+        v += (double)q[lane + 192];                                                                                  \
+        _Pragma("unroll") for (int o = 32; o >= 4; o >>= 1) v += __shfl_xor(v, o, 64);                               \
+        if (lane < 3) row[(size_t)(lane * (ROWS_) + k) * nrows_] = v;                                                \
+    }                                                                                                                \
+    if (tid < 3) row[(size_t)(3 * (ROWS_) + tid) * nrows_] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid]
+
 // ------------------------------------------------------------------ checkpoint-free backward
 // Alternative to trace_bwd_kernel for lenses with allow_backward_rays (no penalty term):
 // instead of re-tracing the ray forwards and keeping the state entering every surface in registers,
@@ -1567,10 +1632,13 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
     const float *__restrict__ gcx, const float *__restrict__ gcy, const double *__restrict__ gmom,
     const float *__restrict__ fx, const float *__restrict__ fy, const float *__restrict__ fcx,
     const float *__restrict__ fcy, const uint8_t *__restrict__ fok, const double *__restrict__ fmom,
-    float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part, const int /*plan hint, unused*/,
+    float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part, const int /*unused, see below*/,
     unsigned *__restrict__ poison, const unsigned token)
 {
 #pragma clang fp contract(fast)       // see TL_REVERSE_CONTRACT above
+    // (The unused int -- once a plan hint, launched as 0 -- keeps this kernel's argument layout: without it the register-
+    //  bound <true> instantiation is allocated differently and loses 3 (strict) / 6 (fast) instructions, unmeasured.  The
+    //  other trace kernels dropped theirs with the same opcodes in the same order; profiles/kernels_shared_stages.txt.)
     // the forward saw an ill-conditioned live ray: the checkpoint kernel (launched next to this one) does
     // the whole batch bit-faithfully instead, and this launch retires at once
     // -- unless it also left per-ray flags (pa.cond_flags; `fok` is then that array: 0 dead, 1 live, 2 live and
@@ -1602,12 +1670,7 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
         gm0 = q[0]; gm1 = q[1]; gm2 = q[2]; gm4 = q[4]; gm5 = q[5]; gm6 = q[6];
     }
     for (int j = 0; j < S; ++j) sacc_dyn[j * kBlock + tid] = 0.0f;         // own slots only: no barrier needed
-    // entrance adjoints summed per lane in fp64: g_z and g_cy are small residuals (~1e-3) of large per-ray
-    // terms, so the fp32 rounding of a running sum over the rays of a lane would show up 1000-fold
-    // (the cz sum is folded into cx and cy per ray with wave-uniform SGPR factors: see trace_bwd_inv_unrolled_kernel)
-    const double rcz0_ = 1.0 / sqrt((1.0 - (double)cx0 * (double)cx0) - (double)cy0 * (double)cy0);
-    const double k_cx = uniform_f64(-(double)cx0 * rcz0_), k_cy = uniform_f64(-(double)cy0 * rcz0_);
-    double acc_z = 0.0, acc_cx = 0.0, acc_cy = 0.0;
+    TL_WALK_ENTRANCE_SUMS(cx0, cy0);
     // 1/mu[k] is wave-uniform: computed once per block into LDS instead of once per ray and surface
     __shared__ float s_inv_mu[TL_MAX_SURFACES];
     if (tid < S) s_inv_mu[tid] = 1.0f / uload(mu_w, tid);
@@ -1655,20 +1718,7 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
             sy += alive ? (float)(gm0 + (gm1 + 2.0 * (double)yi * gm2)) : 0.0f;   // dead lanes walk an axial ray
             sx += alive ? (float)(gm4 + (gm5 + 2.0 * (double)xi * gm6)) : 0.0f;   // with zero seeds: exact zeros
         }
-        // ---- walk back from the image plane.  hit_sphere: intersect the line (q, d) with a sphere of
-        //      curvature c whose vertex is the origin (closed form of find_marching_distance_spherical; the
-        //      signed distance is negative here); cos = cosine between d and the normal at the hit.
-#define TL_HIT(c_, qx_, qy_, qz_, ddx, ddy, ddz, HX, HY, HZ, COS, RCOS, DB)             \
-        {                                                                                \
-            const float e_ = -(((qx_) * (ddx) + (qy_) * (ddy)) + (qz_) * (ddz));         \
-            const float mz_ = (qz_) + e_ * (ddz);                                        \
-            const float m2_ = (((qx_) * (qx_) + (qy_) * (qy_)) + (qz_) * (qz_)) - e_ * e_; \
-            const float tmp_ = (c_) * m2_ - 2.0f * mz_;                                  \
-            const float cos2_ = (ddz) * (ddz) - (c_) * tmp_;                             \
-            tl_rsq_sqrt(cos2_, RCOS, COS);                                               \
-            DB = e_ + tmp_ * tl_rcp((ddz) + COS);                                        \
-            HX = (qx_) + DB * (ddx); HY = (qy_) + DB * (ddy); HZ = (qz_) + DB * (ddz);   \
-        }
+        // ---- walk back from the image plane (TL_HIT: the closed-form hit on a spherical row)
         Adj a;
         float hx, hy, hz, cos_t, r_t;                 // hit on surface k (frame k), refraction-side cosine there
         {
@@ -1679,7 +1729,7 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
                 hit_asph(load_asph(p, S - 1), qx, qy, tl, dx, dy, dz, alive, hx, hy, hz, db);
                 cos_t = r_t = 1.0f;                                // recomputed from the aspheric normal below
             } else {
-                TL_HIT(uload(p.c, S - 1), qx, qy, tl, dx, dy, dz, hx, hy, hz, cos_t, r_t, db);
+                TL_HIT(TL_HIT_PLAIN, uload(p.c, S - 1), qx, qy, tl, dx, dy, dz, hx, hy, hz, cos_t, r_t, db);
             }
             // image-plane adjoint: x_img = x_S + dist*cx', dist = -z_S/cz' = -db
             const float dist = -db, inv_cz = tl_rcp(dz);
@@ -1759,7 +1809,7 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
                 if (ASPH && ((kbits >> (k - 1)) & 1u)) {
                     hit_asph(load_asph(p, k - 1), hx, hy, hzs, ix, iy, iz, alive, px, py, pz, db);
                 } else {
-                    TL_HIT(uload(p.c, k - 1), hx, hy, hzs, ix, iy, iz, px, py, pz, cos_t, r_t, db);
+                    TL_HIT(TL_HIT_PLAIN, uload(p.c, k - 1), hx, hy, hzs, ix, iy, iz, px, py, pz, cos_t, r_t, db);
                 }
                 in.x = px; in.y = py; in.z = pz - tp;
                 in.cx = ix; in.cy = iy; in.cz = iz;
@@ -1801,17 +1851,7 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
             sacc_dyn[k * kBlock + tid] += quad_term_sums(g_c, g_t, g_mu, q_odd, q_hi);
             dx = ix; dy = iy; dz = iz;                             // the ray between surfaces k-1 and k
         }
-#undef TL_HIT
-        // every term of the sweep is linear in the adjoint, so anything non-finite on the way (cannot happen
-        // for a ray the forward kept and called well-conditioned, short of a pathological prescription) is
-        // still there at the entrance: flag it, and the checkpoint kernel redoes the launch bit-faithfully
-        const float fin_ = ((a.x + a.y) + (a.z + a.cz)) + (a.cx + a.cy);
-        // (a plain store: an atomic here makes the compiler treat every later load of the prescription as
-        // clobbered and turn the per-surface scalar loads into vector loads, +4 % on the whole kernel)
-        if (!(fin_ - fin_ == 0.0f)) *poison = token;
-        acc_z += (double)a.z;
-        acc_cx += (double)a.cx + k_cx * (double)a.cz;
-        acc_cy += (double)a.cy + k_cy * (double)a.cz;
+        TL_WALK_ENTRANCE_ADD(a);
         if (valid) {
             if (gxin) gxin[o] = a.x;
             if (gyin) gyin[o] = a.y;
@@ -1819,26 +1859,7 @@ __global__ __launch_bounds__(kBlock, ASPH ? TL_ASPH_INV_WAVES : 1) void trace_bw
     }
     // ---- block reduction (fixed order)
     const int lane = tid & 63, wv = tid >> 6;
-    {
-        const double a0 = wave_sum(acc_z), a1 = wave_sum(acc_cx), a2 = wave_sum(acc_cy);
-        if (lane == 0) { red[wv][0] = a0; red[wv][1] = a1; red[wv][2] = a2; }
-    }
-    __syncthreads();
-    // partials are stored [column][block] (the reduction kernels then read each column as one contiguous run)
-    const size_t nrows_ = (size_t)gridDim.y * gridDim.x;
-    double *row = part + ((size_t)fw * gridDim.x + blockIdx.x);
-    // wave wv reduces surface rows wv, wv+4, ...: lane, lane+64, ... hold the same term (64 = 0 mod 4), the
-    // butterfly over lane bits 2..5 leaves each lane with the total of its own term
-    for (int k = wv; k < S; k += kWaves) {
-        const float *q = sacc_dyn + (size_t)k * kBlock;
-        double v = (double)q[lane] + (double)q[lane + 64];
-        v += (double)q[lane + 128];
-        v += (double)q[lane + 192];
-#pragma unroll
-        for (int o = 32; o >= 4; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane < 3) row[(size_t)(lane * S + k) * nrows_] = v;
-    }
-    if (tid < 3) row[(size_t)(3 * S + tid) * nrows_] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    TL_WALK_STORE_PARTIALS(S);
     if (ASPH) {
         // g_kappa[k] -> column 3S+3+k ; g_poly[k][j] -> column 4S+3+4k+j   (sasph row 5k+{0,1..4})
         for (int j = tid; j < 5 * S; j += kBlock) {
@@ -1945,7 +1966,7 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
     const float *__restrict__ gcx, const float *__restrict__ gcy, const double *__restrict__ gmom,
     const float *__restrict__ fx, const float *__restrict__ fy, const float *__restrict__ fcx,
     const float *__restrict__ fcy, const uint8_t *__restrict__ fok, const double *__restrict__ fmom,
-    float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part, const int /*plan hint, unused*/,
+    float *__restrict__ gxin, float *__restrict__ gyin, double *__restrict__ part,
     unsigned *__restrict__ poison, const unsigned token, const float *__restrict__ gstk)
 {
 #pragma clang fp contract(fast)       // see TL_REVERSE_CONTRACT above
@@ -1993,12 +2014,7 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
     for (int j = 0; j < 2 * NS; ++j) sacc_dyn[j * SLOTS + slot] = 0.0f;   // own slots only: no barrier needed
     if (ASPH)
         for (int j = 0; j < 2 * hit_slots; ++j) sasph_dyn[j * kBlock + tid] = 0.0f;
-    // entrance adjoints summed per lane in fp64 (see trace_bwd_kernel).  The cz term is folded into cx and cy per
-    // ray (cz0 = sqrt(1 - cx0^2 - cy0^2): d cz0 / d cx0 = -cx0 / cz0), which saves the fourth fp64 sum
-    // (the two factors are wave-uniform: moved to SGPRs, they cost no vector register)
-    const double rcz0 = 1.0 / sqrt((1.0 - (double)cx0 * (double)cx0) - (double)cy0 * (double)cy0);
-    const double k_cx = uniform_f64(-(double)cx0 * rcz0), k_cy = uniform_f64(-(double)cy0 * rcz0);
-    double acc_z = 0.0, acc_cx = 0.0, acc_cy = 0.0;
+    TL_WALK_ENTRANCE_SUMS(cx0, cy0);
     if (tid < NS) {
         s_row[tid] = make_float4(uload(p.c, tid), uload(p.t, tid), uload(mu_w, tid), 1.0f / uload(mu_w, tid));
         if (ASPH) {
@@ -2072,19 +2088,6 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
             sy += alive ? (float)(gm0 + (gm1 + 2.0 * (double)yi * gm2)) : 0.0f;
             sx += alive ? (float)(gm4 + (gm5 + 2.0 * (double)xi * gm6)) : 0.0f;
         }
-        // hit_sphere, as in trace_bwd_inv_kernel
-#define TL_HIT(c_, qx_, qy_, qz_, ddx, ddy, ddz, HX, HY, HZ, COS, RCOS, DB)             \
-        {                                                                                \
-            const float e_ = -(((qx_) * (ddx) + (qy_) * (ddy)) + (qz_) * (ddz));         \
-            const float mz_ = (qz_) + e_ * (ddz);                                        \
-            const float m2_ = (((qx_) * (qx_) + (qy_) * (qy_)) + (qz_) * (qz_)) - e_ * e_; \
-            const float tmp_ = (c_) * m2_ - 2.0f * mz_;                                  \
-            const float cos2_ = (ddz) * (ddz) - (c_) * tmp_;                             \
-            tl_rsq_sqrt(cos2_, RCOS, COS);                                               \
-            if (PEN) s2t = ((ddx) * (ddx) + (ddy) * (ddy)) + (c_) * tmp_;                \
-            DB = e_ + tmp_ * tl_rcp((ddz) + COS);                                        \
-            HX = (qx_) + DB * (ddx); HY = (qy_) + DB * (ddy); HZ = (qz_) + DB * (ddz);   \
-        }
         // the stored hit of this lane's ray on the aspheric row with `below_` aspheric rows before it
 #define TL_LOAD_HIT(below_, PX, PY)                                                      \
         {                                                                                \
@@ -2113,7 +2116,7 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
                 db = ((px - xi) * dx + (py - yi) * dy) + (pz - rk_next.y) * dz;
                 hx = px; hy = py; hz = pz;
             } else {
-                TL_HIT(rk_next.x, xi, yi, rk_next.y, dx, dy, dz, hx, hy, hz, cos_t, r_t, db);
+                TL_HIT(TL_HIT_S2T, rk_next.x, xi, yi, rk_next.y, dx, dy, dz, hx, hy, hz, cos_t, r_t, db);
             }
             // image-plane adjoint: x_img = x_S + dist*cx', dist = -z_S/cz' = -db
             const float dist = -db, inv_cz = tl_rcp(dz);
@@ -2291,20 +2294,14 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
             }
         };
         static_for_down<NS>(row);
-#undef TL_HIT
 #undef TL_LOAD_HIT
-        // a non-finite adjoint anywhere on the way is still there at the entrance (see trace_bwd_inv_kernel)
-        const float fin_ = ((a.x + a.y) + (a.z + a.cz)) + (a.cx + a.cy);
-        if (!(fin_ - fin_ == 0.0f)) *poison = token;
-        acc_z += (double)a.z;
-        acc_cx += (double)a.cx + k_cx * (double)a.cz;
-        acc_cy += (double)a.cy + k_cy * (double)a.cz;
+        TL_WALK_ENTRANCE_ADD(a);
         if (valid) {
             if (gxin) (gxin + ob)[ut] = a.x;
             if (gyin) (gyin + ob)[ut] = a.y;
         }
     }
-    // ---- block reduction (fixed order): this lane's sums -> the quad-transposed rows the rolled kernel keeps
+    // ---- block reduction: this lane's sums -> the quad-transposed rows the rolled kernel keeps, then the common tail
     const int lane = tid & 63, wv = tid >> 6;
     if (!PAIR) {
 #pragma unroll
@@ -2325,23 +2322,7 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
 #pragma unroll
         for (int k = 0; k < NS; ++k) sacc_dyn[k * kBlock + tid] = quad_term_sums(r_c[k], vt[k], vm[k], q_odd, q_hi);
     }
-    {
-        const double a0 = wave_sum(acc_z), a1 = wave_sum(acc_cx), a2 = wave_sum(acc_cy);
-        if (lane == 0) { red[wv][0] = a0; red[wv][1] = a1; red[wv][2] = a2; }
-    }
-    __syncthreads();
-    const size_t nrows_ = (size_t)gridDim.y * gridDim.x;
-    double *row = part + ((size_t)fw * gridDim.x + blockIdx.x);
-    for (int k = wv; k < NS; k += kWaves) {
-        const float *q = sacc_dyn + (size_t)k * kBlock;
-        double v = (double)q[lane] + (double)q[lane + 64];
-        v += (double)q[lane + 128];
-        v += (double)q[lane + 192];
-#pragma unroll
-        for (int o = 32; o >= 4; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane < 3) row[(size_t)(lane * NS + k) * nrows_] = v;
-    }
-    if (tid < 3) row[(size_t)(3 * NS + tid) * nrows_] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    TL_WALK_STORE_PARTIALS(NS);
     if (ASPH) {
         // g_kappa[k] -> column 3NS+3+k ; g_poly[k][j] -> column 4NS+3+4k+j.  Slot j holds this lens' j-th aspheric row:
         // lanes = 0, 1, 2 (mod 4) of the even slot row hold kappa, a4, a6, lanes = 0, 1 of the odd one a8, a10.
@@ -2371,6 +2352,13 @@ __global__ __launch_bounds__(kBlock, inv_unroll_waves(NS, ASPH, PEN != kPenNone)
     }
 }
 
+#undef TL_WALK_STORE_PARTIALS
+#undef TL_WALK_ENTRANCE_ADD
+#undef TL_WALK_ENTRANCE_SUMS
+#undef TL_HIT
+#undef TL_HIT_S2T
+#undef TL_HIT_PLAIN
+
 // ------------------------------------------------------------------ arithmetic self-test (tl_selftest_arith)
 __global__ void selftest_arith_kernel(const float *__restrict__ a, const float *__restrict__ b, const int64_t n,
                                       float *__restrict__ quot, float *__restrict__ root)
@@ -2394,7 +2382,7 @@ static int launch_fwd(const tl_problem &p, const tl_rays &o, const tl_part &w, h
 {
     dim3 grid(w.nbx, tl_lenses(p) * p.F * p.W), block(kBlock);
 #define TL_FWD(PEN_, ASPH_, OPD_) \
-    hipLaunchKernelGGL((trace_fwd_kernel<PEN_, ASPH_, OPD_>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, o.opd, o.stacks, w.part, w.R)
+    hipLaunchKernelGGL((trace_fwd_kernel<PEN_, ASPH_, OPD_>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, o.opd, o.stacks, w.part)
     const bool asph = p.surf_kind != nullptr, wopd = p.n_index != nullptr && o.opd != nullptr;
     if (p.aggregate && asph) TL_FWD(true, true, false);
     else if (p.aggregate) TL_FWD(true, false, false);
@@ -2406,19 +2394,19 @@ static int launch_fwd(const tl_problem &p, const tl_rays &o, const tl_part &w, h
         // runs, so that asking for the OPD changes no bit of them (contraction fuses the two kernel bodies into different
         // multiply-adds: up to 3e-6 mm in x, y otherwise); trace_fwd_kernel then writes the OPD alone, and gives none to a ray
         // that the first kernel's `ok` calls dead (kOkIn).  (An optional path, not tuned: one more forward launch.)
-        hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part, w.R);
+        hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part);
         tl_problem q = p;
         q.cond_flags = nullptr;
         hipLaunchKernelGGL((trace_fwd_kernel<false, false, true>), grid, block, 0, st, q, (float *)nullptr, (float *)nullptr,
                            (float *)nullptr, (float *)nullptr, o.ok /* read, not written */, (uint8_t *)nullptr, o.opd,
-                           (float *)nullptr, (double *)nullptr, w.R);
+                           (float *)nullptr, (double *)nullptr);
     }
 #else
     else if (wopd) TL_FWD(false, false, true);
 #endif
 #if TL_FAST
     // two rays per lane: -10 % in fast mode (latency-bound chains), +4 % in strict mode (issue-bound, fewer waves)
-    else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part, w.R);
+    else hipLaunchKernelGGL((trace_fwd_plain_kernel<2>), grid, block, 0, st, p, o.x, o.y, o.cx, o.cy, o.ok, o.back, w.part);
 #else
     else TL_FWD(false, false, false);
 #endif
@@ -2435,7 +2423,7 @@ static int launch_bwd_ns(const tl_problem &p, const tl_seeds &g, const tl_grads 
     const float *gstk = g.g_stacks;
 #define TL_BWD(ASPH_, PEN_) \
     hipLaunchKernelGGL((trace_bwd_kernel<NS, ASPH_, PEN_>), grid, block, 0, st, p, g.gx, g.gy, g.gcx, g.gcy, g.g_moments, \
-                       o.g_x_in, o.g_y_in, w.part, w.R, fb.mom, fb.poison, fb.token, g.g_opd, fb.dead_ok, gstk)
+                       o.g_x_in, o.g_y_in, w.part, fb.mom, fb.poison, fb.token, g.g_opd, fb.dead_ok, gstk)
     if (p.surf_kind && p.aggregate && gstk) TL_BWD(true, kPenRay);
     else if (p.surf_kind && p.aggregate) TL_BWD(true, kPenUniform);
     else if (p.surf_kind) TL_BWD(true, kPenNone);
@@ -2482,10 +2470,10 @@ static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays 
     const size_t lds_asph = hits ? (size_t)2 * p.asph_hit_slots * kBlock * sizeof(float) : 0;
     const float *gstk = g.g_stacks;
 #define TL_INV_ARGS p, g.gx, g.gy, g.gcx, g.gcy, g.g_moments, f.x, f.y, f.cx, f.cy, f.ok, f.moments, o.g_x_in, o.g_y_in, \
-                    w.inv.part, w.inv.R, w.poison, w.token
+                    w.inv.part
 #define TL_INVU_V(NS_, ASPH_, PEN_) \
     hipLaunchKernelGGL((trace_bwd_inv_unrolled_kernel<NS_, ASPH_, PEN_>), grid, block, \
-                       (NS_ < kInvUnrollPairMin ? 2 : 1) * lds + lds_asph + lds_pad, st, TL_INV_ARGS, gstk)
+                       (NS_ < kInvUnrollPairMin ? 2 : 1) * lds + lds_asph + lds_pad, st, TL_INV_ARGS, w.poison, w.token, gstk)
 #define TL_INVU(NS_) \
     case NS_: if (asph && pen && gstk) TL_INVU_V(NS_, true, kPenRay); else if (asph && pen) TL_INVU_V(NS_, true, kPenUniform); \
               else if (asph) TL_INVU_V(NS_, true, kPenNone); else if (pen && gstk) TL_INVU_V(NS_, false, kPenRay); \
@@ -2503,9 +2491,9 @@ static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays 
     } else if (pen) {
         return -1;                // (the C entry point sends the penalty term of such lenses to tl_trace_bwd)
     } else if (asph) {
-        hipLaunchKernelGGL(trace_bwd_inv_kernel<true>, grid, block, lds + lds_pad, st, TL_INV_ARGS);
+        hipLaunchKernelGGL(trace_bwd_inv_kernel<true>, grid, block, lds + lds_pad, st, TL_INV_ARGS, 0 /*unused*/, w.poison, w.token);
     } else {
-        hipLaunchKernelGGL(trace_bwd_inv_kernel<false>, grid, block, lds + lds_pad, st, TL_INV_ARGS);
+        hipLaunchKernelGGL(trace_bwd_inv_kernel<false>, grid, block, lds + lds_pad, st, TL_INV_ARGS, 0 /*unused*/, w.poison, w.token);
     }
 #undef TL_INVU
 #undef TL_INVU_V
