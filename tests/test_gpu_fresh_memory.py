@@ -380,7 +380,7 @@ def test_warp(ta, name):
 
 @pytest.mark.parametrize("name", WARP_IMAGE)
 def test_warp_image_gradient(ta, name):
-    """image_grad='fused': the memset-then-atomics fixed-point accumulator of tl_warp_bwd_image lives in the workspace."""
+    """image_grad='fused': the clear-then-atomics fixed-point accumulator of tl_warp_bwd_image lives in the workspace."""
     import warp_image_cases as wic
     from torchoptics_amd import imaging
     args = wic.inputs(name)

@@ -107,7 +107,7 @@ def main():
         px = H * W
         moved = 4 * (2 * B * px * Cc + 2 * px + px * Cc)                 # g_out, g_image | x, y | gain
         least = moved / HBM * 1e3
-        lines.append(f"B = {B}, tl_warp_bwd_image alone (memset + three kernels + launches, workspace {nbytes / 2**20:.1f} MiB), "
+        lines.append(f"B = {B}, tl_warp_bwd_image alone (clear + three kernels + launches, workspace {nbytes / 2**20:.1f} MiB), "
                      f"{a.calls} calls per timed window:")
         per_call, results = {}, {}
         for name, flags in (("auto", 0), ("direct", 1)):

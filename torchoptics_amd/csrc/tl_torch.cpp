@@ -17,6 +17,7 @@
 
 #include <map>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 #include "../../include/tl_trace.h"
@@ -50,6 +51,16 @@ Tensor workspace(size_t nbytes, const at::Device &dev, void *stream)
     if (!ws.defined() || (size_t)ws.numel() < nbytes)
         ws = at::empty({(int64_t)std::max<size_t>(nbytes, (size_t)1 << 20)}, at::TensorOptions().dtype(at::kByte).device(dev));
     return ws;
+}
+
+// The scratch tensor of (device, stream handle) right now, undefined (None in Python) when there is none: a HIP graph recorded
+// on that stream holds its raw pointer, so the graph's owner keeps the tensor (ops.workspace_of, graphs.capture_step).
+std::optional<Tensor> workspace_of(int device, uintptr_t stream)
+{
+    std::lock_guard<std::mutex> lock(g_ws_mutex);
+    auto it = g_ws.find({device, (void *)stream});
+    if (it == g_ws.end() || !it->second.defined()) return std::nullopt;
+    return it->second;
 }
 
 // ------------------------------------------------------------------ optional live timing of the C-ABI calls (bench.py)
@@ -609,6 +620,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("spot_rms", &spot_rms);
     m.def("pupil_position", &pupil_position);
     m.def("unsup_loss", &unsup_loss);
+    m.def("workspace_of", &workspace_of);
     m.def("last_use_inv", [] { return g_last_use_inv; });
     m.def("enable_timing", &enable_timing);
     m.def("timing_ms", &timing_ms);

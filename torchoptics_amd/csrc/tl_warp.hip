@@ -208,7 +208,9 @@ __global__ __launch_bounds__(kBlock) void warp_bwd_kernel(const Geo g, const flo
 //
 // WORKSPACE (tl_warp_bwd_image_work_bytes): [0, 256) word 0 = the bits of m | int64 accumulators, PLANAR [B,C,H,W], so that
 // neighbouring columns of one channel are neighbouring 8-byte words | one flag bit per element of g_image in its own
-// (channel-last) order.  Cleared by one memset node at the head of the call.
+// (channel-last) order.  Cleared by warp_image_clear_kernel at the head of the call -- a kernel, not hipMemsetAsync: recorded
+// into a HIP graph, the memset node cleared the region on the graph's first launch only and filled it with its own 64-bit
+// destination address on every later one (tests/test_gpu_steps_graph.py: the second replay of a captured warp step).
 //
 // SCATTER KERNEL.  One lane per output pixel, a block owns a tile of 32 x 8 output pixels (lanes along xo), the lens in
 // grid y.  Taps and weights are axis_taps' (with stride 1 the offsets are the clipped indices).  Privatised in LDS: the block
@@ -237,6 +239,12 @@ __device__ __forceinline__ int quantum_exponent(const unsigned mbits, const int 
 }
 
 __device__ __forceinline__ double pow2(const int k) { return __longlong_as_double((long long)(k + 1023) << 52); }   // |k| < 1023
+
+// grid-stride over the 8-byte words of the workspace: the clear at the head of tl_warp_bwd_image
+__global__ __launch_bounds__(kBlock) void warp_image_clear_kernel(u64 *__restrict__ work, const int64_t words)
+{
+    for (int64_t at = (int64_t)blockIdx.x * kBlock + threadIdx.x; at < words; at += (int64_t)gridDim.x * kBlock) work[at] = 0;
+}
 
 // grid-stride over the B Ho Wo output pixels of the call; one atomic per block at the most
 __global__ __launch_bounds__(kBlock) void warp_image_max_kernel(const Geo g, const float *__restrict__ gain,
@@ -514,8 +522,10 @@ int tl_warp_bwd_image(const tl_warp_geom *g, const float *x, const float *y, con
     const int64_t pixels = (int64_t)g->Ho * g->Wo;
     int Hb = 0;                                          // ceil(log2(16 Ho Wo)), in integers
     while (((int64_t)1 << Hb) < 16 * pixels) ++Hb;
-    const hipError_t e = hipMemsetAsync(work, 0, need, st);
-    if (e != hipSuccess) return tl_host::hip_fail(e, "hipMemsetAsync of the warp image workspace");
+    const int64_t words = (int64_t)(need / sizeof(u64));             // need is a multiple of 256, work is aligned to 8 bytes
+    const unsigned cblocks = (unsigned)std::min<int64_t>((words + kBlock - 1) / kBlock, (int64_t)1 << 16);
+    hipLaunchKernelGGL(warp_image_clear_kernel, dim3(cblocks), dim3(kBlock), 0, st, (u64 *)work, words);
+    if (const int rc = tl_host::launched("warp_image_clear_kernel launch")) return rc;
     const unsigned tiles = (unsigned)((g->Wo + kTileX - 1) / kTileX) * (unsigned)((g->Ho + kTileY - 1) / kTileY);
     const int64_t all = (int64_t)g->B * pixels;                       // <= 2^31 2^26
     const unsigned mblocks = (unsigned)std::min<int64_t>((all + kBlock - 1) / kBlock, 2048);

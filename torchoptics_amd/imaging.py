@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .lens_modeling import const_tensor
 
 
 def _axis(n, g, o, window_type, name):
@@ -78,8 +79,11 @@ def _svola_torch(image, psfs, geo):
     x = torch.stack(slabs, dim=0).reshape(1, N * B * Cc, ph + 2 * a, pw + 2 * b)
     k = psfs.expand(B, N, kh, kw, Cc).permute(1, 0, 4, 2, 3).flip(-1, -2).reshape(N * B * Cc, 1, kh, kw)
     y = F.conv2d(x, k, groups=N * B * Cc).reshape(N, B, Cc, ph, pw)
-    tab_r = torch.from_numpy(geo.tab_r).to(device=image.device, dtype=image.dtype)
-    tab_c = torch.from_numpy(geo.tab_c).to(device=image.device, dtype=image.dtype)
+    key = ("torch", image.device, image.dtype)
+    if key not in geo.device_tables:                       # uploaded once per device and dtype (a captured step uploads nothing)
+        geo.device_tables[key] = (torch.from_numpy(geo.tab_r).to(device=image.device, dtype=image.dtype),
+                                  torch.from_numpy(geo.tab_c).to(device=image.device, dtype=image.dtype))
+    tab_r, tab_c = geo.device_tables[key]
     frame = torch.zeros((B, Cc, H + 2 * oh, W + 2 * ow), dtype=y.dtype, device=image.device)
     for n in range(N):
         i, j = divmod(n, geo.gw)
@@ -156,17 +160,28 @@ def psf_grid_from_fields(kernels, grid_shape, index_map=None):
     Without `index_map` the fields are the grid in row-major order (n_fields = gh gw; a column of fields is a gh x 1 grid) and
     the result is a permuted VIEW of `kernels`: the fused kernels read it through its strides, nothing is copied.  With
     `index_map` ([gh, gw] integers: the field of every grid cell, e.g. by image height) the kernels are gathered, which
-    copies N small kernels unless the map is the identity."""
+    copies N small kernels unless the map is the identity.  A map given as host values (nested lists, a numpy array, a CPU
+    tensor) is checked on the host and its device copy is cached: pass it so inside a captured step.  A map that is a device
+    tensor is checked on the device, which synchronises."""
     gh, gw = (int(v) for v in grid_shape)
     if kernels.dim() != 4:
         raise ValueError("psf_grid_from_fields: kernels must be [n_fields, C, kh, kw]")
-    if index_map is not None:
-        idx = torch.as_tensor(index_map, dtype=torch.long).reshape(-1)
+    if index_map is not None and not (torch.is_tensor(index_map) and index_map.device.type != "cpu"):
+        host = (index_map.numpy() if torch.is_tensor(index_map) else np.asarray(index_map)).reshape(-1)
+        if host.size != gh * gw:
+            raise ValueError(f"psf_grid_from_fields: index_map must hold {gh} x {gw} entries")
+        host = host.astype(np.int64)
+        if int(host.min()) < 0 or int(host.max()) >= kernels.shape[0]:
+            raise ValueError("psf_grid_from_fields: index_map names a field that does not exist")
+        if not (host.size == kernels.shape[0] and np.array_equal(host, np.arange(host.size))):
+            kernels = kernels.index_select(0, const_tensor(host.tolist(), torch.long, kernels.device))
+    elif index_map is not None:
+        idx = index_map.to(torch.long).reshape(-1)
         if idx.numel() != gh * gw:
             raise ValueError(f"psf_grid_from_fields: index_map must hold {gh} x {gw} entries")
         if int(idx.min()) < 0 or int(idx.max()) >= kernels.shape[0]:
             raise ValueError("psf_grid_from_fields: index_map names a field that does not exist")
-        if not (idx.numel() == kernels.shape[0] and bool((idx == torch.arange(idx.numel())).all())):
+        if not (idx.numel() == kernels.shape[0] and bool((idx == torch.arange(idx.numel(), device=idx.device)).all())):
             kernels = kernels.index_select(0, idx.to(kernels.device))
     elif kernels.shape[0] != gh * gw:
         raise ValueError(f"psf_grid_from_fields: {kernels.shape[0]} fields do not fill a {gh} x {gw} grid (give an index_map)")
@@ -313,9 +328,12 @@ def psf_grid_from_trace(x, y, ray_ok, cells, n_bins, increment, y_target=None, f
     if fused:
         hist = ops.PsfRotAccumulateFunction.apply(xs, ys, ok, grid, inc, inc, y_target, nx, ny, 0.5 - nx / 2, 0.5 - ny / 2)
     else:
-        src = torch.from_numpy(grid.src.astype(np.int64)).to(x.device)
-        c = torch.from_numpy(grid.c).to(device=x.device, dtype=x.dtype)[:, None, None]
-        s = torch.from_numpy(grid.s).to(device=x.device, dtype=x.dtype)[:, None, None]
+        tkey = ("torch", x.device, x.dtype)
+        if tkey not in grid.device_tables:                  # uploaded once per device and dtype, like the kernels' tables
+            grid.device_tables[tkey] = (torch.from_numpy(grid.src.astype(np.int64)).to(x.device),
+                                        torch.from_numpy(grid.c).to(device=x.device, dtype=x.dtype)[:, None, None],
+                                        torch.from_numpy(grid.s).to(device=x.device, dtype=x.dtype)[:, None, None])
+        src, c, s = grid.device_tables[tkey]
         xi, eta = xs[src], (ys - y_target[:, None, None])[src]                              # [G, W, P]
         xr, yr = c * xi + s * eta, c * eta - s * xi
         rng = lambda n: (torch.arange(n, dtype=x.dtype, device=x.device) + (0.5 - n / 2)) * inc       # noqa: E731
@@ -470,20 +488,40 @@ def _pixel_axes(out_size, aspect, dtype, device):
     return xn, yn, h
 
 
+_NUMPY_FLOAT = {torch.float16: np.float16, torch.float32: np.float32, torch.float64: np.float64}
+
+
 def radial_map(values, fields, out_size, v0=0.0, aspect=None):
     """A radial profile painted over the image: values [L, K] or [L, K, C], sampled at the relative fields `fields` [K]
     (ascending, > 0), become [L, Ho, Wo, C or 1] by piecewise-linear interpolation in h, the pixel's distance from the image
     centre in units of the half-diagonal (the corner pixels are at h = 1).  There is a node (0, v0) at the centre -- v0 = 0
     for distortion, 1 for relative illumination -- and the profile is held constant beyond the last field.  `aspect` is the
-    image's width / height (default Wo / Ho: square pixels).  Plain torch ops, differentiable in `values`."""
+    image's width / height (default Wo / Ho: square pixels).  Plain torch ops, differentiable in `values`.
+
+    `fields` given as host values (a tuple or list of numbers, a numpy array, a CPU tensor) are checked on the host and their
+    device copy is cached: nothing is uploaded and nothing is read back per call, so a captured step passes host values.
+    `fields` given as a tensor on another device than the CPU are checked there, which synchronises."""
     if values.dim() not in (2, 3):
         raise ValueError(f"radial_map: values must be [L, K] or [L, K, C], got {tuple(values.shape)}")
-    f = torch.as_tensor(fields, dtype=values.dtype, device=values.device).reshape(-1)
-    K = f.numel()
+    on_device = torch.is_tensor(fields) and fields.device.type != "cpu"
+    if on_device:
+        f = fields.to(dtype=values.dtype, device=values.device).reshape(-1)
+        K = f.numel()
+    else:
+        # rounded to the dtype of `values` first, as the device copy is: the check sees the numbers the interpolation uses
+        host = np.asarray(fields.detach().numpy() if torch.is_tensor(fields) else fields, dtype=np.float64).reshape(-1)
+        host = host.astype(_NUMPY_FLOAT.get(values.dtype, np.float64)).astype(np.float64)
+        K = host.size
     if values.shape[1] != K or K < 1:
         raise ValueError(f"radial_map: values {tuple(values.shape)} hold {values.shape[1]} samples per lens, fields {K}")
-    if not (bool((f > 0).all()) and bool((f[1:] > f[:-1]).all())):
+    if on_device:
+        ascending = bool((f > 0).all()) and bool((f[1:] > f[:-1]).all())
+    else:
+        ascending = bool((host > 0).all()) and bool((host[1:] > host[:-1]).all())
+    if not ascending:
         raise ValueError("radial_map: fields must be ascending and > 0")
+    if not on_device:
+        f = const_tensor(host.tolist(), values.dtype, values.device)
     v = values if values.dim() == 3 else values[..., None]                               # [L, K, C or 1]
     _, _, h = _pixel_axes(out_size, aspect, values.dtype, values.device)
     nodes_h = torch.cat((f.new_zeros(1), f))                                             # [K + 1]
@@ -520,9 +558,15 @@ def ssim_window(filter_size, filter_sigma, dtype=torch.float64):
     return torch.from_numpy(w / w.sum()).to(dtype)
 
 
+@functools.lru_cache(maxsize=64)
+def _ssim_window_on(filter_size, filter_sigma, dtype, device):
+    """ssim_window on `device`, uploaded once per (window, dtype, device): a captured step uploads nothing."""
+    return ssim_window(filter_size, filter_sigma, dtype).to(device)
+
+
 def _ssim_blur(Cc, filter_size, filter_sigma, dtype, device):
     """t [B, C, H, W] -> its VALID convolution with the 2-D window, as two 1-D grouped conv2d calls."""
-    w = ssim_window(filter_size, filter_sigma, dtype).to(device)
+    w = _ssim_window_on(int(filter_size), float(filter_sigma), dtype, torch.device(device))
     w_row = w.reshape(1, 1, 1, -1).expand(Cc, 1, 1, -1)
     w_col = w.reshape(1, 1, -1, 1).expand(Cc, 1, -1, 1)
     return lambda t: F.conv2d(F.conv2d(t, w_row, groups=Cc), w_col, groups=Cc)
@@ -641,7 +685,7 @@ def _ms_ssim_torch(a, b, max_value, power_factors, filter_size, filter_sigma, k1
             q = q * (2 * mu_a * mu_b + c1) / (mu_a * mu_a + mu_b * mu_b + c1)
         terms.append(q.mean(dim=(2, 3)))
     v = torch.stack(terms, dim=2)                                                      # [B, C, M]
-    p = torch.tensor(power_factors, dtype=a.dtype, device=a.device)
+    p = const_tensor(list(power_factors), a.dtype, a.device)
     # where any term of a (lens, channel) is <= 0 the product is 0 and so are all its gradients: the power is taken of 1
     # there (a finite derivative, which the `where` then multiplies by 0), never of 0
     positive = (v > 0).all(dim=2, keepdim=True)

@@ -280,7 +280,7 @@ class Lens:
 
     def scale(self, factor) -> "Lens":
         if self.kappa is not None:
-            powers = torch.tensor([3., 5., 7., 9.], dtype=self.poly.dtype, device=self.poly.device)
+            powers = const_tensor([3., 5., 7., 9.], self.poly.dtype, self.poly.device)
             return Lens(self.structure, self.c / factor, self.t * factor, self.nd, self.v, self.kappa,
                         self.poly / factor ** powers)
         return Lens(self.structure, self.c / factor, self.t * factor, self.nd, self.v)

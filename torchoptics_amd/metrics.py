@@ -14,6 +14,7 @@ from typing import NamedTuple
 import torch
 
 from . import ops, paraxial
+from .lens_modeling import const_tensor
 from .ray_tracing import RayTracer, _root_of_variance, apply_vignetting
 
 
@@ -44,7 +45,7 @@ def compute_distortion(specs, lens, relative_fields, default_device="cuda"):
         ops.set_backward_algorithm(algo)
     n_lens = len(specs)
     y, cy = y.reshape(n_lens, -1), cy.reshape(n_lens, -1)
-    fields = torch.tensor(list(relative_fields), dtype=y.dtype, device=y.device)
+    fields = const_tensor([float(v) for v in relative_fields], y.dtype, y.device)        # cached: a captured step uploads nothing
     efl, bfl = paraxial.get_first_order(lens)
     ideal = torch.tan(fields[None, :] * specs.hfov[:, None]) * efl[:, None]
     rows = torch.arange(n_lens, device=y.device)
@@ -62,8 +63,8 @@ def compute_relative_illumination(specs, lens, relative_fields, vig_fn=None, n_r
     assert relative_fields[0] == 0., "the first field must be the axis"
     tr = RayTracer(mode='tee', rel_fields=relative_fields, vig_fn=vig_fn, n_ray_aiming_iter=n_ray_aiming_iter,
                    wavelengths=wavelengths, default_device=default_device)
-    x = torch.tensor([0., 0., 1.], device=default_device).reshape(1, 1, 3, 1)
-    y = torch.tensor([1., -1., 0.], device=default_device).reshape(1, 1, 3, 1)
+    x = const_tensor([0., 0., 1.], torch.float32, default_device, (1, 1, 3, 1))      # cached: no upload per call
+    y = const_tensor([1., -1., 0.], torch.float32, default_device, (1, 1, 3, 1))
     _, _, cx, cy, ray_ok, _ = tr.trace_rays(specs, lens, xy=(x, y))
     axis = torch.clamp(2 * cy[:, 0, 0, 0] ** 2, min=1e-6)
     ri = (cy[..., 0, :] - cy[..., 1, :]) * cx[..., 2, :] / axis[:, None, None]
@@ -85,15 +86,15 @@ def compute_ray_aiming_error(specs, lens, rel_fields, vig_fn=None, n_ray_aiming_
         rs = paraxial.compute_pupil_radius(specs2, lens2, default_device=default_device).reshape(-1, 1, 1, 1)
     else:
         raise ValueError("ray_aiming_mode must be 'real' or 'paraxial'")
-    y = torch.tensor([-1., 1.], device=default_device).reshape(1, 1, 2, 1)
-    x = torch.zeros_like(y)
+    y = const_tensor([-1., 1.], torch.float32, default_device, (1, 1, 2, 1))         # cached: no upload per call
+    x = const_tensor([0., 0.], torch.float32, default_device, (1, 1, 2, 1))
     tr = RayTracer(mode='tee', rel_fields=rel_fields, vig_fn=vig_fn, wavelengths=['d'],
                    n_ray_aiming_iter=n_ray_aiming_iter, ray_aiming_mode=ray_aiming_mode, default_device=default_device)
     # the truncated lens ends at the stop: its "image plane" is the stop plane, and ray aiming (computed on
     # the same rows) is applied by trace_rays itself
     _, ys, *_ = tr.trace_rays(specs2, lens2, xy=(x, y), use_vig=True)
     if vig_fn is not None:
-        fields = torch.tensor(list(rel_fields), dtype=torch.float32, device=default_device)[None, :]
+        fields = const_tensor([float(v) for v in rel_fields], torch.float32, default_device)[None, :]
         y = apply_vignetting(y, vig_fn(fields, specs.vig_up), vig_fn(fields, specs.vig_down))
     return ys / rs - y
 

@@ -199,8 +199,23 @@ def _call(name, dev, *args, timed=None):
         _lib.check(rc, name)
 
 
+def workspace_of(device, stream=None) -> tuple:
+    """The scratch tensors the kernels launched on `stream` of `device` (default: its current stream) write to right now:
+    this module's and the C++ host chain's, as far as either has been needed there yet.  A HIP graph recorded on that stream
+    holds their raw pointers: whoever owns the graph keeps the tensors (graphs.capture_step does), because both caches drop
+    their own reference when a later call on a stream with the same handle needs a larger one."""
+    device = torch.device(device)
+    index = torch.cuda.current_device() if device.index is None else device.index
+    stream = torch.cuda.current_stream(device) if stream is None else stream
+    held = [_ws_cache.get((index, stream.cuda_stream))]
+    if _ext() is not None and hasattr(_ext(), "workspace_of"):
+        held.append(_ext().workspace_of(index, stream.cuda_stream))
+    return tuple(t for t in held if t is not None)
+
+
 def _workspace(nbytes: int, device) -> torch.Tensor:
-    """Per-(device, stream) scratch for the block partials; grows monotonically."""
+    """Per-(device, stream) scratch for the block partials; grows monotonically.  Replacing it only drops the cache's
+    reference: a captured graph that still writes to the old tensor holds its own (workspace_of)."""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < nbytes:

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import torch
 
-from .lens_modeling import Lens, mask_replace
+from .lens_modeling import Lens
 
 
 def interface_propagation_abcd(c: torch.Tensor, t: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
@@ -82,7 +82,12 @@ def compute_last_curvature(structures, c: torch.Tensor, t: torch.Tensor, nd: tor
 
     c: flat curvatures WITHOUT the last row; t: flat thicknesses; nd: flat glass indices.
     Returns the flat curvature vector including the solved one.
+
+    Which rows carry a curvature is decided on the host masks of `structures`, and the flat vectors are placed and read back
+    through cached index tensors: no upload, no read-back and no boolean-mask indexing (a device-to-host sync) per call.
     """
+    import numpy as np
+    from .lens_modeling import const_tensor
     mask = structures.mask_torch
     dev = mask.device
     n_lens = mask.shape[0]
@@ -93,9 +98,16 @@ def compute_last_curvature(structures, c: torch.Tensor, t: torch.Tensor, nd: tor
 
     is_last = torch.zeros_like(mask).scatter_(1, (length - 1)[:, None], True)
     c_rows = mask & ~is_last
-    c2d = mask_replace(c_rows.cpu().numpy(), torch.zeros(mask.shape, dtype=c.dtype, device=dev), c)
-    t2d = mask_replace(structures.mask, torch.zeros(mask.shape, dtype=t.dtype, device=dev), t)
-    n2d = mask_replace(structures.mask_G, torch.ones(mask.shape, dtype=nd.dtype, device=dev), nd)
+    c_rows_host = structures.mask.copy()
+    c_rows_host[np.arange(n_lens), structures.mask.sum(axis=1) - 1] = False
+    idx_c = const_tensor(np.flatnonzero(c_rows_host).tolist(), torch.long, dev)
+
+    def placed(flat, idx, fill):
+        base = torch.full((mask.numel(),), fill, dtype=flat.dtype, device=dev)
+        return base.index_copy(0, idx, flat.to(dev)).reshape(mask.shape)
+    c2d = placed(c, idx_c, 0.0)
+    t2d = placed(t, structures.idx_rows, 0.0)
+    n2d = placed(nd, structures.idx_glass, 1.0)
     n2d = _with_air_in_front(n2d)
 
     is_solved = torch.zeros_like(mask).scatter_(1, solve_at[:, None], True)
@@ -107,7 +119,7 @@ def compute_last_curvature(structures, c: torch.Tensor, t: torch.Tensor, nd: tor
     n_before = n2d[rows, solve_at]
     last_c = -(1 + n_before * m[:, 1, 0]) / (m[:, 0, 0] * (n_before - 1))
     c2d = c2d.clone().scatter_(1, solve_at[:, None], last_c[:, None])
-    return c2d[mask]
+    return c2d.reshape(-1).index_select(0, structures.idx_rows)
 
 
 def compute_pupil_radius(specs, lens2stop, default_device="cuda", return_ok=False, allow_backward_rays=True) -> torch.Tensor:

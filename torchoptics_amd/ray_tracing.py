@@ -116,8 +116,10 @@ def _as_rays(x, y, device):
 
 
 def chief(tensor, _n=None, device="cuda"):
-    """The chief ray: pupil centre."""
-    return _as_rays([0.0], [0.0], device)
+    """The chief ray: pupil centre.  Cached constants, shared and READ-ONLY like tee()'s: no host-to-device copy per call."""
+    from .lens_modeling import const_tensor
+    zero = const_tensor([0.0], torch.float32, device, (1, 1, 1, 1))
+    return zero, zero
 
 
 def meridional_uniform(tensor, n_rays, device="cuda"):
@@ -680,7 +682,8 @@ class RayTracer:
     def _vignette(self, specs, yp_rel, xp_rel):
         """Per-field vignetting of the relative pupil coordinates (ray_tracing.py:479-490 of the TF original):
         `vig_fn(fields [1,F], v [B]) -> [B,F]` interpolates the three vignetting factors over the field."""
-        fields = torch.tensor(self.rel_fields, dtype=torch.float32, device=yp_rel.device)[None, :]
+        from .lens_modeling import const_tensor
+        fields = const_tensor([float(v) for v in self.rel_fields], torch.float32, yp_rel.device)[None, :]
         up, down, vx = (self.vig_fn(fields, v) for v in (specs.vig_up, specs.vig_down, specs.vig_x))
         return apply_vignetting(yp_rel, up, down), apply_vignetting(xp_rel, vx, vx)
 
