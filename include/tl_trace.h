@@ -7,7 +7,8 @@
  * mirrors the reference signatures on top of these.  The image side (image_ops.py) is here
  * too: tl_svola_* blurs an image with the lens's PSFs, tl_warp_* resamples it through the
  * distortion map and multiplies the relative illumination in.  tl_focus_* sums the through-focus
- * moments of a traced fan (best focus, tangential / sagittal foci, axial colour).
+ * moments of a traced fan (best focus, tangential / sagittal foci, axial colour), tl_enclosed_* its
+ * encircled / ensquared energy under a smooth edge.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless marked "host";
@@ -696,6 +697,50 @@ int tl_focus_moments(int32_t device, int64_t F, int64_t P, int64_t W, const floa
 int tl_focus_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const float *cx,
                   const float *cy, const uint8_t *ok, int64_t s_f, int64_t s_p, int64_t s_w, const double *g_moments /* [F,W,11] */,
                   float *gx, float *gy, float *gcx, float *gcy, void *stream);
+
+/*
+ * Encircled / ensquared energy of a traced fan (extension; metrics.enclosed_energy / metrics.spot_centroid stand on them): how
+ * much of the light falls inside a circle of radius R, or inside a pixel of half side R, about a centre.
+ *
+ * x, y (float) and ok (bytes) are [F, P, W] tensors that share ONE stride triple s_f, s_p, s_w (elements); a row is one (f, w).
+ * A ray is LIVE iff ok != 0; a dead ray adds exactly 0 to every sum and gets exactly 0 gradient whatever its coordinates hold
+ * (NaN, inf, 1e30); live rays must be finite.  Per row, over the live rays,
+ *   tl_enclosed_centroid   S[f, w] = (n, sum x, sum y)
+ *   tl_enclosed_sums       sums[f, w, k] = sum e_k, with dx = x - centre[f, w, 0], dy = y - centre[f, w, 1],
+ *       shape 0 (circle)   e_k = sigma((R_k - rho) inv_k),  rho = sqrt(dx^2 + dy^2)
+ *       shape 1 (square)   e_k = sigma((R_k - |dx|) inv_k) sigma((R_k - |dy|) inv_k)                    (R_k is the half side)
+ *   sigma(u) = 0 for u <= -1, 1 for u >= 1, else t^2 (3 - 2 t) with t = (u + 1) / 2; sigma'(u) = 3 t (1 - t) inside the band.
+ * radii R_1 < ... < R_K (> 0) and inv_soft = 1 / softness (> 0) are HOST arrays of K <= 32 doubles: they travel to the kernels
+ * as a by-value argument, nothing is uploaded and no call synchronises.  Every difference, product, root and sum is in fp64 from
+ * the fp32 inputs, uncontracted; one partial per block goes to the workspace and a second kernel adds a row's partials in a fixed
+ * order: no atomics, the same bits on every run.  Layout handling, launch plan and limits are tl_focus_moments' (16-byte loads
+ * where s_p = 1 and the row's bases are aligned, one ray at a time elsewhere; F W < 2^31 rows in launches of 65535; P < 2^31).
+ *
+ * tl_enclosed_seed: d(sum g_sums . sums) / d(x, y) per ray in fp64, plus g_lin[f, w, 0..1] (the seeds of sum x, sum y; NULL = 0) on
+ * live rays, rounded once to float and written with the inputs' strides into gx, gy (either may be NULL); dead rays get zeros.
+ *   circle   d e_k / dx = -sigma'(u) inv_k dx / rho   (0 at rho = 0)
+ *   square   d e_k / dx = -sigma'(u_x) sigma(u_y) inv_k sgn(dx)   (sgn(0) = 0),       y likewise.
+ * g_centre[f, w, 0..1] (NULL = not wanted) = minus the row's sum of those edge terms (without g_lin), through partials and the
+ * fixed-order reduce.
+ *
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, F, P or W below 1, F W or P at
+ * or above 2^31, K outside 1..32, an unknown shape, a radius or softness not finite and positive, radii not strictly increasing,
+ * every output of the seed NULL.  TL_EWORKSPACE: workspace NULL or below tl_enclosed_workspace_bytes(F, P, W, K) (0 for sizes
+ * that are refused; tl_enclosed_centroid needs that of K = 1).
+ */
+size_t tl_enclosed_workspace_bytes(int64_t F, int64_t P, int64_t W, int K);
+int tl_enclosed_centroid(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const uint8_t *ok,
+                         int64_t s_f, int64_t s_p, int64_t s_w, double *S /* [F,W,3] */, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int tl_enclosed_sums(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const uint8_t *ok,
+                     int64_t s_f, int64_t s_p, int64_t s_w, const double *centre /* [F,W,2] */, const double *radii /* host, K */,
+                     const double *inv_soft /* host, K */, int K, int shape, double *sums /* [F,W,K] */, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int tl_enclosed_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const uint8_t *ok,
+                     int64_t s_f, int64_t s_p, int64_t s_w, const double *centre /* [F,W,2] */, const double *radii /* host, K */,
+                     const double *inv_soft /* host, K */, int K, int shape, const double *g_sums /* [F,W,K] */,
+                     const double *g_lin /* [F,W,2] or NULL */, float *gx, float *gy, double *g_centre /* [F,W,2] or NULL */,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

@@ -167,6 +167,15 @@ _SIGNATURES = {
     "tl_focus_moments": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 5 + [C.c_int64] * 3 + [_VP] + _WS),
     # ... | g_moments | gx, gy, gcx, gcy | stream
     "tl_focus_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 5 + [C.c_int64] * 3 + [_VP] + [_VP] * 4 + [_VP]),
+    "tl_enclosed_workspace_bytes": (C.c_size_t, [C.c_int64] * 3 + [C.c_int]),
+    # device, F, P, W | x, y, ok | s_f, s_p, s_w | S | workspace, bytes | stream
+    "tl_enclosed_centroid": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + _WS),
+    # ... | centre | radii, inv_soft (host doubles), K, shape | sums | workspace, bytes | stream
+    "tl_enclosed_sums": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int, C.c_int]
+                         + [_VP] + _WS),
+    # ... | centre | radii, inv_soft, K, shape | g_sums, g_lin | gx, gy, g_centre | workspace, bytes | stream
+    "tl_enclosed_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int, C.c_int]
+                         + [_VP] * 2 + [_VP] * 3 + _WS),
 }
 EXPORTS = tuple(_SIGNATURES)
 

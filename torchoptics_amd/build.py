@@ -45,6 +45,7 @@ UNITS = {
     "tl_warp.hip": [],         # the bicubic image warp (distortion, relative illumination) and its coordinate / gain gradients
     "tl_ssim.hip": [],         # the SSIM of two images under a Gaussian window and its gradients to both
     "tl_focus.hip": [],        # the through-focus spot moments of a traced fan (fp64 sums of x, y and the slopes) and their seeds
+    "tl_enclosed.hip": [],     # the encircled / ensquared energy of a traced fan (fp64 sums under a smooth edge) and its seeds
 }
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 

@@ -341,3 +341,170 @@ def through_focus(x, y, cx, cy, ray_ok, common=("wavelength",), centroid="row", 
     finish is plain float64 torch on tiny tensors either way)."""
     M = focus_moments(x, y, cx, cy, ray_ok, fused=fused)
     return through_focus_from_moments(M, common, centroid, dtype=x.dtype)
+
+
+# ---------------------------------------------------------------------------- encircled / ensquared energy
+class EnclosedEnergy(NamedTuple):
+    """What enclosed_energy returns."""
+    n: torch.Tensor                 # live rays, [B, F, W] less the pooled dimensions
+    energy: torch.Tensor            # share of them inside each radius, [..., K]
+    centre: torch.Tensor            # the centre every row was measured about, [B, F, W, 2]
+
+
+def _enclosed_edge(radii, softness, shape):
+    """(radii, 1 / softness) as tuples of K Python floats, checked against the definition."""
+    radii = tuple(float(r) for r in radii)
+    soft = tuple(float(s) for s in softness) if isinstance(softness, (tuple, list)) else (float(softness),) * len(radii)
+    if shape not in ops.ENCLOSED_SHAPES:
+        raise ValueError("shape must be 'circle' or 'square'")
+    if not radii or len(soft) != len(radii):
+        raise ValueError("radii must hold at least one radius, softness one float or one per radius")
+    inv = tuple(1.0 / s if s > 0 else 0.0 for s in soft)
+    ok = all(0 < v < float("inf") for v in radii + soft + inv) and all(a < b for a, b in zip(radii, radii[1:]))
+    if not ok:
+        raise ValueError("radii must be finite, positive and strictly increasing, softness finite and positive")
+    return radii, inv
+
+
+def _enclosed_centre(S, centre):
+    """[B, F, W, 2] float64: the centroid of every row ("row"), of every field's rows together ("field"), or the given tensor."""
+    if isinstance(centre, str):
+        if centre not in ("row", "field"):
+            raise ValueError("centre must be 'row', 'field' or a tensor broadcastable to [B, F, W, 2]")
+        return ops.EnclosedEnergyFunction._centre_of(S, centre)[0]
+    return centre.to(torch.float64).expand(*S.shape[:3], 2)
+
+
+def _enclosed_torch(x, y, ray_ok, radii, inv_soft, shape, centre):
+    """The definition of enclosed_energy in torch ops, in float64, on any device: (S [B, F, W, 3], sums [B, F, W, K], centre
+    [B, F, W, 2]).  It holds the ray x radius tensor the kernels never form."""
+    x, y = x.to(torch.float64), y.to(torch.float64)
+    live = ray_ok != 0
+    zero = x.new_zeros(())
+    # a dead ray is the ray at the origin that is not counted: nothing of what it holds reaches a sum or a gradient
+    x, y = torch.where(live, x, zero), torch.where(live, y, zero)
+    S = torch.stack([live.to(torch.float64).sum(dim=2), x.sum(dim=2), y.sum(dim=2)], dim=-1)
+    c = _enclosed_centre(S, centre)
+    dx, dy = x - c[:, :, None, :, 0], y - c[:, :, None, :, 1]
+    R, inv = const_tensor(radii, torch.float64, x.device), const_tensor(inv_soft, torch.float64, x.device)   # cached: no upload per call
+
+    def sigma(a):                                           # a [B, F, P, W] -> [B, F, P, W, K]
+        t = (((R - a[..., None]) * inv + 1.0) * 0.5).clamp(0.0, 1.0)
+        return t * t * (3.0 - 2.0 * t)
+    if shape == "circle":
+        r2 = dx * dx + dy * dy
+        some = r2 > 0                                       # (the root has no gradient at 0: the definition says 0 there)
+        e = sigma(torch.where(some, torch.sqrt(torch.where(some, r2, torch.ones_like(r2))), zero))
+    else:
+        e = sigma(dx.abs()) * sigma(dy.abs())
+    sums = torch.where(live[..., None], e, zero).sum(dim=2)
+    return S, sums, c
+
+
+def _enclosed_uses_kernels(fused, tensors, where):
+    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
+               and all(t.dtype == torch.float32 for t in tensors[:2]))
+    if fused and not applies:
+        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the enclosed-energy kernels run "
+                           "only on float32 tensors on one AMD GPU (there is no CPU fallback): use fused=False")
+    return applies if fused is None else bool(fused)
+
+
+def _enclosed_rays(x, y, ray_ok, where):
+    x, y, ray_ok = torch.broadcast_tensors(x, y, ray_ok)
+    if x.dim() != 4:
+        raise ValueError(f"{where} takes [B, F, P, W] tensors, got {tuple(x.shape)}")
+    return x, y, ray_ok
+
+
+def enclosed_energy(x, y, ray_ok, radii, softness, shape="circle", common=("wavelength",), centre="row", fused=None):
+    """Encircled (shape="circle") or ensquared ("square") energy of a traced fan: the share of the live rays inside a circle
+    of radius R_k, or a square of half side R_k, about a centre, under a smooth edge of half width `softness`.
+
+    x, y, ray_ok: [B, F, P, W] as RayTracer.trace_rays returns them, broadcastable.  A ROW is one (lens, field, wavelength); a
+    ray is LIVE iff ray_ok != 0.  A dead ray adds exactly 0 to every sum and receives exactly 0 gradient, whatever its
+    coordinates hold (NaN, +-inf, 1e30); live rays must be finite.  Per row S = (n, sum x, sum y) over the live rays.
+    `centre`: "row" -- (sum x / n, sum y / n) of the row, 0 for an empty row; "field" -- S summed over the wavelengths first:
+    one polychromatic centroid per field, so lateral colour counts as spread; or a tensor broadcastable to [B, F, W, 2] (the
+    chief ray, an ideal image point), differentiable.
+    The edge is sigma(u) = 0 for u <= -1, 1 for u >= 1, else t^2 (3 - 2 t) with t = (u + 1) / 2, so sigma'(u) = 3 t (1 - t)
+    inside the band: C1, of compact support (a ray farther than the softness from the edge counts exactly 0 or 1), a
+    polynomial.  It is part of the definition: a hard count has zero gradient everywhere.  With dx = x - c_x, dy = y - c_y,
+    radii R_1 < ... < R_K (Python floats > 0) and softness tau_k > 0 (one float, or K of them),
+        circle   e_ik = sigma((R_k - rho_i) / tau_k),   rho_i = sqrt(dx^2 + dy^2)
+        square   e_ik = sigma((R_k - |dx_i|) / tau_k) sigma((R_k - |dy_i|) / tau_k)
+    (the quotient formed as a product with 1 / tau_k), sums[row, k] = sum over live rays of e_ik, and energy = pooled sums /
+    pooled n: `common`, a subset of ("field", "wavelength"), adds sums and n over the named dimensions before the division, as
+    through_focus does; a pooled set with n = 0 gives energy 0 with zero gradient.
+    Gradients: circle d e_ik / dx_i = -sigma'(u) / tau_k dx / rho (0 at rho = 0); square -sigma'(u_x) sigma(u_y) / tau_k sgn(dx)
+    with sgn(0) = 0; y likewise; d / dc = -sum_i d / dx_i; through an internal centroid dc_x / dx_i = 1 / n on live rays.  Radii
+    and softness are host numbers, not differentiable.
+
+    Returns EnclosedEnergy(n, energy [..., K], centre [B, F, W, 2]) in the dtype of x.  `fused`: False -- the definition in
+    torch ops in float64 on any device (it holds a ray x radius tensor several times over); True -- the HIP kernels
+    (ops.EnclosedEnergyFunction: float32 x, y on one AMD GPU, anything else raises; at most 32 radii per launch, longer lists
+    go in several); None -- the kernels where they apply.  Either way every difference, product, root and sum is in float64."""
+    common = tuple(common)
+    if any(c not in ("field", "wavelength") for c in common):
+        raise ValueError("common must be a subset of ('field', 'wavelength')")
+    radii, inv = _enclosed_edge(radii, softness, shape)
+    tensors = (x, y, ray_ok) + (() if isinstance(centre, str) else (centre,))
+    use = _enclosed_uses_kernels(fused, tensors, "enclosed_energy")
+    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "enclosed_energy")
+    if isinstance(centre, str) and centre not in ("row", "field"):
+        raise ValueError("centre must be 'row', 'field' or a tensor broadcastable to [B, F, W, 2]")
+    if use:
+        parts = []
+        for k in range(0, len(radii), ops.ENCLOSED_MAX_K):
+            S, sums = ops.EnclosedEnergyFunction.apply(x, y, ray_ok, centre, radii[k:k + ops.ENCLOSED_MAX_K],
+                                                       inv[k:k + ops.ENCLOSED_MAX_K], shape)
+            parts.append(sums)
+        sums = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+        c = _enclosed_centre(S, centre)
+    else:
+        S, sums, c = _enclosed_torch(x, y, ray_ok, radii, inv, shape, centre)
+    n = S[..., 0]
+    dims = [d for d, name in ((1, "field"), (2, "wavelength")) if name in common]
+    if dims:
+        n, sums = n.sum(dim=dims), sums.sum(dim=dims)
+    energy = sums / n.clamp(min=1.0)[..., None]             # (n = 0: the sums are 0 and depend on nothing)
+    return EnclosedEnergy(n.detach().to(x.dtype), energy.to(x.dtype), c.to(x.dtype))        # (a count carries no gradient)
+
+
+def enclosed_radius(energy, radii, fraction):
+    """The radius that holds `fraction` of the energy, on the piecewise-linear curve through (0, 0), (R_1, E_1), ..., (R_K, E_K):
+    at the first k with E_k >= fraction,  R_{k-1} + (fraction - E_{k-1}) / (E_k - E_{k-1}) (R_k - R_{k-1}).
+
+    energy: [..., K] (enclosed_energy's); radii: the K Python floats it was computed at.  Returns (radius, reached), both of
+    energy's shape less its last dimension: float64 torch on tiny tensors, differentiable through E.  Where the curve never
+    reaches `fraction` the radius is R_K with zero gradient and reached is False.  No host synchronisation."""
+    radii = tuple(float(r) for r in radii)
+    K = len(radii)
+    if energy.shape[-1] != K:
+        raise ValueError(f"energy holds {energy.shape[-1]} radii, {K} were given")
+    E = energy.to(torch.float64)
+    R0 = const_tensor((0.0,) + radii, torch.float64, E.device)
+    E0 = torch.cat((torch.zeros_like(E[..., :1]), E), dim=-1)
+    hit = E >= fraction
+    reached = hit.any(dim=-1)
+    k = (torch.cumsum(hit.to(torch.int64), dim=-1) == 0).sum(dim=-1).clamp(max=K - 1)      # the first hit (K - 1 where none)
+    lo, hi = torch.gather(E0, -1, k[..., None])[..., 0], torch.gather(E0, -1, k[..., None] + 1)[..., 0]
+    r_lo, r_hi = R0[k], R0[k + 1]
+    good = reached & (hi > lo)
+    at = r_lo + (fraction - lo) / torch.where(good, hi - lo, torch.ones_like(hi)) * (r_hi - r_lo)
+    return torch.where(good, at, torch.where(reached, r_lo, r_hi)), reached
+
+
+def spot_centroid(x, y, ray_ok, fused=None):
+    """(n [B, F, W], centroid [B, F, W, 2]) of the live rays of every row (lens, field, wavelength), in the dtype of x: the
+    per-wavelength centroids are the lateral colour through_focus does not give.  An empty row gets centroid 0.  Sums in
+    float64; differentiable in x, y; `fused` as for enclosed_energy (tl_enclosed_centroid forward, tl_enclosed_seed backward)."""
+    use = _enclosed_uses_kernels(fused, (x, y, ray_ok), "spot_centroid")
+    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "spot_centroid")
+    if use:
+        S, _ = ops.EnclosedEnergyFunction.apply(x, y, ray_ok, "row", (), (), "circle")
+    else:
+        live = ray_ok != 0
+        x64, y64 = (torch.where(live, t.to(torch.float64), t.new_zeros((), dtype=torch.float64)) for t in (x, y))
+        S = torch.stack([live.to(torch.float64).sum(dim=2), x64.sum(dim=2), y64.sum(dim=2)], dim=-1)
+    return S[..., 0].detach().to(x.dtype), _enclosed_centre(S, "row").to(x.dtype)

@@ -149,8 +149,8 @@ def timing_ms() -> dict:
 
 
 def named_timing_ms() -> dict:
-    """Mean GPU milliseconds per call, by entry point, of the timed calls outside the trace (tl_focus_moments, tl_focus_seed)
-    since enable_timing(); synchronises the device."""
+    """Mean GPU milliseconds per call, by entry point, of the timed calls outside the trace (tl_focus_moments, tl_focus_seed,
+    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed) since enable_timing(); synchronises the device."""
     torch.cuda.synchronize()
     return {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in (_timing_named or {}).items()}
 
@@ -566,6 +566,102 @@ class FocusMomentsFunction(torch.autograd.Function):
         _call("tl_focus_seed", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], gm, *outs,
               timed="tl_focus_seed")
         return (*outs, None)
+
+
+ENCLOSED_MAX_K = 32        # radii per tl_enclosed_sums / tl_enclosed_seed call (the largest register bucket)
+ENCLOSED_SHAPES = {"circle": 0, "square": 1}
+
+
+def _host_doubles(values):
+    return (C.c_double * len(values))(*values)
+
+
+class EnclosedEnergyFunction(torch.autograd.Function):
+    """(S [B, F, W, 3], sums [B, F, W, K]), both float64, of per-ray tensors x, y, ok of ONE shape [B, F, P, W]: S = (n, sum x,
+    sum y) over the live rays (tl_enclosed_centroid), sums[.., k] = the live rays' edge terms about the centre
+    (tl_enclosed_sums); backward is tl_enclosed_seed.  `centre`: a tensor broadcastable to [B, F, W, 2] (differentiable), or
+    "row" / "field": the centroid S[.., 1:3] / n of the row, or of the field's rows together, formed here from S and
+    differentiated through.  radii, inv_soft: K <= ENCLOSED_MAX_K host floats; shape: "circle" / "square".  The three arrays
+    are brought to one layout exactly as FocusMomentsFunction does, and B is folded into F.  Nothing of size rays x K is stored."""
+
+    @staticmethod
+    def _centre_of(S, mode):
+        if mode == "field":
+            S = S.sum(dim=2, keepdim=True).expand_as(S)
+        return S[..., 1:3] / S[..., :1].clamp(min=1.0), S[..., :1].clamp(min=1.0)
+
+    @staticmethod
+    def forward(ctx, x, y, ok, centre, radii, inv_soft, shape):
+        for name, t in (("x", x), ("y", y)):
+            _require_device(t, name)
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"torchoptics_amd: the enclosed-energy kernels take float32 tensors; `{name}` is {t.dtype} "
+                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        _require_device(ok, "ray_ok")
+        dev, full = x.device, x.shape
+        B, F, P, W = full
+        K = len(radii)
+        st = _focus_layout((x, y))
+
+        def placed(t):
+            return t if _same_layout(t, full, st) else torch.empty_strided(full, st, dtype=t.dtype, device=dev).copy_(t)
+        x, y = placed(x), placed(y)
+        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
+        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
+        rays = (dev.index, B * F, P, W, x, y, oks, s_f, st[2], st[3])
+        # (no radii: S alone, metrics.spot_centroid; the seed call then runs on one radius whose seed is 0)
+        edge = (_host_doubles(radii or (1.0,)), _host_doubles(inv_soft or (1.0,)), max(K, 1), ENCLOSED_SHAPES[shape])
+        S = torch.empty((B, F, W, 3), dtype=torch.float64, device=dev)
+        sums = torch.empty((B, F, W, K), dtype=torch.float64, device=dev)
+        ws = _workspace(_lib.lib().tl_enclosed_workspace_bytes(B * F, P, W, max(K, 1)), dev)
+        _call("tl_enclosed_centroid", dev, *rays, S, ws, ws.numel(), timed="tl_enclosed_centroid")
+        if isinstance(centre, str):
+            c = EnclosedEnergyFunction._centre_of(S, centre)[0]
+        else:
+            _require_device(centre, "centre")
+            c = centre
+        c64 = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev).copy_(c)
+        if K:
+            _call("tl_enclosed_sums", dev, *rays, c64, *edge, sums, ws, ws.numel(), timed="tl_enclosed_sums")
+        ctx.save_for_backward(x, y, oks, c64, S)
+        ctx.plan = (st, s_f, edge, centre if isinstance(centre, str) else (centre.shape, centre.dtype))
+        return S, sums
+
+    @staticmethod
+    def backward(ctx, g_S, g_sums):
+        x, y, oks, c64, S = ctx.saved_tensors
+        dev, full = x.device, x.shape
+        B, F, P, W = full
+        st, s_f, edge, centre = ctx.plan
+        rays = (dev.index, B * F, P, W, x, y, oks, s_f, st[2], st[3])
+        if g_sums.shape[-1]:
+            gs = torch.empty(g_sums.shape, dtype=torch.float64, device=dev).copy_(g_sums)
+        else:
+            gs = torch.empty((B, F, W, 1), dtype=torch.float64, device=dev).zero_()
+        g_lin = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev).copy_(g_S[..., 1:3])
+        outs = [torch.empty_strided(full, st, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2]]
+        ws = _workspace(_lib.lib().tl_enclosed_workspace_bytes(B * F, P, W, edge[2]), dev)
+        g_centre = None
+        if isinstance(centre, str):
+            if all(o is None for o in outs):
+                return (None,) * 7
+            # the centroid's share: the centre's gradient alone first, then spread over the live rays it is the mean of
+            g_c = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev)
+            _call("tl_enclosed_seed", dev, *rays, c64, *edge, gs, None, None, None, g_c, ws, ws.numel(), timed="tl_enclosed_seed")
+            n1 = EnclosedEnergyFunction._centre_of(S, centre)[1]
+            if centre == "field":
+                g_c = g_c.sum(dim=2, keepdim=True).expand_as(g_lin)
+            g_lin = (g_lin + g_c / n1).contiguous()
+            _call("tl_enclosed_seed", dev, *rays, c64, *edge, gs, g_lin, *outs, None, ws, ws.numel(), timed="tl_enclosed_seed")
+        else:
+            want_c = ctx.needs_input_grad[3]
+            if all(o is None for o in outs) and not want_c:
+                return (None,) * 7
+            g_c = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev) if want_c else None
+            _call("tl_enclosed_seed", dev, *rays, c64, *edge, gs, g_lin, *outs, g_c, ws, ws.numel(), timed="tl_enclosed_seed")
+            if want_c:
+                g_centre = g_c.sum_to_size(centre[0]).to(centre[1])
+        return (*outs, None, g_centre, None, None, None)
 
 
 PSF_MAX_BINS = 32          # rows / columns of the half kernel tl_psf_accumulate takes (one 32x32 MFMA tile)
