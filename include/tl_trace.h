@@ -8,7 +8,8 @@
  * too: tl_svola_* blurs an image with the lens's PSFs, tl_warp_* resamples it through the
  * distortion map and multiplies the relative illumination in.  tl_focus_* sums the through-focus
  * moments of a traced fan (best focus, tangential / sagittal foci, axial colour), tl_enclosed_* its
- * encircled / ensquared energy under a smooth edge.
+ * encircled / ensquared energy under a smooth edge, tl_zfit_* fits Zernike wavefront coefficients
+ * to its transverse ray errors.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless marked "host";
@@ -741,6 +742,53 @@ int tl_enclosed_seed(int32_t device, int64_t F, int64_t P, int64_t W, const floa
                      const double *inv_soft /* host, K */, int K, int shape, const double *g_sums /* [F,W,K] */,
                      const double *g_lin /* [F,W,2] or NULL */, float *gx, float *gy, double *g_centre /* [F,W,2] or NULL */,
                      void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Zernike wavefront fit of a traced fan from its transverse ray errors (extension; metrics.zernike_moments / metrics.zernike_fit
+ * stand on them).  The ray error (x, y) is the gradient of the wavefront over the pupil, so the coefficients a of the Noll-indexed
+ * Zernike polynomials Z_2 .. Z_{J+1} (orthonormal over the unit disc, radial order <= `order` = N in 2 .. 6, J = (N+1)(N+2)/2 - 1;
+ * p along x, q along y) solve, per row and over its live rays, the least-squares problem
+ *   min_a  sum (x - sum_j a_j dZ_j/dp)^2 + (y - sum_j a_j dZ_j/dq)^2,     G a = b,  G_jk = sum grad Z_j . grad Z_k,
+ *   b_j = sum x dZ_j/dp + y dZ_j/dq.
+ *
+ * x, y (float) and ok (bytes) are [F, P, W] tensors that share ONE stride triple s_f, s_p, s_w (elements); px, py (float), the
+ * rays' pupil coordinates, share a triple of their own, ps_f, ps_p, ps_w (0, 1, 0 for one pupil shared by every row).  A row is one
+ * (f, w); a ray is LIVE iff ok != 0; a dead ray adds exactly 0 to every sum and gets exactly 0 gradient whatever x, y, px, py hold.
+ *
+ * tl_zfit_moments: per row the K = 3 N^2 + 2 monomial sums, with tri(a, b) = (a + b)(a + b + 1) / 2 + b,
+ *   moments[f, w, tri(a, b)]                        = sum p^a q^b          a + b <= 2N - 2          (N (2N - 1) of them; the first is n)
+ *   moments[f, w, N(2N-1) + tri(a, b)]              = sum x p^a q^b        a + b <= N - 1
+ *   moments[f, w, N(2N-1) + N(N+1)/2 + tri(a, b)]   = sum y p^a q^b        a + b <= N - 1
+ *   moments[f, w, K - 2], moments[f, w, K - 1]      = sum x^2, sum y^2
+ * in fp64 from the fp32 inputs, uncontracted: p^0 = 1, p^k = p^(k-1) p, a term is (p^a q^b) and then times x.  Layout handling,
+ * launch plan, reduction and limits are tl_focus_moments' (16-byte loads where both ray strides are 1 and the row's bases are
+ * aligned; one partial per block, a fixed-order reduce, no atomics; F W < 2^31 rows in launches of 65535; P < 2^31).
+ *
+ * tl_zfit_solve, the fit (moments not NULL): per row [rows = F W] the normal equations in the Zernike basis from the moments, scaled
+ * by their diagonal D, G^ = D^-1/2 G D^-1/2, factorised by Cholesky in natural order.  A row is VALID iff 2n >= J (fewer equations than unknowns leave G singular), every D_jj > 0 and
+ * every pivot (the value whose root is the factor's diagonal) exceeds 2^-30.  Writes a[row, J] (zeros for an invalid row),
+ * q[row] = sum (x^2 + y^2) - b . a (0 for an invalid row), valid[row] and factor[row, J J + J] (the scaled factor and D^-1/2) for the adjoint.
+ * tl_zfit_solve, the adjoint (moments NULL): from factor, a, valid and the adjoints g_a[row, J] of a and g_q[row] of
+ * q = sum (x^2 + y^2) - b . a, b_bar = G^-1 g_a - 2 g_q a, written as coef[row, J + 1]: the coefficients of sum_j b_bar_j Z_j over
+ * the monomials p^a q^b of degree 1 .. N at index tri(a, b) - 1, then 2 g_q; zeros for an invalid row.
+ * tl_zfit_seed: gx = coef_J x + d/dp sum_m coef_m p^a q^b, gy likewise with y and d/dq, per ray in fp64 (Horner), rounded once to
+ * float, written with the rays' strides into those of gx, gy that are not NULL; dead rays get zeros.
+ * No call synchronises or uploads anything.
+ *
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, F, P, W or rows below 1, F W,
+ * rows or P at or above 2^31, an order outside 2 .. 6, both outputs of the seed NULL.  TL_EWORKSPACE: workspace NULL or below
+ * tl_zfit_workspace_bytes(F, P, W, order) (0 for arguments that are refused).
+ */
+size_t tl_zfit_workspace_bytes(int64_t F, int64_t P, int64_t W, int order);
+int tl_zfit_moments(int32_t device, int64_t F, int64_t P, int64_t W, int order, const float *x, const float *y, const uint8_t *ok,
+                    int64_t s_f, int64_t s_p, int64_t s_w, const float *px, const float *py, int64_t ps_f, int64_t ps_p,
+                    int64_t ps_w, double *moments /* [F,W,K] */, void *workspace, size_t workspace_bytes, void *stream);
+int tl_zfit_solve(int32_t device, int64_t rows, int order, const double *moments /* [rows,K] or NULL */,
+                  const double *g_a /* [rows,J] */, const double *g_q /* [rows] */, double *a /* [rows,J] */, double *q /* [rows] */,
+                  uint8_t *valid /* [rows] */, double *factor /* [rows,J J + J] */, double *coef /* [rows,J + 1] */, void *stream);
+int tl_zfit_seed(int32_t device, int64_t F, int64_t P, int64_t W, int order, const float *x, const float *y, const uint8_t *ok,
+                 int64_t s_f, int64_t s_p, int64_t s_w, const float *px, const float *py, int64_t ps_f, int64_t ps_p, int64_t ps_w,
+                 const double *coef /* [F,W,J + 1] */, float *gx, float *gy, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

@@ -176,6 +176,15 @@ _SIGNATURES = {
     # ... | centre | radii, inv_soft, K, shape | g_sums, g_lin | gx, gy, g_centre | workspace, bytes | stream
     "tl_enclosed_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int, C.c_int]
                          + [_VP] * 2 + [_VP] * 3 + _WS),
+    "tl_zfit_workspace_bytes": (C.c_size_t, [C.c_int64] * 3 + [C.c_int]),
+    # device, F, P, W, order | x, y, ok | s_f, s_p, s_w | px, py | ps_f, ps_p, ps_w | moments | workspace, bytes | stream
+    "tl_zfit_moments": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [C.c_int] + [_VP] * 3 + [C.c_int64] * 3 + [_VP] * 2
+                        + [C.c_int64] * 3 + [_VP] + _WS),
+    # device, rows, order | moments (NULL: the adjoint) | g_a, g_q | a, q, valid, factor | coef | stream
+    "tl_zfit_solve": (C.c_int, [C.c_int32, C.c_int64, C.c_int] + [_VP] + [_VP] * 2 + [_VP] * 4 + [_VP] + [_VP]),
+    # ... | px, py | ps_f, ps_p, ps_w | coef | gx, gy | stream
+    "tl_zfit_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [C.c_int] + [_VP] * 3 + [C.c_int64] * 3 + [_VP] * 2
+                     + [C.c_int64] * 3 + [_VP] + [_VP] * 2 + [_VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

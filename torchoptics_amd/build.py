@@ -46,7 +46,12 @@ UNITS = {
     "tl_ssim.hip": [],         # the SSIM of two images under a Gaussian window and its gradients to both
     "tl_focus.hip": [],        # the through-focus spot moments of a traced fan (fp64 sums of x, y and the slopes) and their seeds
     "tl_enclosed.hip": [],     # the encircled / ensquared energy of a traced fan (fp64 sums under a smooth edge) and its seeds
+    "tl_zfit.hip": [],         # the Zernike wavefront fit of a traced fan from its ray errors (fp64 moments, solve, seeds)
 }
+# -mllvm options of COMMON a unit is compiled WITHOUT.  tl_zfit.hip: under the iterative-ilp scheduler this compiler's greedy
+# register allocator crashes (a segmentation fault in VirtRegAuxInfo::isRematerializable) on the moment kernels with 29 and more
+# fp64 accumulators; the default scheduler compiles them without scratch (profiles/zfit_kernel_resources.txt).
+WITHOUT = {"tl_zfit.hip": ("-amdgpu-sched-strategy=iterative-ilp",)}
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 
 
@@ -55,6 +60,15 @@ def _hipcc():
     if not os.path.exists(exe):
         raise RuntimeError("hipcc not found: the HIP library cannot be built")
     return exe
+
+
+def _without(flags, drop):
+    """`flags` less every "-mllvm <option>" pair whose option is in `drop`."""
+    out = list(flags)
+    for opt in drop:
+        i = out.index(opt)
+        del out[i - 1:i + 1]
+    return out
 
 
 def _digest(paths, flags):
@@ -86,7 +100,7 @@ def _build(OBJ, LIB, extra_flags, force, verbose):
         spath = os.path.join(CSRC, src)
         opath = os.path.join(OBJ, src.replace(".hip", ".o"))
         stamp = opath + ".sha"
-        flags = COMMON + extra + extra_flags
+        flags = _without(COMMON, WITHOUT.get(src, ())) + extra + extra_flags
         dig = _digest([spath] + deps, flags)
         fresh = (not force and os.path.exists(opath) and os.path.exists(stamp)
                  and open(stamp).read() == dig)

@@ -508,3 +508,206 @@ def spot_centroid(x, y, ray_ok, fused=None):
         x64, y64 = (torch.where(live, t.to(torch.float64), t.new_zeros((), dtype=torch.float64)) for t in (x, y))
         S = torch.stack([live.to(torch.float64).sum(dim=2), x64.sum(dim=2), y64.sum(dim=2)], dim=-1)
     return S[..., 0].detach().to(x.dtype), _enclosed_centre(S, "row").to(x.dtype)
+
+
+# ---------------------------------------------------------------------------- Zernike wavefront fit from the ray errors
+class ZernikeFit(NamedTuple):
+    """What zernike_fit returns; every member is [B, F, W], coeffs [B, F, W, J]."""
+    n: torch.Tensor                 # live rays
+    valid: torch.Tensor             # bool: the row's fit is determined (the validity rule)
+    coeffs: torch.Tensor            # scale a_j for Z_2 .. Z_{J+1} (Noll): coeffs[..., j - 2]
+    rms: torch.Tensor               # sqrt(sum_{j >= 4} coeffs_j^2): RMS wavefront error, tilt removed
+    rms_focus: torch.Tensor         # sqrt(sum_{j >= 5} coeffs_j^2): tilt and defocus removed
+    residual: torch.Tensor          # the transverse RMS ray error the polynomial does not explain
+
+
+class ZernikeBasis(NamedTuple):
+    """What zernike_basis returns."""
+    T: torch.Tensor                 # [J, J] float64: Z_{j+2}(p, q) = sum_m T[m, j] p^a_m q^b_m (+ a constant the fit never sees)
+    exponents: tuple                # ((a_m, b_m), ...): the monomials of degree 1 .. N, by degree, b ascending
+    noll: tuple                     # ((j, n, m), ...): Noll index, radial order, azimuthal frequency (m < 0: the sine term)
+
+
+ZFIT_PIVOT_FLOOR = 2.0 ** -30       # a pivot of the scaled normal equations at or below this: the row's fit is not determined
+_ZBASIS = {}
+
+
+def zernike_basis(max_order):
+    """The Noll-indexed Zernike polynomials Z_2 .. Z_{J+1} of radial order <= max_order in {2, .., 6}, J = (N+1)(N+2)/2 - 1,
+    orthonormal over the unit disc (their mean square is 1), with p = rho cos(theta) along x and q = rho sin(theta) along y:
+    Z_j = N_nm R_n^m(rho) cos(m theta) for even j, sin for odd j, N_n0 = sqrt(n + 1), N_nm = sqrt(2 (n + 1)); so Z2 = 2 p,
+    Z3 = 2 q, Z4 = sqrt(3) (2 rho^2 - 1), Z11 = sqrt(5) (6 rho^4 - 6 rho^2 + 1).  Returns ZernikeBasis(T, exponents, noll): the
+    monomial coefficients from the closed form (a host tensor; the constant terms, which have no gradient, are left out)."""
+    from math import comb, factorial, sqrt
+    J, _ = ops.zfit_sizes(max_order)
+    if max_order not in _ZBASIS:
+        expo = tuple((d - b, b) for d in range(1, max_order + 1) for b in range(d + 1))
+        at = {e: i for i, e in enumerate(expo)}
+        T = torch.zeros((J, J), dtype=torch.float64)
+        noll = []
+        for j in range(2, J + 2):
+            n = 0
+            while (n + 1) * (n + 2) // 2 < j:
+                n += 1
+            k = j - n * (n + 1) // 2
+            m = 2 * (k // 2) if n % 2 == 0 else 2 * ((k - 1) // 2) + 1
+            sine = m != 0 and j % 2 == 1
+            noll.append((j, n, -m if sine else m))
+            norm = sqrt(n + 1) if m == 0 else sqrt(2 * (n + 1))
+            for s in range((n - m) // 2 + 1):
+                rc = (-1) ** s * factorial(n - s) // (factorial(s) * factorial((n + m) // 2 - s) * factorial((n - m) // 2 - s))
+                t = (n - m) // 2 - s            # rho^(m + 2 t) cos / sin (m theta) = (p^2 + q^2)^t Re / Im (p + i q)^m
+                for u in range(t + 1):
+                    for h in range(1 if sine else 0, m + 1, 2):
+                        e = (2 * (t - u) + m - h, 2 * u + h)
+                        if e != (0, 0):
+                            T[at[e], j - 2] += norm * rc * comb(t, u) * comb(m, h) * (-1) ** (h // 2)
+        _ZBASIS[max_order] = ZernikeBasis(T, expo, tuple(noll))
+    return _ZBASIS[max_order]
+
+
+def _zfit_uses_kernels(fused, tensors, where):
+    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
+               and all(t.dtype == torch.float32 for t in tensors[:2]))
+    if fused and not applies:
+        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the Zernike-fit kernels run only "
+                           "on float32 rays on one AMD GPU (there is no CPU fallback): use fused=False")
+    return applies if fused is None else bool(fused)
+
+
+def _zfit_rays(x, y, ray_ok, px, py, where):
+    x, y, ray_ok, px, py = torch.broadcast_tensors(x, y, ray_ok, px, py)
+    if x.dim() != 4:
+        raise ValueError(f"{where} takes [B, F, P, W] tensors, got {tuple(x.shape)}")
+    return x, y, ray_ok, px, py
+
+
+def _zfit_powers(p, q, top):
+    """p^k, q^k for k = 0 .. top as lists: p^0 = 1, p^k = p^(k-1) p."""
+    pp, qq = [torch.ones_like(p)], [torch.ones_like(q)]
+    for _ in range(top):
+        pp.append(pp[-1] * p)
+        qq.append(qq[-1] * q)
+    return pp, qq
+
+
+def _zfit_live(x, y, ray_ok, px, py):
+    """The rays in float64 with the dead ones at the origin of the spot and of the pupil, and the live mask."""
+    live = ray_ok != 0
+    zero = x.new_zeros((), dtype=torch.float64)
+    return tuple(torch.where(live, t.to(torch.float64), zero) for t in (x, y, px, py)) + (live,)
+
+
+def _zernike_moments_torch(x, y, ray_ok, px, py, order):
+    x, y, p, q, live = _zfit_live(x, y, ray_ok, px, py)
+    pp, qq = _zfit_powers(p, q, 2 * order - 2)
+    mono = lambda top: [(d - b, b) for d in range(top + 1) for b in range(d + 1)]                       # noqa: E731
+    terms = [live.to(torch.float64) if (a, b) == (0, 0) else pp[a] * qq[b] for a, b in mono(2 * order - 2)]
+    terms += [(pp[a] * qq[b]) * x for a, b in mono(order - 1)] + [(pp[a] * qq[b]) * y for a, b in mono(order - 1)] + [x * x, y * y]
+    return torch.stack([t.sum(dim=2) for t in terms], dim=-1)
+
+
+def zernike_moments(x, y, ray_ok, px, py, max_order=4, fused=None):
+    """The K = 3 N^2 + 2 monomial sums [B, F, W, K] (float64) the Zernike fit of order N = max_order is formed from: per row,
+    over the live rays (ray_ok != 0), with tri(a, b) = (a + b)(a + b + 1) / 2 + b,
+        M[tri(a, b)] = sum p^a q^b (a + b <= 2N - 2; M[0] = n),   then sum x p^a q^b and sum y p^a q^b (a + b <= N - 1, each by tri),
+        then sum x^2, sum y^2,
+    p^0 = 1, p^k = p^(k-1) p, a term (p^a q^b) and then times x, all in float64.  A dead ray adds exactly 0 whatever it holds.
+    An intermediate: it carries no gradient (zernike_fit does).  `fused` as for zernike_fit."""
+    ops.zfit_sizes(max_order)
+    use = _zfit_uses_kernels(fused, (x, y, ray_ok, px, py), "zernike_moments")
+    x, y, ray_ok, px, py = _zfit_rays(x, y, ray_ok, px, py, "zernike_moments")
+    if use:
+        return ops.ZernikeFitFunction.apply(x, y, ray_ok, px, py, max_order)[0]
+    return _zernike_moments_torch(x, y, ray_ok, px, py, max_order).detach()
+
+
+def _zernike_fit_torch(x, y, ray_ok, px, py, order):
+    """The definition of zernike_fit in torch ops, in float64, design-matrix form: (n, a, q, valid)."""
+    basis = zernike_basis(order)
+    J = len(basis.noll)
+    x, y, p, q, live = _zfit_live(x, y, ray_ok, px, py)
+    pp, qq = _zfit_powers(p, q, order)
+    zero = torch.zeros_like(p)
+    dp = torch.stack([a * pp[a - 1] * qq[b] if a else zero for a, b in basis.exponents], dim=-1)       # [B,F,P,W,J] monomials
+    dq = torch.stack([b * pp[a] * qq[b - 1] if b else zero for a, b in basis.exponents], dim=-1)
+    T = const_tensor(basis.T.tolist(), torch.float64, x.device)
+    lv = live[..., None]
+    # [B,F,W,P,J]: dZ_j/dp, dZ_j/dq (the pupil has no gradient)
+    Ap = torch.where(lv, dp @ T, zero[..., None]).permute(0, 1, 3, 2, 4).detach()
+    Aq = torch.where(lv, dq @ T, zero[..., None]).permute(0, 1, 3, 2, 4).detach()
+    xr, yr = x.permute(0, 1, 3, 2)[..., None], y.permute(0, 1, 3, 2)[..., None]                       # [B,F,W,P,1]
+    G = Ap.transpose(-1, -2) @ Ap + Aq.transpose(-1, -2) @ Aq
+    b = (Ap.transpose(-1, -2) @ xr + Aq.transpose(-1, -2) @ yr)[..., 0]                                # [B,F,W,J]
+    n = live.to(torch.float64).sum(dim=2)
+    D = torch.diagonal(G, dim1=-2, dim2=-1)
+    pos = (D > 0).all(dim=-1) & (2 * n >= J)
+    isd = torch.where(pos[..., None], D.clamp(min=1e-300).rsqrt(), torch.ones_like(D))
+    eye = torch.eye(J, dtype=torch.float64, device=x.device)
+    Gs = torch.where(pos[..., None, None], G * isd[..., :, None] * isd[..., None, :], eye)
+    L, info = torch.linalg.cholesky_ex(Gs)
+    piv = torch.diagonal(L, dim1=-2, dim2=-1) ** 2
+    valid = pos & (info == 0) & (piv > ZFIT_PIVOT_FLOOR).all(dim=-1)                                   # (NaN > floor is false)
+    L = torch.where(valid[..., None, None], L, eye)
+    a = torch.cholesky_solve((b * isd)[..., None], L)[..., 0] * isd
+    a = torch.where(valid[..., None], a, torch.zeros_like(a))
+    qsum = (x * x + y * y).sum(dim=2) - (b * a).sum(dim=-1)
+    return n, a, torch.where(valid, qsum, torch.zeros_like(qsum)), valid
+
+
+def zernike_fit(x, y, ray_ok, px, py, max_order=4, scale=None, fused=None):
+    """Zernike coefficients of the wavefront, and its RMS error, from the transverse ray errors of a traced fan.
+
+    The transverse ray error is the gradient of the wavefront over the pupil, so the coefficients follow from a linear
+    least-squares fit of the spot (x, y) against the gradients of the Zernike polynomials at each ray's pupil coordinates --
+    the modal reconstruction of a Shack-Hartmann sensor.  It needs no optical path length: its inputs are x, y, ray_ok, which
+    every trace gives at full accuracy, in either precision.
+
+    x, y, ray_ok: [B, F, P, W] as RayTracer.trace_rays returns them; px, py: the rays' pupil coordinates relative to the pupil
+    radius (RayTracer.pupil_coordinates), broadcastable -- [1, 1, P, 1] for one shared pupil, which is not copied.  The
+    caller's coordinates define the unit disc.  N = max_order in {2, 3, 4, 5, 6}, J = (N+1)(N+2)/2 - 1 = 5, 9, 14, 20, 27; Z_j,
+    j = 2 .. J+1, are the Noll-indexed polynomials of zernike_basis(N), orthonormal over the unit disc, p along x, q along y.
+    A ROW is one (lens, field, wavelength).  A ray is live iff ray_ok != 0; a dead ray adds exactly 0 to every sum and receives
+    exactly 0 gradient, whatever x, y, px, py hold at it (NaN, +-inf, 1e30).  Per row, over the live rays, minimise over a
+        sum_i (x_i - sum_j a_j dZ_j/dp(p_i, q_i))^2 + (y_i - sum_j a_j dZ_j/dq(p_i, q_i))^2:
+    the tilt terms have constant gradients, so they absorb the centroid and no separate centring is needed.  The normal
+    equations are G a = b with G_jk = sum_i grad Z_j . grad Z_k and b_j = sum_i (x_i dZ_j/dp + y_i dZ_j/dq).  Outputs:
+        coeffs    = scale a, [B, F, W, J]; `scale` broadcastable to [B, F, W], default 1; for an object at infinity
+                    epd / (2 efl) / lambda gives waves (x, y and lambda in the same unit).  Applied in torch, differentiable.
+        rms       = sqrt(sum_{j >= 4} coeffs_j^2): tilt removed;   rms_focus = sqrt(sum_{j >= 5} coeffs_j^2): and defocus
+        residual  = sqrt(max(sum (x^2 + y^2) - b . a, 0) / n): the transverse RMS the polynomial does not explain
+        n         the live-ray count;   valid   the flag below.
+    The root of a value <= 0 is 0 with zero gradient.
+    VALIDITY.  With D = diag(G) and G^ = D^-1/2 G D^-1/2, a row is valid iff 2 n >= J (fewer equations than
+    unknowns leave G singular in exact arithmetic; rounding must not decide that), every D_jj > 0 and every pivot of the
+    Cholesky factorisation of G^ (natural order, no pivoting; the pivot is the value whose root is the factor's diagonal)
+    exceeds ZFIT_PIVOT_FLOOR = 2^-30.  That leaves float64 23 bits in the coefficients, the precision of the inputs; a full
+    disc's smallest pivot is ~1/130 at order 6.  An invalid row (one ray, fewer than J / 2 rays, a meridional-only fan)
+    returns 0 everywhere with zero gradients and valid = False.
+    SIGN.  W = +scale a agrees with the oracle's optical path length (held by a test).  The relation between slope and
+    wavefront is first order in the pupil's aberration: off axis the coefficients differ from a fit of the optical path
+    difference by a few per cent (README).  Gradients flow to x, y and scale; px, py and ray_ok get none.
+
+    Returns ZernikeFit(n, valid, coeffs, rms, rms_focus, residual) in the dtype of x (valid bool).  `fused`: False -- this
+    definition in float64 torch ops on any device and dtype (it holds the rays x J design matrix); True -- the HIP kernels
+    (ops.ZernikeFitFunction: float32 x, y on one AMD GPU, anything else raises), which form G and b from K = 3 N^2 + 2
+    monomial sums per row; None -- the kernels where they apply.  Either way every product and sum is in float64."""
+    ops.zfit_sizes(max_order)
+    tensors = (x, y, ray_ok, px, py) + ((scale,) if torch.is_tensor(scale) else ())
+    use = _zfit_uses_kernels(fused, tensors, "zernike_fit")
+    x, y, ray_ok, px, py = _zfit_rays(x, y, ray_ok, px, py, "zernike_fit")
+    if use:
+        M, a, q, valid = ops.ZernikeFitFunction.apply(x, y, ray_ok, px, py, max_order)
+        n, valid = M[..., 0], valid != 0
+    else:
+        n, a, q, valid = _zernike_fit_torch(x, y, ray_ok, px, py, max_order)
+    if scale is None:
+        coeffs = a
+    elif torch.is_tensor(scale):
+        coeffs = a * scale.to(torch.float64)[..., None]
+    else:
+        coeffs = a * float(scale)
+    sq = coeffs * coeffs
+    out = ZernikeFit(n=n.detach(), valid=valid, coeffs=coeffs, rms=_root_of_variance(sq[..., 2:].sum(dim=-1)),
+                     rms_focus=_root_of_variance(sq[..., 3:].sum(dim=-1)), residual=_root_of_variance(q / n.detach().clamp(min=1.0)))
+    return ZernikeFit(*(t if t.dtype == torch.bool else t.to(x.dtype) for t in out))

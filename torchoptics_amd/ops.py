@@ -150,7 +150,8 @@ def timing_ms() -> dict:
 
 def named_timing_ms() -> dict:
     """Mean GPU milliseconds per call, by entry point, of the timed calls outside the trace (tl_focus_moments, tl_focus_seed,
-    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed) since enable_timing(); synchronises the device."""
+    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed, tl_zfit_moments, tl_zfit_solve, tl_zfit_seed) since enable_timing();
+    synchronises the device."""
     torch.cuda.synchronize()
     return {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in (_timing_named or {}).items()}
 
@@ -662,6 +663,94 @@ class EnclosedEnergyFunction(torch.autograd.Function):
             if want_c:
                 g_centre = g_c.sum_to_size(centre[0]).to(centre[1])
         return (*outs, None, g_centre, None, None, None)
+
+
+ZFIT_ORDERS = (2, 3, 4, 5, 6)      # radial orders the tl_zfit_* kernels are instantiated for
+
+
+def zfit_sizes(order):
+    """(J, K) of a Zernike fit of radial order `order`: coefficients Z_2 .. Z_{J+1}, monomial sums per row (include/tl_trace.h)."""
+    if order not in ZFIT_ORDERS:
+        raise ValueError(f"max_order must be one of {ZFIT_ORDERS}, got {order!r}")
+    return (order + 1) * (order + 2) // 2 - 1, 3 * order * order + 2
+
+
+def _pupil_layout(px, py, shape, dev):
+    """px, py [B,F,P,W] as the zfit kernels read them: one stride quadruple for both whose lenses fold into its fields.  The
+    kernels only read them, so an expanded pupil (stride 0 over lenses, fields and wavelengths) goes as it is; what is not
+    float32 on `dev`, or strided otherwise, is copied into the tracer's [B,F,W,P] memory."""
+    B, F, P, W = shape
+    st = px.stride()
+
+    def folds(t):
+        s = t.stride()
+        return B == 1 or F == 1 or s[0] == F * s[1]
+    if not (px.dtype == py.dtype == torch.float32 and px.device == py.device == dev and folds(px) and _same_layout(py, shape, st)):
+        st = (F * W * P, W * P, 1, P)
+        px, py = (torch.empty_strided(shape, st, dtype=torch.float32, device=dev).copy_(t) for t in (px, py))
+    return px, py, (st[1] if B == 1 else st[0] if F == 1 else st[1], st[2], st[3])
+
+
+class ZernikeFitFunction(torch.autograd.Function):
+    """(moments [B, F, W, K], a [B, F, W, J], q [B, F, W], valid [B, F, W]) of per-ray tensors x, y, ok, px, py of ONE shape
+    [B, F, P, W] (the caller broadcasts): the monomial sums of tl_zfit_moments, the coefficients a of the least-squares fit of
+    (x, y) against the gradients of the Noll Zernike polynomials Z_2 .. Z_{J+1} at the pupil coordinates (px, py), the residual
+    sum q = sum (x^2 + y^2) - b . a and the validity flag (tl_zfit_solve); float64, uint8 the flag.  An invalid row has a = 0,
+    q = 0.  Backward: tl_zfit_solve's adjoint and tl_zfit_seed, to x and y only; the moments are an intermediate and carry no
+    gradient.  x, y, ok are brought to one layout exactly as FocusMomentsFunction does, px and py are read with strides of their
+    own (_pupil_layout), and B is folded into F."""
+
+    @staticmethod
+    def forward(ctx, x, y, ok, px, py, order):
+        J, K = zfit_sizes(order)
+        for name, t in (("x", x), ("y", y)):
+            _require_device(t, name)
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"torchoptics_amd: the Zernike-fit kernels take float32 rays; `{name}` is {t.dtype} "
+                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        for name, t in (("ray_ok", ok), ("px", px), ("py", py)):
+            _require_device(t, name)
+        dev, shape = x.device, x.shape
+        B, F, P, W = shape
+        st = _focus_layout((x, y))
+
+        def placed(t):
+            return t if _same_layout(t, shape, st) else torch.empty_strided(shape, st, dtype=t.dtype, device=dev).copy_(t)
+        x, y = placed(x), placed(y)
+        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
+        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
+        px, py, pst = _pupil_layout(px, py, shape, dev)
+        rays = (dev.index, B * F, P, W, order, x, y, oks, s_f, st[2], st[3], px, py, *pst)
+        moments = torch.empty((B, F, W, K), dtype=torch.float64, device=dev)
+        a = torch.empty((B, F, W, J), dtype=torch.float64, device=dev)
+        q = torch.empty((B, F, W), dtype=torch.float64, device=dev)
+        valid = torch.empty((B, F, W), dtype=torch.uint8, device=dev)
+        factor = torch.empty((B, F, W, J * J + J), dtype=torch.float64, device=dev)
+        ws = _workspace(_lib.lib().tl_zfit_workspace_bytes(B * F, P, W, order), dev)
+        _call("tl_zfit_moments", dev, *rays, moments, ws, ws.numel(), timed="tl_zfit_moments")
+        _call("tl_zfit_solve", dev, dev.index, B * F * W, order, moments, None, None, a, q, valid, factor, None, timed="tl_zfit_solve")
+        ctx.save_for_backward(x, y, oks, px, py, a, valid, factor)
+        ctx.plan = (order, st, s_f, pst)
+        ctx.mark_non_differentiable(moments, valid)
+        return moments, a, q, valid
+
+    @staticmethod
+    def backward(ctx, _g_moments, g_a, g_q, _g_valid):
+        x, y, oks, px, py, a, valid, factor = ctx.saved_tensors
+        dev, shape = x.device, x.shape
+        B, F, P, W = shape
+        order, st, s_f, pst = ctx.plan
+        J, _ = zfit_sizes(order)
+        outs = [torch.empty_strided(shape, st, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2]]
+        if all(o is None for o in outs):
+            return (None,) * 6
+        ga = torch.empty((B, F, W, J), dtype=torch.float64, device=dev).copy_(g_a)
+        gq = torch.empty((B, F, W), dtype=torch.float64, device=dev).copy_(g_q)
+        coef = torch.empty((B, F, W, J + 1), dtype=torch.float64, device=dev)
+        _call("tl_zfit_solve", dev, dev.index, B * F * W, order, None, ga, gq, a, None, valid, factor, coef, timed="tl_zfit_solve")
+        _call("tl_zfit_seed", dev, dev.index, B * F, P, W, order, x, y, oks, s_f, st[2], st[3], px, py, *pst, coef, *outs,
+              timed="tl_zfit_seed")
+        return (*outs, None, None, None, None)
 
 
 PSF_MAX_BINS = 32          # rows / columns of the half kernel tl_psf_accumulate takes (one 32x32 MFMA tile)

@@ -687,6 +687,20 @@ class RayTracer:
         up, down, vx = (self.vig_fn(fields, v) for v in (specs.vig_up, specs.vig_down, specs.vig_x))
         return apply_vignetting(yp_rel, up, down), apply_vignetting(xp_rel, vx, vx)
 
+    def pupil_coordinates(self, specs, lens, use_vig=True):
+        """(xp, yp): the relative pupil coordinates `assemble` starts the fan from -- the mode's pupil grid in units of the
+        entrance pupil's radius, after vignetting (`use_vig` and a vig_fn: then [B,F,P,1]) and before ray aiming, detached;
+        [1,1,P,1] for one pupil shared by every row.  They are the (px, py) metrics.zernike_fit takes.  The deterministic
+        modes give the coordinates trace_rays uses; 'skew_random' draws anew on every call (pass them on as trace_rays' xy)."""
+        dev = self.default_device
+        if self.double_precision and lens.c.dtype != torch.float64:
+            specs, lens = specs.double(), lens.double()
+        z = compute_pupil_position(lens, self.arith, front=lens.up_to_stop()).reshape(-1, 1, 1, 1)
+        xp_rel, yp_rel = self.pupil_span(z)
+        if use_vig and self.vig_fn is not None and self.mode != 'chief':
+            yp_rel, xp_rel = self._vignette(specs, yp_rel.to(dev), xp_rel.to(dev))
+        return xp_rel.to(dev).detach(), yp_rel.to(dev).detach()
+
     def trace_rays(self, specs, lens, use_vig=True, aggregate=False, xy=None, up_to_stop=False, want_opd=False,
                    x_moments=False):
         a = self.assemble(specs, lens, xy=xy, up_to_stop=up_to_stop, use_vig=use_vig)
