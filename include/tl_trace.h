@@ -222,7 +222,10 @@ int tl_trace_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out,
  *     the forward left their flags in p->cond_flags (read in place of fwd->ok, which may then be NULL; the ok bytes given
  *     otherwise must be 0 / 1 as tl_trace_fwd writes them), for the whole launch when it did not -- or
  *   - the walk-back met a non-finite adjoint (it then flags a word at the end of the workspace): the whole launch.
- * Pass `fwd->moments` whenever it is available: without it an ill-conditioned fan is walked back anyway.
+ * Pass `fwd->moments` whenever it is available.  It may be NULL only when p->cond_flags is NULL too: an ill-conditioned fan is
+ * then walked back anyway (nothing tells the call that it holds such rays).  With p->cond_flags and no `fwd->moments` the
+ * call is refused (TL_EINVAL, before any HIP call; the message names cond_flags and moments): the walk-back leaves the rays
+ * flagged 2 to the checkpoint kernel, which takes them only when the moments count them -- their gradient would be dropped.
  * allow_backward = 1 only, no OPD gradient (TL_EINVAL for g->g_opd or out->g_n_index: use tl_trace_bwd).  Aspheric rows
  * are walked back too (g_kappa, g_poly as in tl_trace_bwd, required iff p->surf_kind).
  * Workspace: tl_workspace_bytes(p); its contents need not be initialised.
@@ -231,11 +234,30 @@ int tl_trace_bwd(const tl_problem *p, const tl_seeds *g, const tl_grads *out,
  * that one replay that had to fall back does not pin every later replay to the (exact, slower) checkpoint kernel.
  * Penalty term (p->aggregate, ABI 13): walked back too for lenses of 3..20 rows -- the rays alive at the image plane by
  * the walk-back kernel, the rays that died on the way (they keep the gradient of the rows they passed alive) by the
- * checkpoint kernel in the same call; other lenses are handed to tl_trace_bwd as a whole.  Aspheric rows (ABI 13): with
- * p->asph_hits filled by tl_trace_fwd the hit on an aspheric row is read instead of searched.
+ * checkpoint kernel in the same call; other lenses, pupils of fewer than 256 points and aspheric lenses whose hits were not
+ * stored are handed to tl_trace_bwd as a whole (the bits of tl_trace_bwd; tl_bwd_route below names the decision).  Aspheric
+ * rows (ABI 13): with p->asph_hits filled by tl_trace_fwd the hit on an aspheric row is read instead of searched.
  */
 int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_rays *fwd, const tl_grads *out,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Which kernels tl_trace_bwd_from_outputs enqueues for `p` -- the decision it takes on the host, from S, P, aggregate,
+ * surf_kind, asph_hits and asph_hit_slots alone (nothing else of `p` is read, no pointer is followed, no HIP call is made:
+ * callable without a device; additive entry point, ABI unchanged):
+ *   TL_ROUTE_CHECKPOINT      the whole call is handed to tl_trace_bwd: the penalty term (p->aggregate) of a lens outside
+ *                            3..20 rows, of a pupil below 256 points, or with aspheric rows whose hits are not stored
+ *                            (p->asph_hits NULL or p->asph_hit_slots 0).  The gradients have the bits of tl_trace_bwd.
+ *   TL_ROUTE_WALK_ROLLED     trace_bwd_inv_kernel, rows in a loop: no penalty term, and 1, 2 or 21..32 rows, or P < 256, or
+ *                            aspheric rows without stored hits (Newton iteration on the reversed ray).
+ *   TL_ROUTE_WALK_UNROLLED   trace_bwd_inv_unrolled_kernel<S>: 3..20 rows, P >= 256, aspheric rows (if any) with stored hits;
+ *                            with or without the penalty term.
+ *   TL_ROUTE_EMPTY           P = 0: an empty shard, the gradients are zeroed by memsets.
+ * Behind either walk-back the checkpoint kernel is still enqueued and takes, on the device, what the walk-back leaves (see
+ * above): the route names the launch, not every ray's path.  TL_EINVAL for p NULL, S outside 1..TL_MAX_SURFACES or P < 0.
+ */
+enum { TL_ROUTE_CHECKPOINT = 0, TL_ROUTE_WALK_ROLLED = 1, TL_ROUTE_WALK_UNROLLED = 2, TL_ROUTE_EMPTY = 3 };
+int tl_bwd_route(const tl_problem *p);
 
 /*
  * Spot moments of arbitrary per-ray tensors (same TL_NMOM layout): the reduction inside

@@ -20,6 +20,13 @@ sources by test_row_matrix_covers_every_instantiation_and_boundary, which needs 
 pupil (P < 256: rolled walk-back, penalty on the checkpoint kernel) at S = 3, 12, 13, 20, two hit-slot edge cases and lens
 batches of three.  Lenses: truncations / extensions of zoom20 (zoom20_rows.lens_args).
 
+Each cell also asserts that ops.backward_route names the family listed above for it (_family; tl_bwd_route's own answer is
+checked against it without a GPU).  The route is the launch, not every ray's path: test_gpu_backward_route.py found on the
+device that trace_bwd_inv_kernel<true> flags a non-finite adjoint on every fan that holds a dead ray -- all of _fan's -- so the
+aspheric rms cells of the rolled range here (S = 1, 2, 21..32, and P = 200) are launched on that kernel and differentiated by
+the checkpoint kernel behind it.  The rolled aspheric walk-back itself is held to the oracle by that file's cells on the same
+fans without their dead rays (ADVICE.md has the finding).
+
 One oracle run per (lens, pupil) in fp32 (IEEE sqrt) and one in fp64, with two retained backward passes (rms, sumQ): the
 reference for the penalty loss is g_rms + lam g_Q, lam = |g_rms(c)| / |g_Q(c)| in fp64 so that both terms carry
 comparable gradient (sumQ grows with the ray count: ~1.3e3 on these fans against an rms of 1e-3..1).  Gates are against fp64 only;
@@ -216,7 +223,7 @@ def _run_gpu(ta, lenses, S, variant, pen, lam, mode, algo, weights=None):
     try:
         out = ta.trace_skew(a0["x"].to(DEV), a0["y"].to(DEV), lv["z"], a0["cx"].to(DEV), lv["cy"], lv["c"], lv["t"], lv["mu"],
                             a0["mask"].to(DEV), True if pen else False, True, mode=mode, **kw)
-        inv = ops.used_walk_back(out[0])
+        inv, route = ops.used_walk_back(out[0]), ops.backward_route(out[0])
         if B > 1:
             if pen:
                 ld = rt.unsupervised_loss_batch(out, S, lam)
@@ -233,7 +240,7 @@ def _run_gpu(ta, lenses, S, variant, pen, lam, mode, algo, weights=None):
     finally:
         ops.set_backward_algorithm("inverse")
         ops.set_asph_hit_slots(4)
-    return dict(fwd=[t.detach().cpu() for t in out[:6]], inv=inv,
+    return dict(fwd=[t.detach().cpu() for t in out[:6]], inv=inv, route=route,
                 rms=rms.detach().cpu().double().reshape(-1), q=None if q is None else q.detach().cpu().double().reshape(-1),
                 grads={n: lv[n].grad.detach().cpu().double() for n in names})
 
@@ -340,6 +347,17 @@ _MODES = ("strict", "fast")
 _ALGOS = ("inverse", "checkpoint")
 
 
+def _family(S, P, pen, algo):
+    """The kernel family the module docstring lists for a cell, in the words of ops.backward_route.  Every variant of the
+    matrix stores its aspheric hits (4 or 8 slots), 'asph5' included: its launch is the unrolled walk-back, which hands the
+    lens to the checkpoint kernel on the device."""
+    if algo == "checkpoint":
+        return "checkpoint"
+    if 3 <= S <= 20 and P >= 256:
+        return "walk_unrolled"
+    return "checkpoint" if pen else "walk_rolled"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("algo", _ALGOS)
 @pytest.mark.parametrize("mode", _MODES)
@@ -362,6 +380,7 @@ def test_backward_instantiation_matches_fp64_oracle(ta, S, variant, P, loss, mod
     got = _run_gpu(ta, [a], S, variant, pen, lam, mode, algo)
     tag = f"S={S} {variant} P={P} {loss} {mode} {algo}"
     assert got["inv"] is (algo == "inverse"), tag
+    assert got["route"] == _family(S, P, pen, algo), (tag, got["route"])
     _check_forward(tag, got["fwd"], r["f32"]["fwd"], r["f64"]["fwd"], exact=(variant == "sph" and mode == "strict"), k=k)
     _check_losses(tag, got["rms"].item(), None if got["q"] is None else got["q"].item(), r, pen, k)
     msg = _grad_errors(tag, got["grads"], _ref_grad(r["f32"], pen, lam), _ref_grad(r["f64"], pen, lam), pen, k,
@@ -384,6 +403,7 @@ def test_lens_batch_matches_fp64_oracle_per_lens(ta, S, variant, loss, mode, alg
     got = _run_gpu(ta, [r["args"] for r in rs], S, variant, pen, lam, mode, algo, weights=BATCH_W)
     tag = f"batch S={S} {variant} {loss} {mode} {algo}"
     assert got["inv"] is (algo == "inverse"), tag
+    assert got["route"] == _family(S, P_MAIN, pen, algo), (tag, got["route"])
     msg = []
     shared = {}
     for b, (r, w) in enumerate(zip(rs, BATCH_W)):
@@ -456,3 +476,20 @@ def test_row_matrix_covers_every_instantiation_and_boundary():
         if S >= pair + 2:
             assert any(pair <= j < S - 1 for j in rows_a), (S, rows_a)
     assert len(_asph_rows(20, "asph8")) == 8 and len(_asph_rows(16, "asph5")) == 5
+    # the kernel family each cell asserts (_family) is tl_bwd_route's answer for the problem the host chains build there,
+    # and every family of the docstring is reached with and without the penalty term where it exists
+    import ctypes as C
+    from torchoptics_amd import _lib, ops
+    reached = set()
+    for S, variant, P in LENSES:
+        for pen in (False, True):
+            if pen and S > 31:
+                continue
+            p = _lib.tl_problem()
+            p.F, p.W, p.S, p.P, p.aggregate = 3, 3, S, P, int(pen)
+            if variant != "sph":
+                p.surf_kind = p.kappa = p.poly = p.asph_hits = 8            # (addresses: never followed)
+                p.asph_hit_slots = min(HIT_SLOTS.get(variant, 4), S)
+            assert ops.BACKWARD_ROUTES[_lib.lib().tl_bwd_route(C.byref(p))] == _family(S, P, pen, "inverse"), (S, variant, P, pen)
+            reached.add((_family(S, P, pen, "inverse"), pen))
+    assert reached == {("walk_unrolled", False), ("walk_unrolled", True), ("walk_rolled", False), ("checkpoint", True)}

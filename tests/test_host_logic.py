@@ -232,6 +232,70 @@ def test_new_entry_points_refuse_bad_arguments_before_touching_a_device():
     p.P = 1 << 24
     big = dll.tl_workspace_bytes(C.byref(p))
     assert big - small >= ((1 << 24) - (1 << 20)) // 256 * 4          # one byte per chunk and wave of the block
+    # tl_trace_bwd_from_outputs: the conditioning flags without the forward's moments (the checkpoint kernel would never take
+    # the rays flagged 2, and the walk-back leaves them: their gradient would be dropped) -- refused, whatever the route
+    for S, Pn, agg in ((7, 256, 0), (7, 255, 0), (2, 256, 0), (7, 256, 1), (7, 255, 1), (21, 256, 1)):
+        p = _lib.tl_problem()
+        p.F, p.W, p.S, p.P, p.B, p.allow_backward, p.aggregate = 3, 3, S, Pn, 1, 1, agg
+        for name in ("x_in", "y_in", "z", "cx", "cy", "c", "t", "mu", "mask", "cond_flags"):
+            setattr(p, name, 8)
+        seeds = _lib.tl_seeds(g_moments=8)
+        grads = _lib.tl_grads(g_c=8, g_t=8, g_mu=8, g_z=8, g_cx=8, g_cy=8)
+        fwd = _lib.tl_rays(x=8, y=8, cx=8, cy=8, ok=8)                  # every member the call reads, but the moments
+        assert dll.tl_trace_bwd_from_outputs(C.byref(p), seeds, fwd, grads, one, 1 << 30, None) == EINVAL, (S, Pn, agg)
+        msg = dll.tl_last_error()
+        assert b"cond_flags" in msg and b"moments" in msg, msg
+
+
+ROUTE_VARIANTS = {                 # surf_kind / kappa / poly, asph_hits, asph_hit_slots (addresses are never followed)
+    "spherical": (None, None, 0),
+    "aspheric, hits stored": (8, 8, 4),
+    "aspheric, asph_hits NULL": (8, None, 4),
+    "aspheric, asph_hit_slots 0": (8, 8, 0),
+}
+
+
+def test_backward_route_table_is_the_header_s():
+    """tl_bwd_route over S = 1..32 x P in {0, 1, 255, 256} x aggregate x the aspheric variants, against the words of
+    include/tl_trace.h (tl_bwd_route, tl_trace_bwd_from_outputs), written out here independently of the library's predicate:
+    P = 0 the empty shard; 3..20 rows, P >= 256 and aspheric rows only with stored hits the unrolled walk-back; otherwise the
+    penalty term goes to tl_trace_bwd as a whole and everything else to the rolled walk-back.  No device is touched."""
+    import ctypes as C
+    from torchoptics_amd import _lib
+    dll = _lib.lib()
+    names = {_lib.ROUTE_CHECKPOINT: "TL_ROUTE_CHECKPOINT", _lib.ROUTE_WALK_ROLLED: "TL_ROUTE_WALK_ROLLED",
+             _lib.ROUTE_WALK_UNROLLED: "TL_ROUTE_WALK_UNROLLED", _lib.ROUTE_EMPTY: "TL_ROUTE_EMPTY"}
+    hdr = open(os.path.join(ROOT, "include", "tl_trace.h")).read()
+    for value, name in names.items():
+        assert re.search(r"\b%s = %d\b" % (name, value), hdr), name
+    seen = set()
+    for S in range(1, 33):
+        for Pn in (0, 1, 255, 256):
+            for agg in (0, 1):
+                for variant, (kind, hits, slots) in ROUTE_VARIANTS.items():
+                    p = _lib.tl_problem()
+                    p.F, p.W, p.S, p.P, p.aggregate = 3, 3, S, Pn, agg
+                    p.surf_kind = p.kappa = p.poly = kind
+                    p.asph_hits, p.asph_hit_slots = hits, slots
+                    if Pn == 0:
+                        want = _lib.ROUTE_EMPTY
+                    elif 3 <= S <= 20 and Pn >= 256 and variant in ("spherical", "aspheric, hits stored"):
+                        want = _lib.ROUTE_WALK_UNROLLED
+                    elif agg:
+                        want = _lib.ROUTE_CHECKPOINT
+                    else:
+                        want = _lib.ROUTE_WALK_ROLLED
+                    got = dll.tl_bwd_route(C.byref(p))
+                    assert got == want, (S, Pn, agg, variant, names.get(got, got), names[want])
+                    seen.add(got)
+    assert seen == set(names)
+    # not a problem at all: TL_EINVAL and a message, as everywhere
+    assert dll.tl_bwd_route(None) == -1
+    for S, Pn in ((0, 256), (33, 256), (7, -1)):
+        p = _lib.tl_problem()
+        p.F, p.W, p.S, p.P = 3, 3, S, Pn
+        assert dll.tl_bwd_route(C.byref(p)) == -1, (S, Pn)
+        assert b"tl_bwd_route" in dll.tl_last_error()
 
 
 # B, F, W, S, P, asph -> tl_workspace_bytes, tl_workspace_bytes_f64 (no TL_* variable set): the sizes callers have been told

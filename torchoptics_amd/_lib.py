@@ -19,6 +19,8 @@ TL_MAX_POLY = 4
 TL_MAX_HIT_SLOTS = 8
 TL_MAX_AIM_ITER = 16
 MODE_STRICT, MODE_FAST = 0, 1
+# tl_bwd_route: what tl_trace_bwd_from_outputs enqueues for a problem
+ROUTE_CHECKPOINT, ROUTE_WALK_ROLLED, ROUTE_WALK_UNROLLED, ROUTE_EMPTY = 0, 1, 2, 3
 
 
 class tl_problem(C.Structure):
@@ -111,6 +113,7 @@ _SIGNATURES = {
     "tl_trace_fwd": (C.c_int, [_P, _R] + _WS),
     "tl_trace_bwd": (C.c_int, [_P, _S, _G] + _WS),
     "tl_trace_bwd_from_outputs": (C.c_int, [_P, _S, _R, _G] + _WS),
+    "tl_bwd_route": (C.c_int, [_P]),
     "tl_spot_moments": (C.c_int, [C.c_int32] * 4 + [_VP] * 3 + [C.c_int64] * 3 + [_VP, _VP, C.c_size_t, _VP]),
     "tl_spot_rms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP, _VP, _VP]),
     "tl_unsup_loss": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP, C.c_double, C.c_float, _VP, _VP, _VP, _VP, _VP]),

@@ -789,6 +789,13 @@ size_t tl_problem_size(void) { return sizeof(tl_problem); }
 
 size_t tl_workspace_bytes(const tl_problem *p) { return no_layout(p) ? 0 : layout(p).total; }
 
+int tl_bwd_route(const tl_problem *p)
+{
+    if (!p) return fail(TL_EINVAL, "tl_problem is NULL");
+    if (p->S < 1 || p->S > TL_MAX_SURFACES || p->P < 0) return fail(TL_EINVAL, "tl_bwd_route: S must be 1..TL_MAX_SURFACES and P >= 0");
+    return tl_route(*p);
+}
+
 int tl_trace_fwd(const tl_problem *p, const tl_rays *out, void *workspace, size_t workspace_bytes, void *stream)
 {
     int rc = check_problem(p);
@@ -893,10 +900,14 @@ int tl_trace_bwd_from_outputs(const tl_problem *p, const tl_seeds *g, const tl_r
         return fail(TL_EINVAL, "the forward outputs x, y, cx, cy, ok are required");
     if (!p->allow_backward)
         return fail(TL_EINVAL, "tl_trace_bwd_from_outputs: allow_backward_rays only");
-    const bool hits_ok = p->surf_kind == nullptr || (p->asph_hits != nullptr && p->asph_hit_slots > 0);
+    // the walk-back leaves the rays flagged 2 to the checkpoint kernel, which takes them only when the moments count them:
+    // without the moments their gradient would be dropped
+    if (p->cond_flags && !f.moments)
+        return fail(TL_EINVAL, "tl_trace_bwd_from_outputs: tl_problem.cond_flags needs the forward's moments (tl_rays.moments is NULL)");
     // the penalty term is walked back by the unrolled kernels only (3..20 rows, aspheric rows with stored hits);
-    // other lenses take the checkpoint kernel for every ray -- and an empty shard its memsets
-    if ((p->aggregate && !(tl_walk_unrolled(p->S, p->P) && hits_ok)) || p->P == 0)
+    // other lenses take the checkpoint kernel for every ray -- and an empty shard its memsets (tl_route, tl_common.h)
+    const int route = tl_route(*p);
+    if (route == TL_ROUTE_CHECKPOINT || route == TL_ROUTE_EMPTY)
         return tl_trace_bwd(p, g, out, workspace, workspace_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
     if ((rc = use_device(p->device))) return rc;

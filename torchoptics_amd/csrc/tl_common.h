@@ -31,6 +31,16 @@ __host__ __device__ static inline size_t tl_scanmap_bytes(int rows, int64_t nchu
 
 static inline bool tl_walk_unrolled(int S, int P) { return S >= TL_INVU_MIN && S <= TL_INVU_MAX && P >= 256; }
 
+// The host's routing of tl_trace_bwd_from_outputs (tl_trace.h: tl_bwd_route), written once: the C entry point, launch_bwd_inv
+// and tl_bwd_route all read it.  Aspheric rows are walked back by the unrolled kernels only from their stored hit points.
+static inline int tl_route(const tl_problem &p)
+{
+    if (p.P == 0) return TL_ROUTE_EMPTY;
+    const bool hits_ok = p.surf_kind == nullptr || (p.asph_hits != nullptr && p.asph_hit_slots > 0);
+    if (tl_walk_unrolled(p.S, p.P) && hits_ok) return TL_ROUTE_WALK_UNROLLED;
+    return p.aggregate ? TL_ROUTE_CHECKPOINT : TL_ROUTE_WALK_ROLLED;
+}
+
 // What makes a checkpoint launch (trace_bwd_kernel) the fallback of a walk-back launch in front of it: the forward's moments
 // and the walk-back's poison word / token decide on the device whether it runs; dead_ok = the forward's ok bytes when it also
 // takes single rays (the penalty term's dead rays, flagged ill-conditioned rays).  All zero: an ordinary backward.

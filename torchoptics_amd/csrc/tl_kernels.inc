@@ -2478,7 +2478,7 @@ static int launch_bwd_inv(const tl_problem &p, const tl_seeds &g, const tl_rays 
     case NS_: if (asph && pen && gstk) TL_INVU_V(NS_, true, kPenRay); else if (asph && pen) TL_INVU_V(NS_, true, kPenUniform); \
               else if (asph) TL_INVU_V(NS_, true, kPenNone); else if (pen && gstk) TL_INVU_V(NS_, false, kPenRay); \
               else if (pen) TL_INVU_V(NS_, false, kPenUniform); else TL_INVU_V(NS_, false, kPenNone); break
-    if (tl_walk_unrolled(p.S, p.P) && !rolled_only && (!asph || hits)) {     // (no skip there for waves past the end of a small pupil)
+    if (tl_route(p) == TL_ROUTE_WALK_UNROLLED && !rolled_only) {              // (no skip there for waves past the end of a small pupil)
         switch (p.S) {
 #ifdef TL_INVU_DEV      // development builds: the row counts of the bench workloads only (compile time)
             TL_INVU(7); TL_INVU(11); TL_INVU(20);

@@ -192,6 +192,7 @@ Tensor to_shape(const Tensor &g, at::IntArrayRef full, at::IntArrayRef orig)
 }
 
 thread_local bool g_last_use_inv = false;
+thread_local int g_last_route = TL_ROUTE_CHECKPOINT;     // tl_bwd_route of the last trace's backward (ops.backward_route)
 
 // flag bits of the int argument of TraceFn (kept in one int: every extra non-tensor argument of a custom function is
 // one more slot in the gradient list)
@@ -277,6 +278,8 @@ public:
         Tensor cond;
         if (use_inv && need_any) cond = at::empty({B, F, W, P}, fopt.dtype(at::kByte));
         tl_problem prob = make_problem(n, allow_back, (int)mode, aggregate, hits, moments_x, want_opd, cond);
+        // what the backward will enqueue: tl_trace_bwd_from_outputs' own host decision, or tl_trace_bwd by the choice above
+        g_last_route = use_inv ? tl_bwd_route(&prob) : TL_ROUTE_CHECKPOINT;
         const size_t nbytes = tl_workspace_bytes(&prob);
         Tensor ws = workspace(nbytes, dev, (void *)st);
         Tensor fp[4], bp[2], opd, stacks;
@@ -622,6 +625,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("unsup_loss", &unsup_loss);
     m.def("workspace_of", &workspace_of);
     m.def("last_use_inv", [] { return g_last_use_inv; });
+    m.def("last_route", [] { return g_last_route; });
     m.def("enable_timing", &enable_timing);
     m.def("timing_ms", &timing_ms);
     m.def("timing_counts", &timing_counts);

@@ -71,12 +71,35 @@ def host_chain() -> str:
 
 
 def used_walk_back(t: torch.Tensor) -> bool:
-    """Whether the backward of the trace that produced `t` (the x returned by trace_skew) is the walk-back from the
-    forward's outputs (tl_trace_bwd_from_outputs) rather than the checkpoint algorithm."""
-    return bool(getattr(t, "_tl_use_inv"))
+    """Whether the backward of the trace that produced `t` (the x returned by trace_skew) will CALL
+    tl_trace_bwd_from_outputs rather than tl_trace_bwd: the host chain's choice of entry point (backward algorithm
+    'inverse', allow_backward_rays, no OPD gradient, no per-ray input gradients, fp32).  It does not say that a walk-back
+    kernel runs: tl_trace_bwd_from_outputs hands the penalty term of some lenses to tl_trace_bwd as a whole --
+    `backward_route(t)` names the kernels.  A batch traced in lens chunks reports its chunks' (common) answer; a tensor
+    that no trace produced: False."""
+    return bool(getattr(t, "_tl_use_inv", False))
+
+
+BACKWARD_ROUTES = {_lib.ROUTE_CHECKPOINT: "checkpoint", _lib.ROUTE_WALK_ROLLED: "walk_rolled",
+                   _lib.ROUTE_WALK_UNROLLED: "walk_unrolled", _lib.ROUTE_EMPTY: "empty"}
+
+
+def backward_route(t: torch.Tensor) -> str:
+    """Which kernels the backward of the trace that produced `t` (the x returned by trace_skew) enqueues: 'checkpoint'
+    (trace_bwd_kernel for every ray: tl_trace_bwd), 'walk_rolled' (trace_bwd_inv_kernel), 'walk_unrolled'
+    (trace_bwd_inv_unrolled_kernel) or 'empty' (no rays) -- tl_bwd_route of the trace's own tl_problem (include/tl_trace.h),
+    the decision tl_trace_bwd_from_outputs takes on the host.  A trace whose backward calls tl_trace_bwd by the host
+    chain's own choice (`used_walk_back(t)` False: 'checkpoint' algorithm, OPD gradient, per-ray input gradients, fp64)
+    reports 'checkpoint'.  Either host chain; a batch traced in lens chunks reports the route of its chunks (the last,
+    shorter chunk has the same S, P, aggregate and hit slots: the same route)."""
+    route = getattr(t, "_tl_route", None)
+    if route is None:
+        raise ValueError("backward_route: not the x of a trace_skew call")
+    return BACKWARD_ROUTES[route]
 
 
 _last_use_inv = False
+_last_route = _lib.ROUTE_CHECKPOINT
 
 
 def set_backward_algorithm(name: str) -> None:
@@ -341,8 +364,10 @@ class TraceFunction(torch.autograd.Function):
         moments = torch.empty((B * F, TL_NMOM), dtype=torch.float64, device=dev)
         out = _lib.rays(x=fp[0], y=fp[1], cx=fp[2], cy=fp[3], ok=bp[0], back=bp[1], opd=opd, stacks=stacks, moments=moments)
         _call(prec.fwd, dev, C.byref(prob), out, ws, ws.numel(), timed="fwd" if prec.timed else None)
-        global _last_use_inv
+        global _last_use_inv, _last_route
         _last_use_inv = use_inv
+        # (tl_bwd_route reads the problem's sizes and hit-slot members only: the same answer in backward)
+        _last_route = _lib.lib().tl_bwd_route(C.byref(prob)) if use_inv else _lib.ROUTE_CHECKPOINT
         fwd_out = (fp[0], fp[1], fp[2], fp[3], bp[0], moments) if use_inv else (None,) * 6
         ctx.save_for_backward(x_e, y_e, z, cx, cy, c, t, mu, mask_u8, kappa, poly, kind_u8, *fwd_out,
                               n_index if want_opd else None, hits, cond)
@@ -1275,7 +1300,8 @@ def _dist_initialized() -> bool:
 def trace_cpp(ext, x, y, z, cx, cy, c, t, mu, mask, kappa, poly, kind, n_index, allow_back, mode, want_rays, want_opd,
               aggregate, want_stacks, moments_x):
     """The trace through the C++ host extension: the arguments exactly as trace_skew received them (their broadcast
-    shapes are normalised in C++).  Returns (the nine outputs of TraceFunction, use_inv)."""
+    shapes are normalised in C++).  Returns (the nine outputs of TraceFunction, use_inv, the tl_bwd_route value of the
+    backward: used_walk_back / backward_route)."""
     flags = ((ext.ALLOW_BACK if allow_back else 0) | (ext.WANT_RAYS if want_rays else 0) | (ext.WANT_OPD if want_opd else 0)
              | (ext.AGGREGATE if aggregate else 0) | (ext.WANT_STACKS if want_stacks else 0)
              | (ext.MOMENTS_X if moments_x else 0) | (ext.INVERSE if _bwd_algo == "inverse" else 0)
@@ -1284,7 +1310,7 @@ def trace_cpp(ext, x, y, z, cx, cy, c, t, mu, mask, kappa, poly, kind, n_index, 
              # (nor with the penalty term: those callers take the whole loss_dict from the moments, unsup_loss below)
              | (ext.FUSE_RMS if (want_rays and not aggregate and hasattr(ext, "FUSE_RMS") and not _dist_initialized()) else 0))
     out = ext.trace(x, y, z, cx, cy, c, t, mu, mask, kappa, poly, kind, n_index, flags, _MODES[mode], ASPH_HIT_SLOTS)
-    return out, ext.last_use_inv()
+    return out, ext.last_use_inv(), ext.last_route()
 
 
 def pupil_position(c, t, n, mode=None):

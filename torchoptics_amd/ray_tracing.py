@@ -218,6 +218,28 @@ def _rows(a: torch.Tensor, n_lens: int, tail: tuple) -> torch.Tensor:
     return _dense(a.reshape(1, *tail).expand(n_lens, *tail))
 
 
+def _check_extension_shapes(B, S, W, kappa, poly, n_index):
+    """The shapes trace_skew takes for kappa, poly and n_index (its docstring), refused here, at the call, for both host
+    chains: a shape that merely reshapes to [-1,S] would trace, and then fail inside backward when its gradient is summed
+    back."""
+    for name, a, tail in (("kappa", kappa, (S,)), ("poly", poly, (S, 4))):
+        if a is None:
+            continue
+        if not torch.is_tensor(a):
+            raise TypeError(f"{name} must be a tensor")
+        shape = tuple(a.shape)
+        if shape != tail and shape not in ((1, *tail), (B, *tail)):
+            forms = ", ".join(str(list(f)) for f in (tail, (1, *tail), (B, *tail)))
+            raise ValueError(f"{name} must have one of the shapes {forms} (S = {S} rows, B = {B} lenses), got {list(shape)}")
+    if n_index is not None and W is not None:      # (W None: x, y or mu malformed, refused by name further on)
+        if not torch.is_tensor(n_index):
+            raise TypeError("n_index must be a tensor")
+        shape = tuple(n_index.shape)
+        if len(shape) != 5 or shape[0] not in (1, B) or shape[1:] != (1, 1, W, S + 1):
+            raise ValueError(f"n_index must have the shape [1|B,1,1,W,S+1] (B = {B} lenses, W = {W} wavelengths, S = {S} rows), "
+                             f"got {list(shape)}")
+
+
 def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_rays=True, mode=None,
                want_rays=True, kappa=None, poly=None, surf_kind=None, n_index=None, want_opd=False, x_moments=False):
     """Trace rays from the entrance pupil to the image plane through S surface rows.
@@ -237,11 +259,14 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
                   'sum': the same 7th value WITHOUT the per-surface tensors -- only the fused sums that
                   `penalty_sum` / `unsupervised_loss` read (the lists are 12 S bytes of HBM writes per ray);
       mode        'strict' | 'fast' arithmetic (default ops.get_default_mode());
-      kappa, poly aspheric rows: conic constants [S] and even polynomial terms [S,4] (a4..a10);
-                  `surf_kind` [S] (bool/int) marks the rows traced by Newton iteration -- default: the
-                  rows where kappa or poly is non-zero.  Differentiable w.r.t. kappa and poly too;
-      n_index, want_opd   refractive indices [1,1,1,W,S+1] (entry 0 = object space) and a seventh
-                  return value: the optical path length per ray, differentiable w.r.t. every lens and launch
+      kappa, poly aspheric rows: conic constants and even polynomial terms (a4..a10), one set for all lenses or one per
+                  lens of a batch of B.  Accepted shapes, on both host chains -- kappa: [S], [1,S], [B,S]; poly: [S,4],
+                  [1,S,4], [B,S,4]; anything else is a ValueError naming the argument, at this call.
+                  `surf_kind` [S] or [1|B,S] (bool/int) marks the rows traced by Newton iteration -- default: the
+                  rows where kappa or poly is non-zero.  Differentiable w.r.t. kappa and poly too: the gradient has
+                  the argument's shape, a shared set receives the sum over the lenses;
+      n_index, want_opd   refractive indices [1|B,1,1,W,S+1] (entry 0 = object space; no other shape: ValueError) and a
+                  seventh return value: the optical path length per ray, differentiable w.r.t. every lens and launch
                   parameter and w.r.t. n_index (its backward runs the checkpoint kernel);
       x_moments   also fuse the x-moments of the spot into the trace (for `compute_rms_spot_xy`; compute_rms2d reads
                   y only, ray_tracing_lite.py:684-701, so by default the kernel does not spend time on them);
@@ -258,6 +283,9 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
             return _trace_skew_in_lens_chunks(max(1, _MAX_GRID_ROWS // rows_per_lens), B, x, y, z, cx, cy, c, t, mu, mask,
                                               aggregate, allow_backward_rays, mode, want_rays, kappa, poly, surf_kind,
                                               n_index, want_opd, x_moments)
+    if kappa is not None or poly is not None or want_opd:
+        W = max(x.shape[3], y.shape[3], mu.shape[3]) if (x.dim() == 4 and y.dim() == 4 and mu.dim() == 5) else None
+        _check_extension_shapes(B, c.shape[-1], W, kappa, poly, n_index if want_opd else None)
     # double precision (RayTracer(double_precision=True)): the generic fp64 kernels, through the Python host chain below
     f64 = any(torch.is_tensor(a) and a.dtype == torch.float64 for a in (x, y, z, cy, c, t, mu))
     if f64 and (aggregate or want_opd):
@@ -276,11 +304,11 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
     ext = None if f64 else ops._ext()
     if ext is not None:
         # the C++ host chain: shapes are normalised, outputs allocated and the autograd node built in csrc/tl_torch.cpp
-        out, use_inv = ops.trace_cpp(ext, x, y, z, cx, cy, c, t, mu, mask, kap, pol, kind, n_index if want_opd else None,
-                                     bool(allow_backward_rays), mode or ops.get_default_mode(), want_rays, bool(want_opd),
-                                     bool(aggregate), bool(aggregate is True and want_rays), bool(x_moments))
+        out, use_inv, route = ops.trace_cpp(ext, x, y, z, cx, cy, c, t, mu, mask, kap, pol, kind, n_index if want_opd else None,
+                                            bool(allow_backward_rays), mode or ops.get_default_mode(), want_rays, bool(want_opd),
+                                            bool(aggregate), bool(aggregate is True and want_rays), bool(x_moments))
         n_pw = max(x.shape[2], y.shape[2]) * max(x.shape[3], y.shape[3], mu.shape[3])
-        return _trace_result(out, use_inv, want_rays, want_opd, aggregate, x_moments, n_pw, B)
+        return _trace_result(out, use_inv, route, want_rays, want_opd, aggregate, x_moments, n_pw, B)
     cast = _as_f64 if f64 else _as_f32          # (the normalisation below is dtype-blind)
     x, y, z, cx, cy = (cast(a, n) for a, n in ((x, 'x'), (y, 'y'), (z, 'z'), (cx, 'cx'), (cy, 'cy')))
     c, t, mu = cast(c, 'c'), cast(t, 't'), cast(mu, 'mu')
@@ -321,11 +349,11 @@ def trace_skew(x, y, z, cx, cy, c, t, mu, mask, aggregate=False, allow_backward_
         # the fp64 kernels: 'strict' arithmetic only, no walk-back, and the x-moments always filled (nothing to ask for)
         out = ops.TraceFunction.apply(x_e, y_e, zv, cx2, cy2, c2, t2, mu3, kap, pol, mask_u8, kind_u8, None,
                                       bool(allow_backward_rays), "strict", want_rays, False, False, False, False)
-        return _trace_result(out, False, want_rays, False, False, True, P * W, B)
+        return _trace_result(out, False, ops._last_route, want_rays, False, False, True, P * W, B)
     out = ops.TraceFunction.apply(x_e, y_e, zv, cx2, cy2, c2, t2, mu3, kap, pol, mask_u8, kind_u8, nidx,
                                   bool(allow_backward_rays), mode or ops.get_default_mode(), want_rays, bool(want_opd),
                                   bool(aggregate), bool(aggregate is True and want_rays), bool(x_moments))
-    return _trace_result(out, ops._last_use_inv, want_rays, want_opd, aggregate, x_moments, P * W, B)
+    return _trace_result(out, ops._last_use_inv, ops._last_route, want_rays, want_opd, aggregate, x_moments, P * W, B)
 
 
 class _SpotTag(NamedTuple):
@@ -377,7 +405,7 @@ def _moments_f64(x, y, ray_ok):
     return torch.stack(cols, dim=-1)[0]
 
 
-def _trace_result(out, use_inv, want_rays, want_opd, aggregate, x_moments, n_pw, B):
+def _trace_result(out, use_inv, route, want_rays, want_opd, aggregate, x_moments, n_pw, B):
     """The tuple trace_skew returns, from the nine outputs of the trace function."""
     xo, yo, cxo, cyo, ok, back, moments, opd, stk = out[:9]
     rms = out[9] if len(out) > 9 and out[9].numel() > 0 else None      # C++ host chain: the spot metric, fused into the trace node
@@ -385,7 +413,8 @@ def _trace_result(out, use_inv, want_rays, want_opd, aggregate, x_moments, n_pw,
         # remember which moments belong to these rays (checked by identity + version in compute_rms2d):
         # [B*F, TL_NMOM], lens-major; and their spot metric when the trace node computed it already
         yo._tl_spot = _SpotTag(moments, ok, yo._version, n_pw, bool(x_moments), rms)
-        xo._tl_use_inv = bool(use_inv)                 # which backward algorithm this trace will take (ops.used_walk_back)
+        xo._tl_use_inv = bool(use_inv)                 # which backward entry point this trace will call (ops.used_walk_back)
+        xo._tl_route = route                           # ... and which kernels that enqueues (ops.backward_route)
         res = (xo, yo, cxo, cyo, ok, back)
         if want_opd:
             res += (opd,)
@@ -422,6 +451,8 @@ def _trace_skew_in_lens_chunks(nb, B, x, y, z, cx, cy, c, t, mu, mask, aggregate
     res = [torch.cat([o[i] for o in outs], dim=0) for i in range(n_ray)]
     moments = torch.cat([o[1]._tl_spot.moments for o in outs], dim=0)
     res[1]._tl_spot = _SpotTag(moments, res[4], res[1]._version, outs[0][1]._tl_spot.n_pw, bool(x_moments))
+    # every chunk has the same S, P, options and hit slots, so the same backward (ops.used_walk_back, ops.backward_route)
+    res[0]._tl_use_inv, res[0]._tl_route = outs[0][0]._tl_use_inv, outs[0][0]._tl_route
     if aggregate:
         stk = None
         if aggregate is True:
