@@ -9,7 +9,7 @@
  * distortion map and multiplies the relative illumination in.  tl_focus_* sums the through-focus
  * moments of a traced fan (best focus, tangential / sagittal foci, axial colour), tl_enclosed_* its
  * encircled / ensquared energy under a smooth edge, tl_zfit_* fits Zernike wavefront coefficients
- * to its transverse ray errors.
+ * to its transverse ray errors, tl_mtf_* sums its geometric OTF at given spatial frequencies.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless marked "host";
@@ -811,6 +811,47 @@ int tl_zfit_solve(int32_t device, int64_t rows, int order, const double *moments
 int tl_zfit_seed(int32_t device, int64_t F, int64_t P, int64_t W, int order, const float *x, const float *y, const uint8_t *ok,
                  int64_t s_f, int64_t s_p, int64_t s_w, const float *px, const float *py, int64_t ps_f, int64_t ps_p, int64_t ps_w,
                  const double *coef /* [F,W,J + 1] */, float *gx, float *gy, void *stream);
+
+/*
+ * Geometric OTF of a traced fan as Fourier sums over the spot (extension; metrics.otf_sums / metrics.geometric_mtf stand on them):
+ * the characteristic function of the spot at J spatial-frequency vectors, exact for the traced rays at any frequency -- no
+ * histogram, no bin width in the result.
+ *
+ * x, y (float) and ok (bytes) are [F, P, W] tensors that share ONE stride triple s_f, s_p, s_w (elements); a row is one (f, w).
+ * A ray is LIVE iff ok != 0; a dead ray adds exactly 0 to every sum and gets exactly 0 gradient whatever its coordinates hold
+ * (NaN, inf, 1e30): it is excluded by a select, not by a product with 0; live rays must be finite.  origin[f, w, 0..1] (device
+ * doubles, contiguous) is a constant of the calculation: the modulus of the OTF does not depend on it, only the phase does, so it
+ * gets no gradient; it exists for conditioning.  nu_x, nu_y are HOST arrays of J <= 16 doubles, cycles per length unit of x,
+ * finite, of any sign, zero allowed: they travel to the kernels as a by-value argument, nothing is uploaded and no call
+ * synchronises.  Per row, over the live rays, every operation in fp64 from the fp32 inputs, uncontracted:
+ *   dx = (double)x - o_x,  dy = (double)y - o_y,  u = nu_x dx + nu_y dy  (two products, one sum: cycles),  r = u - rint(u)  (exact)
+ *   sums[f, w, j, 0] = C_j = sum cos(2 pi r),   sums[f, w, j, 1] = S_j = sum sin(2 pi r)
+ * through the device library's double-precision sincospi on 2 r (the factor 2 is exact, pi never multiplies in).  OTF_j = (C_j -
+ * i S_j) / n, MTF_j = sqrt(C_j^2 + S_j^2) / n.  nu = 0 gives the term (1, 0) exactly: C = n, S = 0 without a rounding.  One partial
+ * per block goes to the workspace and a second kernel adds a row's partials in a fixed order: no atomics, the same bits on every
+ * run, and a column has the bits it has when it is computed alone.  Layout handling, launch plan and limits are
+ * tl_enclosed_sums' (16-byte loads where s_p = 1 and the row's bases are aligned, one ray at a time elsewhere; F W < 2^31 rows in
+ * launches of 65535; P < 2^31).
+ *
+ * tl_mtf_seed: for the seeds g_sums[f, w, j, 0..1] = (gC_j, gS_j), with phi = 2 pi r,  dC_j / dx = -2 pi nu_xj sin phi,  dS_j / dx =
+ * 2 pi nu_xj cos phi:   q_j = gS_j cos phi_j - gC_j sin phi_j,   gx = 2 pi sum_j nu_xj q_j,   gy = 2 pi sum_j nu_yj q_j,
+ * the sums over j in order in fp64, times 2 pi, rounded once to float and written with the inputs' strides into gx, gy (either
+ * may be NULL, not both); dead rays get zeros.  It reduces nothing and leaves the workspace untouched; the workspace is checked
+ * as for tl_mtf_sums so that one allocation serves both calls.
+ *
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, F, P or W below 1, F W or P at
+ * or above 2^31, J outside 1..16, a frequency not finite, both outputs of the seed NULL.  TL_EWORKSPACE: workspace NULL or below
+ * tl_mtf_workspace_bytes(F, P, W, J) (0 for arguments that are refused).
+ */
+size_t tl_mtf_workspace_bytes(int64_t F, int64_t P, int64_t W, int J);
+int tl_mtf_sums(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const uint8_t *ok, int64_t s_f,
+                int64_t s_p, int64_t s_w, const double *origin /* [F,W,2] */, const double *nu_x /* host, J */,
+                const double *nu_y /* host, J */, int J, double *sums /* [F,W,J,2] */, void *workspace, size_t workspace_bytes,
+                void *stream);
+int tl_mtf_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const uint8_t *ok, int64_t s_f,
+                int64_t s_p, int64_t s_w, const double *origin /* [F,W,2] */, const double *nu_x /* host, J */,
+                const double *nu_y /* host, J */, int J, const double *g_sums /* [F,W,J,2] */, float *gx, float *gy,
+                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

@@ -188,6 +188,12 @@ _SIGNATURES = {
     # ... | px, py | ps_f, ps_p, ps_w | coef | gx, gy | stream
     "tl_zfit_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [C.c_int] + [_VP] * 3 + [C.c_int64] * 3 + [_VP] * 2
                      + [C.c_int64] * 3 + [_VP] + [_VP] * 2 + [_VP]),
+    "tl_mtf_workspace_bytes": (C.c_size_t, [C.c_int64] * 3 + [C.c_int]),
+    # device, F, P, W | x, y, ok | s_f, s_p, s_w | origin | nu_x, nu_y (host doubles), J | sums | workspace, bytes | stream
+    "tl_mtf_sums": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int] + [_VP] + _WS),
+    # ... | origin | nu_x, nu_y, J | g_sums | gx, gy | workspace, bytes | stream
+    "tl_mtf_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int] + [_VP]
+                    + [_VP] * 2 + _WS),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -47,11 +47,14 @@ UNITS = {
     "tl_focus.hip": [],        # the through-focus spot moments of a traced fan (fp64 sums of x, y and the slopes) and their seeds
     "tl_enclosed.hip": [],     # the encircled / ensquared energy of a traced fan (fp64 sums under a smooth edge) and its seeds
     "tl_zfit.hip": [],         # the Zernike wavefront fit of a traced fan from its ray errors (fp64 moments, solve, seeds)
+    "tl_mtf.hip": [],          # the geometric OTF of a traced fan (fp64 Fourier sums over the spot at given frequencies) and its seeds
 }
 # -mllvm options of COMMON a unit is compiled WITHOUT.  tl_zfit.hip: under the iterative-ilp scheduler this compiler's greedy
 # register allocator crashes (a segmentation fault in VirtRegAuxInfo::isRematerializable) on the moment kernels with 29 and more
 # fp64 accumulators; the default scheduler compiles them without scratch (profiles/zfit_kernel_resources.txt).
-WITHOUT = {"tl_zfit.hip": ("-amdgpu-sched-strategy=iterative-ilp",)}
+# tl_mtf.hip: the same crash of the compiler under iterative-ilp, on mtf_sums_kernel (8 to 32 fp64 accumulators around an inlined
+# sincospi); the default scheduler gives 62 / 78 / 110 VGPRs and no scratch (profiles/mtf_kernel_resources.txt).
+WITHOUT = {"tl_zfit.hip": ("-amdgpu-sched-strategy=iterative-ilp",), "tl_mtf.hip": ("-amdgpu-sched-strategy=iterative-ilp",)}
 DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
 
 

@@ -9,6 +9,7 @@ definitions in tests/metrics_ref.py (cases and gates: tests/metrics_cases.py, te
 """
 from __future__ import annotations
 
+import math
 from typing import NamedTuple
 
 import torch
@@ -711,3 +712,188 @@ def zernike_fit(x, y, ray_ok, px, py, max_order=4, scale=None, fused=None):
     out = ZernikeFit(n=n.detach(), valid=valid, coeffs=coeffs, rms=_root_of_variance(sq[..., 2:].sum(dim=-1)),
                      rms_focus=_root_of_variance(sq[..., 3:].sum(dim=-1)), residual=_root_of_variance(q / n.detach().clamp(min=1.0)))
     return ZernikeFit(*(t if t.dtype == torch.bool else t.to(x.dtype) for t in out))
+
+
+# ---------------------------------------------------------------------------- geometric MTF: Fourier sums over the spot
+class GeometricMTF(NamedTuple):
+    """What geometric_mtf returns."""
+    n: torch.Tensor                 # weighted live rays, [B, F, W] less the pooled dimension
+    mtf: torch.Tensor               # modulus of the geometric OTF, [..., D, K]: directions x frequencies
+    centre: torch.Tensor            # the origin every row's phase was measured from, [B, F, W, 2]
+
+
+def _mtf_uses_kernels(fused, tensors, where):
+    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
+               and all(t.dtype == torch.float32 for t in tensors[:2]))
+    if fused and not applies:
+        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the MTF kernels run "
+                           "only on float32 tensors on one AMD GPU (there is no CPU fallback): use fused=False")
+    return applies if fused is None else bool(fused)
+
+
+def _mtf_vectors(frequencies, directions):
+    """(nu_x, nu_y, D, K): the D K frequency vectors as Python floats, direction-major, formed on the host in float64."""
+    freqs = tuple(float(f) for f in frequencies)
+    if not freqs or not all(0.0 <= f < float("inf") for f in freqs):
+        raise ValueError("frequencies must hold at least one finite float >= 0 (cycles per unit of x)")
+    directions = tuple(directions)
+    if not directions:
+        raise ValueError("directions must hold at least one of 'tangential', 'sagittal' or an angle in degrees")
+    nu_x, nu_y = [], []
+    for d in directions:
+        if isinstance(d, str):
+            if d not in ("tangential", "sagittal"):
+                raise ValueError(f"direction must be 'tangential', 'sagittal' or an angle in degrees from +x, got {d!r}")
+            cs = (0.0, 1.0) if d == "tangential" else (1.0, 0.0)
+        elif isinstance(d, (int, float)) and not isinstance(d, bool) and math.isfinite(d):
+            cs = (math.cos(math.radians(float(d))), math.sin(math.radians(float(d))))
+        else:
+            raise ValueError(f"direction must be 'tangential', 'sagittal' or a finite angle in degrees from +x, got {d!r}")
+        nu_x += [f * cs[0] for f in freqs]
+        nu_y += [f * cs[1] for f in freqs]
+    return tuple(nu_x), tuple(nu_y), len(directions), len(freqs)
+
+
+def _spot_sums(x, y, ray_ok, use):
+    """S [B, F, W, 3] = (n, sum x, sum y) over the live rays, float64, detached: tl_enclosed_centroid, or the same in torch."""
+    with torch.no_grad():
+        if use:
+            return ops.EnclosedEnergyFunction.apply(x, y, ray_ok, "row", (), (), "circle")[0]
+        live = ray_ok != 0
+        x64, y64 = (torch.where(live, t.to(torch.float64), t.new_zeros((), dtype=torch.float64)) for t in (x, y))
+        return torch.stack([live.to(torch.float64).sum(dim=2), x64.sum(dim=2), y64.sum(dim=2)], dim=-1)
+
+
+def _otf_sums_torch(x, y, ray_ok, origin, nu_x, nu_y):
+    """The definition of otf_sums in torch ops, in float64, on any device.  It holds the ray x J tensors the kernels never form."""
+    live = ray_ok != 0
+    zero = x.new_zeros((), dtype=torch.float64)
+    # a dead ray is the ray at 0 that is not counted: nothing of what it holds reaches a sum or a gradient
+    x, y = torch.where(live, x.to(torch.float64), zero), torch.where(live, y.to(torch.float64), zero)
+    o = origin.detach()
+    dx, dy = x - o[:, :, None, :, 0], y - o[:, :, None, :, 1]
+    nx, ny = const_tensor(nu_x, torch.float64, x.device), const_tensor(nu_y, torch.float64, x.device)   # cached: no upload per call
+    u = nx * dx[..., None] + ny * dy[..., None]             # cycles, [B, F, P, W, J]
+    r = u - torch.round(u)                                  # (round: to nearest even, rint's; its derivative is 0)
+    # sincospi(2 r) as the device library forms it: quarter turns taken off exactly, pi multiplies only into |t| <= 1 / 8, so
+    # that r = 0, 1 / 4, 1 / 2 give (1, 0), (0, 1), (-1, 0) without a rounding (two rays half a period apart cancel exactly)
+    k = torch.round(4.0 * r)
+    phi = (2.0 * math.pi) * (r - 0.25 * k)
+    c0, s0, k = torch.cos(phi), torch.sin(phi), torch.remainder(k, 4.0)
+    cos = torch.where(k == 0, c0, torch.where(k == 1, -s0, torch.where(k == 2, -c0, s0)))
+    sin = torch.where(k == 0, s0, torch.where(k == 1, c0, torch.where(k == 2, -s0, -c0)))
+    keep = live[..., None]
+    return torch.stack([torch.where(keep, cos, zero).sum(dim=2), torch.where(keep, sin, zero).sum(dim=2)], dim=-1)
+
+
+def otf_sums(x, y, ray_ok, origin, nu_x, nu_y, fused=None):
+    """The Fourier sums [B, F, W, J, 2] (float64) of a traced fan: per row (lens, field, wavelength) and frequency vector j
+
+        sums[row, j] = (C_j, S_j) = sum over the live rays of (cos, sin)(2 pi (nu_xj (x - o_x) + nu_yj (y - o_y))),
+
+    so that OTF_j = (C_j - i S_j) / n.  The low-level form of geometric_mtf, which states the definition; differentiable in x, y.
+    `origin`: broadcastable to [B, F, W, 2], a constant (no gradient); nu_x, nu_y: J Python floats each, cycles per unit of x,
+    finite, of any sign.  `fused` as for geometric_mtf; more than ops.MTF_MAX_J vectors go in several launches."""
+    nu_x, nu_y = tuple(float(v) for v in nu_x), tuple(float(v) for v in nu_y)
+    if not nu_x or len(nu_x) != len(nu_y) or not all(math.isfinite(v) for v in nu_x + nu_y):
+        raise ValueError("nu_x and nu_y must hold the same number (at least one) of finite floats")
+    use = _mtf_uses_kernels(fused, (x, y, ray_ok, origin), "otf_sums")
+    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "otf_sums")
+    B, F, _, W = x.shape
+    origin = origin.detach().to(torch.float64).expand(B, F, W, 2)
+    if not use:
+        return _otf_sums_torch(x, y, ray_ok, origin, nu_x, nu_y)
+    parts = [ops.MTFSumsFunction.apply(x, y, ray_ok, origin, nu_x[j:j + ops.MTF_MAX_J], nu_y[j:j + ops.MTF_MAX_J])
+             for j in range(0, len(nu_x), ops.MTF_MAX_J)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=3)
+
+
+def geometric_mtf(x, y, ray_ok, frequencies, directions=("tangential", "sagittal"), common=("wavelength",), centre="field",
+                  weights=None, fused=None):
+    """The geometric MTF of a traced fan at given spatial frequencies: the modulus of the characteristic function of the spot.
+
+    It is a sum over the traced rays, not the transform of a histogram: exact for those rays at any frequency, with no bin width
+    in the result, and smooth in the ray coordinates, so it needs no softening to be differentiable.
+
+    RAYS.  x, y, ray_ok: [B, F, P, W] as RayTracer.trace_rays returns them, broadcastable.  A ROW is one (lens, field,
+    wavelength); a ray is LIVE iff ray_ok != 0.  A dead ray adds exactly 0 to every sum and receives exactly 0 gradient, whatever
+    its coordinates hold (NaN, +-inf, 1e30): it is excluded by a select, not by a product with 0.  Live rays must be finite.
+    FREQUENCY VECTORS.  `frequencies`: K Python floats >= 0 in cycles per length unit of x (cycles / mm here); 0, repeats and
+    any order are allowed.  `directions`: D entries, each "tangential" -- modulation along +y, the meridian the tracer puts its
+    fields on, nu = (0, nu); "sagittal" -- nu = (nu, 0); or a float, degrees from +x, nu = (nu cos, nu sin), formed on the host in
+    float64.  The J = D K vectors (nu_x, nu_y)_j are host doubles.
+    DEFINITION.  With the row's origin o (float64, a constant), per row over the live rays, every operation in float64 from the
+    inputs and nothing contracted:
+        dx = x - o_x,   dy = y - o_y,   u = nu_x dx + nu_y dy  (two products, one sum: cycles),   r = u - rint(u)  (exact)
+        C_j = sum cos(2 pi r),   S_j = sum sin(2 pi r)         (the kernels: sincospi(2 r); pi never multiplies into the phase)
+        OTF_j = (C_j - i S_j) / n,   MTF_j = sqrt(C_j^2 + S_j^2) / n.
+    nu = 0 gives the term (1, 0) exactly: C = n, S = 0 and MTF = 1 with no rounding at all.  |OTF| does not depend on o, only
+    the phase does: o carries no gradient because that gradient vanishes identically, and exists for conditioning only -- at an
+    image height of 9 mm and 75 cycles / mm the raw phase is ~700 cycles, and float32 anywhere in u leaves nothing of it.
+    POOLING.  `common` is a subset of ("wavelength",): C, S and n are added over the wavelengths, each times a weight a_w >= 0
+    (`weights`: W Python floats, not all 0; default all 1), before the modulus and the division -- the polychromatic MTF, in which
+    lateral colour counts as blur.  It is an OTF only when the pooled rows share one origin, so with pooling the origin must not
+    depend on the wavelength.  "field" in `common` raises: rows at different image points have no common OTF.  Without pooling
+    the weights multiply each row's own C, S and n (a row of weight 0 is an empty one).  A set with sum a_w n_w = 0 gives MTF 0
+    with zero gradient; a modulus of exactly 0 gives zero gradient, by definition.
+    ORIGIN.  `centre`: "field" (default) -- the centroid of the field's live rays of all wavelengths; "row" -- the row's own
+    (only with common=()); or a tensor broadcastable to [B, F, W, 2] (with pooling: from [B, F, 1, 2]).  A named centre is
+    formed from S = (n, sum x, sum y), ROUNDED TO FLOAT32 and widened again, and detached: dx, dy are then exact differences in
+    float64, and the origin does not depend on the last bits of a summation order.  An empty row gets origin 0.
+    GRADIENTS, with phi = 2 pi r:  dC_j / dx_i = -2 pi nu_xj sin phi_ij,  dS_j / dx_i = 2 pi nu_xj cos phi_ij;  for seeds gC, gS
+    gx_i = 2 pi sum_j nu_xj q_ij,  gy_i = 2 pi sum_j nu_yj q_ij,  q_ij = gS_j cos phi_ij - gC_j sin phi_ij (the kernels: the sums
+    over j in float64, rounded once to float32 at the store).
+
+    Returns GeometricMTF(n, mtf, centre): mtf [B, F, W, D, K], or [B, F, D, K] when pooled, in the dtype of x; n the (pooled)
+    weighted live count, detached; centre the origin used, [B, F, W, 2].  `fused`: False -- the definition in float64 torch ops
+    on any device (it holds the ray x J tensors several times over); True -- the HIP kernels (ops.MTFSumsFunction: float32 x, y
+    on one AMD GPU, anything else raises; at most ops.MTF_MAX_J vectors per launch, longer lists go in several launches that each
+    read the rays again); None -- the kernels where they apply.  The finish (weights, pooling, modulus, division, the zero
+    rules) is plain float64 torch on tiny tensors either way.  No host synchronisation.  Designers multiply the curve by
+    diffraction_limit_mtf; this function does not."""
+    common = tuple(common)
+    if "field" in common:
+        raise ValueError("common must not hold 'field': rows at different image points have no common OTF")
+    if any(c != "wavelength" for c in common):
+        raise ValueError("common must be a subset of ('wavelength',)")
+    pooled = bool(common)
+    nu_x, nu_y, D, K = _mtf_vectors(frequencies, directions)
+    if isinstance(centre, str):
+        if centre not in ("row", "field"):
+            raise ValueError("centre must be 'row', 'field' or a tensor broadcastable to [B, F, W, 2]")
+        if centre == "row" and pooled:
+            raise ValueError("centre='row' gives every wavelength its own origin: pooled rows need one (centre='field' or a tensor)")
+    tensors = (x, y, ray_ok) + (() if isinstance(centre, str) else (centre,))
+    use = _mtf_uses_kernels(fused, tensors, "geometric_mtf")
+    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "geometric_mtf")
+    B, F, _, W = x.shape
+    a = (1.0,) * W if weights is None else tuple(float(v) for v in weights)
+    if len(a) != W or not all(0.0 <= v < float("inf") for v in a) or not any(v > 0.0 for v in a):
+        raise ValueError(f"weights must be {W} finite floats >= 0 (one per wavelength), not all 0")
+    S = _spot_sums(x, y, ray_ok, use)
+    if isinstance(centre, str):
+        origin = _enclosed_centre(S, centre).to(torch.float32).to(torch.float64)
+    else:
+        shape = (1,) * (4 - centre.dim()) + tuple(centre.shape)
+        if centre.dim() > 4 or (pooled and shape[2] != 1):
+            raise ValueError("with pooling the centre must not depend on the wavelength: broadcastable from [B, F, 1, 2]")
+        origin = centre.detach().to(torch.float64).expand(B, F, W, 2)
+    sums = otf_sums(x, y, ray_ok, origin, nu_x, nu_y, fused=use)
+    a = const_tensor(a, torch.float64, x.device)
+    sums, n = sums * a[:, None, None], S[..., 0] * a
+    if pooled:
+        sums, n = sums.sum(dim=2), n.sum(dim=2)
+    m2 = sums[..., 0] * sums[..., 0] + sums[..., 1] * sums[..., 1]
+    some, lit = m2 > 0, (n > 0)[..., None]
+    modulus = torch.where(some, torch.sqrt(torch.where(some, m2, torch.ones_like(m2))), torch.zeros_like(m2))
+    mtf = torch.where(lit, modulus / torch.where(lit, n[..., None], torch.ones_like(m2)), torch.zeros_like(m2))
+    return GeometricMTF(n.detach().to(x.dtype), mtf.reshape(*mtf.shape[:-1], D, K).to(x.dtype), origin.to(x.dtype))
+
+
+def diffraction_limit_mtf(frequencies, wavelength, f_number):
+    """The MTF of an aberration-free circular pupil, 2 / pi (acos s - s sqrt(1 - s^2)) with s = nu lambda N, 0 from the cutoff
+    1 / (lambda N) on.  frequencies: floats or a tensor, cycles per length unit; wavelength in that unit; returns a float64
+    tensor of the frequencies' shape.  Plain torch."""
+    nu = torch.as_tensor(frequencies, dtype=torch.float64)
+    s = (nu.abs() * wavelength * f_number).clamp(max=1.0)
+    return (2.0 / math.pi) * (torch.acos(s) - s * torch.sqrt(1.0 - s * s))

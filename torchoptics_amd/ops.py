@@ -173,7 +173,7 @@ def timing_ms() -> dict:
 
 def named_timing_ms() -> dict:
     """Mean GPU milliseconds per call, by entry point, of the timed calls outside the trace (tl_focus_moments, tl_focus_seed,
-    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed, tl_zfit_moments, tl_zfit_solve, tl_zfit_seed) since enable_timing();
+    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed, tl_zfit_moments, tl_zfit_solve, tl_zfit_seed, tl_mtf_sums, tl_mtf_seed) since enable_timing();
     synchronises the device."""
     torch.cuda.synchronize()
     return {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in (_timing_named or {}).items()}
@@ -688,6 +688,69 @@ class EnclosedEnergyFunction(torch.autograd.Function):
             if want_c:
                 g_centre = g_c.sum_to_size(centre[0]).to(centre[1])
         return (*outs, None, g_centre, None, None, None)
+
+
+MTF_MAX_J = 16             # frequency vectors per tl_mtf_sums / tl_mtf_seed call (the largest register bucket)
+
+
+class MTFSumsFunction(torch.autograd.Function):
+    """sums [B, F, W, J, 2] (float64) = (C_j, S_j), the sums of cos / sin(2 pi nu_j . (r - origin)) over the live rays, of per-ray
+    tensors x, y, ok of ONE shape [B, F, P, W]: tl_mtf_sums forward, tl_mtf_seed backward.  `origin`: a float64 tensor [B, F, W, 2],
+    possibly expanded; a constant of the calculation (the modulus does not depend on it): no gradient.  It is read in place where it
+    is contiguous and copied otherwise, as EnclosedEnergyFunction's centre is.  nu_x, nu_y: J <= MTF_MAX_J host floats (cycles per
+    unit of x).  The three ray arrays are brought to one layout exactly as FocusMomentsFunction does, and B is folded into F.
+    Nothing of size rays x J is stored."""
+
+    @staticmethod
+    def forward(ctx, x, y, ok, origin, nu_x, nu_y):
+        for name, t in (("x", x), ("y", y)):
+            _require_device(t, name)
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"torchoptics_amd: the MTF kernels take float32 tensors; `{name}` is {t.dtype} "
+                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+        _require_device(ok, "ray_ok")
+        _require_device(origin, "origin")
+        dev, full = x.device, x.shape
+        B, F, P, W = full
+        J = len(nu_x)
+        if not 1 <= J <= MTF_MAX_J or len(nu_y) != J:
+            raise ValueError(f"nu_x and nu_y must hold the same 1 .. {MTF_MAX_J} frequencies, got {J} and {len(nu_y)}")
+        if origin.dtype != torch.float64 or tuple(origin.shape) != (B, F, W, 2):
+            raise ValueError(f"origin must be a float64 tensor [B, F, W, 2] = {(B, F, W, 2)}, got {origin.dtype} {tuple(origin.shape)}")
+        st = _focus_layout((x, y))
+
+        def placed(t):
+            return t if _same_layout(t, full, st) else torch.empty_strided(full, st, dtype=t.dtype, device=dev).copy_(t)
+        x, y = placed(x), placed(y)
+        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
+        o64 = origin.detach()
+        if not o64.is_contiguous():
+            o64 = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev).copy_(o64)
+        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
+        sums = torch.empty((B, F, W, J, 2), dtype=torch.float64, device=dev)
+        ctx.save_for_backward(x, y, oks, o64)
+        ctx.plan = (st, s_f, (_host_doubles(nu_x), _host_doubles(nu_y), J))
+        if P == 0 or sums.numel() == 0:                     # an empty fan: every sum is 0
+            return sums.zero_()
+        ws = _workspace(_lib.lib().tl_mtf_workspace_bytes(B * F, P, W, J), dev)
+        _call("tl_mtf_sums", dev, dev.index, B * F, P, W, x, y, oks, s_f, st[2], st[3], o64, *ctx.plan[2], sums, ws, ws.numel(),
+              timed="tl_mtf_sums")
+        return sums
+
+    @staticmethod
+    def backward(ctx, g_sums):
+        x, y, oks, o64 = ctx.saved_tensors
+        dev, full = x.device, x.shape
+        B, F, P, W = full
+        st, s_f, freq = ctx.plan
+        outs = [torch.empty_strided(full, st, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2]]
+        if all(o is None for o in outs) or x.numel() == 0:
+            return (*outs, None, None, None, None)
+        gs = torch.empty(g_sums.shape, dtype=torch.float64, device=dev).copy_(g_sums)
+        ws = _workspace(_lib.lib().tl_mtf_workspace_bytes(B * F, P, W, freq[2]), dev)
+        _call("tl_mtf_seed", dev, dev.index, B * F, P, W, x, y, oks, s_f, st[2], st[3], o64, *freq, gs, *outs, ws, ws.numel(),
+              timed="tl_mtf_seed")
+        return (*outs, None, None, None, None)
 
 
 ZFIT_ORDERS = (2, 3, 4, 5, 6)      # radial orders the tl_zfit_* kernels are instantiated for
