@@ -36,9 +36,11 @@ BOUNDS (U = 2^-53; derived here, never fitted to a kernel's output).  The inputs
 """
 import numpy as np
 
+import rows_ref
+from rows_ref import BLOCK, CHUNK, MAX_Y, TARGET_BLOCKS, VEC, launches, plan        # noqa: F401 (the tests read them from here)
+
 U = 2.0 ** -53
-BLOCK, VEC, TARGET_BLOCKS, MAX_Y, MAX_K = 256, 4, 2048, 65535, 32
-CHUNK = BLOCK * VEC
+MAX_K = 32
 
 
 def sigma(u):
@@ -238,19 +240,5 @@ def sums_in_order(x, y, ok, radii, soft, shape, c, order, inner=np.float64):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the plan
-def plan(rows, P):
-    """(nbx, R) of the kernels: blocks per row and steps of 1024 rays per block, aiming at 2048 blocks (tl_focus_moments')."""
-    chunks = -(-P // CHUNK)
-    want = max(1, -(-TARGET_BLOCKS // rows))
-    R = -(-chunks // min(chunks, want))
-    return -(-chunks // R), R
-
-
 def workspace_bytes(F, P, W, K):
-    if min(F, P, W) < 1 or F * W >= 2 ** 31 or F >= 2 ** 31 or W >= 2 ** 31 or P >= 2 ** 31 or not 1 <= K <= MAX_K:
-        return 0
-    return F * W * plan(F * W, P)[0] * max(K, 3) * 8
-
-
-def launches(rows):
-    return [(r0, min(MAX_Y, rows - r0)) for r0 in range(0, rows, MAX_Y)]
+    return rows_ref.workspace_bytes(F, P, W, max(K, 3)) if 1 <= K <= MAX_K else 0

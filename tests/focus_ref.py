@@ -15,10 +15,11 @@ BOUNDS (U = 2^-53, derived, not measured).
 """
 import numpy as np
 
+import rows_ref
+from rows_ref import BLOCK, CHUNK, MAX_Y, TARGET_BLOCKS, VEC, launches, plan        # noqa: F401 (the tests read them from here)
+
 U = 2.0 ** -53
 NMOM = 11
-BLOCK, VEC, TARGET_BLOCKS, MAX_Y = 256, 4, 2048, 65535
-CHUNK = BLOCK * VEC
 
 
 def live_rays(cx, cy, ok):
@@ -144,23 +145,8 @@ def rms_shifted(x, y, cx, cy, ok, delta, common=("wavelength",), centroid="row")
 
 
 # ---------------------------------------------------------------------------------------------------- the kernels, emulated
-def plan(rows, P):
-    """(nbx, R) of tl_focus_moments: blocks per row and steps of 1024 rays per block, aiming at 2048 blocks."""
-    chunks = -(-P // CHUNK)
-    want = max(1, -(-TARGET_BLOCKS // rows))
-    R = -(-chunks // min(chunks, want))
-    return -(-chunks // R), R
-
-
 def workspace_bytes(F, P, W):
-    if min(F, P, W) < 1 or F * W >= 2 ** 31 or P >= 2 ** 31:
-        return 0
-    return F * W * plan(F * W, P)[0] * NMOM * 8
-
-
-def launches(rows):
-    """(row0, rows of the launch) of the grid-y chunks."""
-    return [(r0, min(MAX_Y, rows - r0)) for r0 in range(0, rows, MAX_Y)]
+    return rows_ref.workspace_bytes(F, P, W, NMOM)
 
 
 def emulate_moments(x, y, cx, cy, ok, aligned, wrong=None, batch=2048):
@@ -171,32 +157,7 @@ def emulate_moments(x, y, cx, cy, ok, aligned, wrong=None, batch=2048):
     B, F, P, W, _ = t.shape
     t = np.ascontiguousarray(t.transpose(0, 1, 3, 2, 4)).reshape(B * F * W, P, NMOM)
     rows = B * F * W
-    nbx, R = plan(rows, P)
-    out = np.zeros((rows, NMOM))
-    lane, xor = np.arange(BLOCK), np.arange(64)
-    for r0 in range(0, rows, batch):
-        for vec in (False, True):
-            sel = r0 + np.flatnonzero(np.asarray(aligned[r0:r0 + batch]) == vec)
-            if not len(sel):
-                continue
-            acc = np.zeros((len(sel), NMOM))
-            for bx in range(nbx):
-                first, last = bx * R * CHUNK, min((bx + 1) * R * CHUNK, P)
-                lanes = np.zeros((len(sel), BLOCK, NMOM))
-                steps = [first + k * CHUNK + VEC * lane + j for k in range(R) for j in range(VEC)] if vec else \
-                        [first + k * BLOCK + lane for k in range(R * VEC)]
-                for idx in steps:
-                    m = idx < last
-                    if m.any():
-                        lanes[:, m] += t[sel][:, idx[m]]
-                w = lanes.reshape(len(sel), BLOCK // 64, 64, NMOM)
-                for o in (32, 16, 8, 4, 2, 1):
-                    w = w + w[:, :, xor ^ o]
-                part = np.zeros((len(sel), NMOM))
-                for q in range(BLOCK // 64):
-                    part = part + w[:, q, 0]
-                acc = acc + part
-            out[sel] = acc
+    out = rows_ref.emulate_sums(t, aligned, batch)
     if wrong == "transpose":                                  # the row of (f, w) taken as (w, f)
         out = out.reshape(B, W, F, NMOM).transpose(0, 2, 1, 3).reshape(rows, NMOM)
     return out.reshape(B, F, W, NMOM)

@@ -30,12 +30,14 @@ import math
 
 import numpy as np
 
+import rows_ref
+from rows_ref import BLOCK, CHUNK, MAX_Y, TARGET_BLOCKS, VEC, plan        # noqa: F401 (the tests read them from here)
+
 LD = np.longdouble
 assert np.finfo(LD).eps < 2e-19, "the reference needs an 80-bit long double"
 TWO_PI = 8 * np.arctan(LD(1))
 U = 2.0 ** -53
-BLOCK, VEC, TARGET_BLOCKS, MAX_Y, MAX_J = 256, 4, 2048, 65535, 16
-CHUNK = BLOCK * VEC
+MAX_J = 16
 SEED_C = 4 + 3 + 1 + (MAX_J - 1) + 2
 
 
@@ -143,15 +145,5 @@ def sums_in_order(x, y, ok, origin, nu_x, nu_y, order, phase=np.float64, trig=np
 
 
 # ---------------------------------------------------------------------------------------------------------------- the plan
-def plan(rows, P):
-    """(nbx, R) of the kernels: blocks per row and steps of 1024 rays per block, aiming at 2048 blocks (tl_enclosed_sums')."""
-    chunks = -(-P // CHUNK)
-    want = max(1, -(-TARGET_BLOCKS // rows))
-    R = -(-chunks // min(chunks, want))
-    return -(-chunks // R), R
-
-
 def workspace_bytes(F, P, W, J):
-    if min(F, P, W) < 1 or F * W >= 2 ** 31 or F >= 2 ** 31 or W >= 2 ** 31 or P >= 2 ** 31 or not 1 <= J <= MAX_J:
-        return 0
-    return F * W * plan(F * W, P)[0] * 2 * J * 8
+    return rows_ref.workspace_bytes(F, P, W, 2 * J) if 1 <= J <= MAX_J else 0

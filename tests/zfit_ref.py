@@ -30,10 +30,11 @@ BOUNDS (U = 2^-53, derived, not measured).
 """
 import numpy as np
 
+import rows_ref
+from rows_ref import BLOCK, CHUNK, MAX_Y, TARGET_BLOCKS, VEC, plan        # noqa: F401 (the tests read them from here)
+
 U = 2.0 ** -53
 PIVOT_FLOOR = 2.0 ** -30
-BLOCK, VEC, TARGET_BLOCKS, MAX_Y = 256, 4, 2048, 65535
-CHUNK = BLOCK * VEC
 
 
 def sizes(order):
@@ -248,18 +249,8 @@ def finish(a, q, n, valid, scale=1.0):
 
 
 # ---------------------------------------------------------------------------------------------------- the kernels, emulated
-def plan(rows, P):
-    """(nbx, R) of tl_zfit_moments (tl_focus_moments' plan): blocks per row and steps of 1024 rays per block."""
-    chunks = -(-P // CHUNK)
-    want = max(1, -(-TARGET_BLOCKS // rows))
-    R = -(-chunks // min(chunks, want))
-    return -(-chunks // R), R
-
-
 def workspace_bytes(F, P, W, order):
-    if min(F, P, W) < 1 or F * W >= 2 ** 31 or P >= 2 ** 31 or F >= 2 ** 31 or W >= 2 ** 31 or order not in (2, 3, 4, 5, 6):
-        return 0
-    return F * W * plan(F * W, P)[0] * sizes(order)[1] * 8
+    return rows_ref.workspace_bytes(F, P, W, sizes(order)[1]) if order in (2, 3, 4, 5, 6) else 0
 
 
 def emulate_moments(x, y, ok, px, py, order, aligned, dtype=np.float64, wrong=None):
@@ -269,30 +260,5 @@ def emulate_moments(x, y, ok, px, py, order, aligned, dtype=np.float64, wrong=No
     t = ray_terms(x, y, ok, px, py, order, dtype=dtype, wrong=wrong)
     B, F, P, W, K = t.shape
     t = np.ascontiguousarray(t.transpose(0, 1, 3, 2, 4)).reshape(B * F * W, P, K)
-    rows = B * F * W
-    nbx, R = plan(rows, P)
-    out = np.zeros((rows, K))
-    lane, xor = np.arange(BLOCK), np.arange(64)
-    for vec in (False, True):
-        sel = np.flatnonzero(np.asarray(aligned) == vec)
-        if not len(sel):
-            continue
-        acc = np.zeros((len(sel), K))
-        for bx in range(nbx):
-            first, last = bx * R * CHUNK, min((bx + 1) * R * CHUNK, P)
-            lanes = np.zeros((len(sel), BLOCK, K))
-            steps = [first + k * CHUNK + VEC * lane + j for k in range(R) for j in range(VEC)] if vec else \
-                    [first + k * BLOCK + lane for k in range(R * VEC)]
-            for idx in steps:
-                m = idx < last
-                if m.any():
-                    lanes[:, m] += t[sel][:, idx[m]]
-            w = lanes.reshape(len(sel), BLOCK // 64, 64, K)
-            for o in (32, 16, 8, 4, 2, 1):
-                w = w + w[:, :, xor ^ o]
-            part = np.zeros((len(sel), K))
-            for i in range(BLOCK // 64):
-                part = part + w[:, i, 0]
-            acc = acc + part
-        out[sel] = acc
+    out = rows_ref.emulate_sums(t, np.asarray(aligned))
     return out.reshape(B, F, W, K)

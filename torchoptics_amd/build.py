@@ -55,7 +55,7 @@ UNITS = {
 # tl_mtf.hip: the same crash of the compiler under iterative-ilp, on mtf_sums_kernel (8 to 32 fp64 accumulators around an inlined
 # sincospi); the default scheduler gives 62 / 78 / 110 VGPRs and no scratch (profiles/mtf_kernel_resources.txt).
 WITHOUT = {"tl_zfit.hip": ("-amdgpu-sched-strategy=iterative-ilp",), "tl_mtf.hip": ("-amdgpu-sched-strategy=iterative-ilp",)}
-DEPS = ["tl_kernels.inc", "tl_common.h", os.path.join("..", "..", "include", "tl_trace.h")]
+DEPS = ["tl_kernels.inc", "tl_common.h", "tl_rows.h", os.path.join("..", "..", "include", "tl_trace.h")]
 
 
 def _hipcc():

@@ -11,31 +11,19 @@
 // centre sits at millimetres while a spot measures microns, and (R - rho) inv amplifies rho's error by rho inv: fp32 would
 // leave nothing of a band of a few microns.
 //
-// LAYOUT AND PLAN are the focus kernels' (tl_focus.hip): grid (nbx, rows of this launch), 256 lanes; block bx of a row takes
-// the rays [bx R 1024, (bx + 1) R 1024); where the ray stride is 1 and the row's base addresses are aligned a lane takes four
-// consecutive rays with 16-byte loads (ok as one dword), otherwise one ray at a time.  The K running sums are a static register
-// array of the compile-time bucket KB = 8 / 16 / 32 >= K; radii and 1 / softness travel in a by-value kernel argument, so nothing
-// is uploaded, and are staged in LDS, read wave-uniformly (a broadcast).  A butterfly over the wave, the four waves added in order through LDS, one partial
-// per block in the workspace, enclosed_reduce_kernel adds a row's partials in order.  No atomics: the same bits on every run.
+// LAYOUT, PLAN, PARTIALS AND REDUCE are the row frame's (tl_rows.h).  The K running sums are a static register array of the
+// compile-time bucket KB = 8 / 16 / 32 >= K; radii and 1 / softness travel in a by-value kernel argument, so nothing is uploaded,
+// and are staged in LDS, read wave-uniformly (a broadcast).
 // SEED.  enclosed_seed_kernel walks the rays the same way: the K seeds of the row staged in LDS next to the radii, per ray the sum over
 // k of g_k d e_k / d(x, y) in fp64, rounded once to fp32 at the store; the centre's gradient is minus the sum of those over the
 // row, through partials and the same reduce.  Dead rays get zeros.
-#include "tl_common.h"
+#include "tl_rows.h"
 
 #include <math.h>
-#include <stdio.h>
-
-#include <algorithm>
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kVec = 4;                         // rays per lane and load on the aligned path
-constexpr int kChunk = kBlock * kVec;           // rays a block takes per step: the unit of the plan
-constexpr int kMaxY = 65535;                    // rows per launch (grid y)
 constexpr int kMaxK = 32;                       // radii per call
-constexpr int64_t kTargetBlocks = 2048;         // 256 CUs x 8 blocks of 4 waves
-constexpr int64_t kMaxDim = ((int64_t)1 << 31) - 1;
 constexpr int kCircle = 0, kSquare = 1;
 
 struct Rays {
@@ -45,74 +33,6 @@ struct Rays {
 };
 
 struct Edge { double R[kMaxK], inv[kMaxK]; };   // radii and 1 / softness; slots from K on hold 0 and are never stored
-
-struct Plan { int nbx, R; };                    // blocks per row, steps of kChunk rays per block
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-Plan enclosed_plan(int64_t rows, int64_t P)
-{
-    const int64_t chunks = cdiv(P, kChunk);
-    const int64_t want = std::max<int64_t>(1, cdiv(kTargetBlocks, rows));
-    const int64_t R = cdiv(chunks, std::min(chunks, want));
-    return {(int)cdiv(chunks, R), (int)R};
-}
-
-__device__ __forceinline__ bool aligned_to(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
-
-// body(o, xs, ys, oks) on every ray of [first, last) that this lane owns: four consecutive rays at element offset o on the
-// aligned path, one elsewhere (the arrays' length says which)
-template <class Body>
-__device__ __forceinline__ void walk_rays(const float *__restrict__ x, const float *__restrict__ y, const uint8_t *__restrict__ ok,
-                                          int64_t s_p, bool vec, int64_t first, int64_t last, int64_t P, Body &&body)
-{
-    if (vec) {                                              // (uniform over the block)
-        for (int64_t ip = first + kVec * (int64_t)threadIdx.x; ip < last; ip += kChunk) {
-            if (ip + kVec <= P) {
-                const float4 x4 = *reinterpret_cast<const float4 *>(x + ip), y4 = *reinterpret_cast<const float4 *>(y + ip);
-                const unsigned o4 = *reinterpret_cast<const unsigned *>(ok + ip);
-                const float xs[kVec] = {x4.x, x4.y, x4.z, x4.w}, ys[kVec] = {y4.x, y4.y, y4.z, y4.w};
-                const unsigned oks[kVec] = {o4 & 0xffu, o4 & 0xff00u, o4 & 0xff0000u, o4 & 0xff000000u};
-                body(ip, xs, ys, oks);
-            } else {                                        // the last one to three rays of the row
-                for (int64_t q = ip; q < P; ++q) {
-                    const float xs[1] = {x[q]}, ys[1] = {y[q]};
-                    const unsigned oks[1] = {ok[q]};
-                    body(q, xs, ys, oks);
-                }
-            }
-        }
-    } else {
-        for (int64_t ip = first + threadIdx.x; ip < last; ip += kBlock) {
-            const int64_t o = ip * s_p;
-            const float xs[1] = {x[o]}, ys[1] = {y[o]};
-            const unsigned oks[1] = {ok[o]};
-            body(o, xs, ys, oks);
-        }
-    }
-}
-
-// part[(row nbx + bx) n + j] = the block's sum of m[j], j < n <= N: a butterfly over the wave, the four waves in order
-template <int N>
-__device__ __forceinline__ void block_partial(const double (&m)[N], double *__restrict__ part, int row, int nbx, int n)
-{
-    __shared__ double red[kBlock / 64][N];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double v = m[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wv][j] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < kBlock / 64; ++q) s += red[q][threadIdx.x];
-        part[((int64_t)row * nbx + blockIdx.x) * n + threadIdx.x] = s;
-    }
-}
 
 // t of the edge: (u + 1) / 2 clamped to [0, 1]
 __device__ __forceinline__ double edge_t(double u)
@@ -141,21 +61,6 @@ __device__ __forceinline__ void stage_edge(const Edge &e, double *eR, double *eI
         eI[threadIdx.x] = e.inv[threadIdx.x];
     }
     __syncthreads();
-}
-
-struct RowBase {
-    const float *x, *y;
-    const uint8_t *ok;
-    int64_t off;
-    int row;
-};
-
-__device__ __forceinline__ RowBase row_base(const Rays &r, int W, int row0)
-{
-    const int row = row0 + (int)blockIdx.y;
-    const int f = row / W, w = row - f * W;
-    const int64_t off = f * r.s_f + w * r.s_w;
-    return {r.x + off, r.y + off, r.ok + off, off, row};
 }
 
 __global__ __launch_bounds__(kBlock) void enclosed_centroid_kernel(Rays r, int64_t P, int W, int row0, double *__restrict__ part,
@@ -220,17 +125,10 @@ __global__ __launch_bounds__(kBlock) void enclosed_sums_kernel(Rays r, int64_t P
     block_partial(m, part, b.row, nbx, K);
 }
 
-// out[row][j] = the row's nbx partials added in order
 __global__ __launch_bounds__(kBlock) void enclosed_reduce_kernel(const double *__restrict__ part, double *__restrict__ out,
                                                                  int64_t total, int nbx, int n)
 {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= total) return;
-    const int64_t row = i / n;
-    const double *p = part + row * nbx * n + (i - row * n);
-    double s = 0.0;
-    for (int b = 0; b < nbx; ++b) s += p[(int64_t)b * n];
-    out[i] = s;
+    reduce_rows(part, out, total, nbx, n);
 }
 
 template <int SHAPE>
@@ -313,55 +211,44 @@ struct Checked { int rc; Edge e; };
 // the argument check the calls share; `name` opens the message
 int check_rays(const char *name, int64_t F, int64_t P, int64_t W, const Rays &r, const char *missing)
 {
-    static thread_local char msg[200];
-    const char *what = nullptr;
-    if (F < 1 || P < 1 || W < 1) what = "F, P and W must be at least 1";
-    else if (F > kMaxDim || W > kMaxDim || F * W > kMaxDim || P > kMaxDim) what = "F W and P must stay below 2^31";
-    else if (!r.x || !r.y || !r.ok) what = "x, y and ok are required";
-    else if (missing) what = missing;
-    if (!what) return TL_OK;
-    snprintf(msg, sizeof msg, "%s: %s", name, what);
-    return tl_host::fail(TL_EINVAL, msg);
+    if (const char *what = size_fault(F, P, W)) return refuse(name, what);
+    if (!r.x || !r.y || !r.ok) return refuse(name, "x, y and ok are required");
+    if (missing) return refuse(name, missing);
+    return TL_OK;
 }
 
 // radii and 1 / softness (host) into the kernel argument; refuses what the definition excludes
 Checked check_edge(const char *name, const double *radii, const double *inv_soft, int K, int shape)
 {
-    static thread_local char msg[200];
     Checked c = {TL_OK, {}};
     const char *what = nullptr;
     if (K < 1 || K > kMaxK) what = "K must be 1 .. 32";
     else if (shape != kCircle && shape != kSquare) what = "shape must be 0 (circle) or 1 (square)";
     else if (!radii || !inv_soft) what = "radii and inv_soft (host) are required";
-    else {
-        for (int k = 0; k < K && !what; ++k) {
-            if (!(std::isfinite(radii[k]) && radii[k] > 0.0)) what = "every radius must be finite and positive";
-            else if (!(std::isfinite(inv_soft[k]) && inv_soft[k] > 0.0)) what = "every softness must be finite and positive";
-            else if (k > 0 && !(radii[k] > radii[k - 1])) what = "the radii must be strictly increasing";
-            c.e.R[k] = radii[k];
-            c.e.inv[k] = inv_soft[k];
-        }
+    for (int k = 0; k < K && !what; ++k) {
+        if (!(std::isfinite(radii[k]) && radii[k] > 0.0)) what = "every radius must be finite and positive";
+        else if (!(std::isfinite(inv_soft[k]) && inv_soft[k] > 0.0)) what = "every softness must be finite and positive";
+        else if (k > 0 && !(radii[k] > radii[k - 1])) what = "the radii must be strictly increasing";
+        c.e.R[k] = radii[k];
+        c.e.inv[k] = inv_soft[k];
     }
-    if (what) {
-        snprintf(msg, sizeof msg, "%s: %s", name, what);
-        c.rc = tl_host::fail(TL_EINVAL, msg);
-    }
+    if (what) c.rc = refuse(name, what);
     return c;
 }
 
-int check_workspace(const char *name, const void *ws, size_t bytes, size_t need)
+// everything before the first HIP call: rays, edge, workspace, in that order
+Checked check_call(const char *name, int64_t F, int64_t P, int64_t W, const Rays &r, const char *missing, const double *radii,
+                   const double *inv_soft, int K, int shape, const void *ws, size_t ws_bytes)
 {
-    static thread_local char msg[200];
-    if (ws && bytes >= need) return TL_OK;
-    snprintf(msg, sizeof msg, "%s: workspace NULL or below tl_enclosed_workspace_bytes", name);
-    return tl_host::fail(TL_EWORKSPACE, msg);
+    Checked c = {check_rays(name, F, P, W, r, missing), {}};
+    if (!c.rc) c = check_edge(name, radii, inv_soft, K, shape);
+    if (!c.rc) c.rc = check_workspace(name, ws, ws_bytes, tl_enclosed_workspace_bytes(F, P, W, K), "tl_enclosed_workspace_bytes");
+    return c;
 }
 
 int reduce(const double *part, double *out, int64_t rows, int nbx, int n, hipStream_t st)
 {
-    const int64_t total = rows * n;
-    hipLaunchKernelGGL(enclosed_reduce_kernel, dim3((unsigned)cdiv(total, kBlock)), dim3(kBlock), 0, st, part, out, total, nbx, n);
-    return tl_host::launched("enclosed_reduce_kernel launch");
+    return launch_reduce(enclosed_reduce_kernel, "enclosed_reduce_kernel launch", part, out, rows, nbx, n, st);
 }
 
 template <int KB, int SHAPE>
@@ -395,8 +282,8 @@ extern "C" {
 
 size_t tl_enclosed_workspace_bytes(int64_t F, int64_t P, int64_t W, int K)
 {
-    if (F < 1 || P < 1 || W < 1 || F > kMaxDim || W > kMaxDim || F * W > kMaxDim || P > kMaxDim || K < 1 || K > kMaxK) return 0;
-    return (size_t)(F * W) * (size_t)enclosed_plan(F * W, P).nbx * (size_t)std::max(K, 3) * sizeof(double);
+    if (size_fault(F, P, W) || K < 1 || K > kMaxK) return 0;
+    return (size_t)(F * W) * (size_t)row_plan(F * W, P).nbx * (size_t)std::max(K, 3) * sizeof(double);
 }
 
 int tl_enclosed_centroid(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const uint8_t *ok,
@@ -405,17 +292,16 @@ int tl_enclosed_centroid(int32_t device, int64_t F, int64_t P, int64_t W, const 
     static const char *name = "tl_enclosed_centroid";
     const Rays r = {x, y, ok, s_f, s_p, s_w};
     if (const int rc = check_rays(name, F, P, W, r, S ? nullptr : "the S pointer is NULL")) return rc;
-    if (const int rc = check_workspace(name, workspace, workspace_bytes, tl_enclosed_workspace_bytes(F, P, W, 1))) return rc;
+    if (const int rc = check_workspace(name, workspace, workspace_bytes, tl_enclosed_workspace_bytes(F, P, W, 1), "tl_enclosed_workspace_bytes"))
+        return rc;
     if (const int rc = tl_host::use_device(device)) return rc;
     const int64_t rows = F * W;
-    const Plan pl = enclosed_plan(rows, P);
+    const Plan pl = row_plan(rows, P);
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-        hipLaunchKernelGGL(enclosed_centroid_kernel, dim3(pl.nbx, ny), dim3(kBlock), 0, st, r, P, (int)W, (int)row0,
-                           (double *)workspace, pl.nbx, pl.R);
-        if (const int rc = tl_host::launched("enclosed_centroid_kernel launch")) return rc;
-    }
+    if (const int rc = launch_rows(rows, pl.nbx, "enclosed_centroid_kernel launch", [&](dim3 grid, int row0) {
+            hipLaunchKernelGGL(enclosed_centroid_kernel, grid, dim3(kBlock), 0, st, r, P, (int)W, row0, (double *)workspace, pl.nbx, pl.R);
+        }))
+        return rc;
     return reduce((const double *)workspace, S, rows, pl.nbx, 3, st);
 }
 
@@ -423,22 +309,18 @@ int tl_enclosed_sums(int32_t device, int64_t F, int64_t P, int64_t W, const floa
                      int64_t s_f, int64_t s_p, int64_t s_w, const double *centre, const double *radii, const double *inv_soft,
                      int K, int shape, double *sums, void *workspace, size_t workspace_bytes, void *stream)
 {
-    static const char *name = "tl_enclosed_sums";
     const Rays r = {x, y, ok, s_f, s_p, s_w};
-    if (const int rc = check_rays(name, F, P, W, r, !centre ? "the centre pointer is NULL" : !sums ? "the sums pointer is NULL" : nullptr))
-        return rc;
-    const Checked c = check_edge(name, radii, inv_soft, K, shape);
+    const Checked c = check_call("tl_enclosed_sums", F, P, W, r, !centre ? "the centre pointer is NULL" : !sums ? "the sums pointer is NULL" : nullptr,
+                                 radii, inv_soft, K, shape, workspace, workspace_bytes);
     if (c.rc) return c.rc;
-    if (const int rc = check_workspace(name, workspace, workspace_bytes, tl_enclosed_workspace_bytes(F, P, W, K))) return rc;
     if (const int rc = tl_host::use_device(device)) return rc;
     const int64_t rows = F * W;
-    const Plan pl = enclosed_plan(rows, P);
+    const Plan pl = row_plan(rows, P);
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-        sums_launcher(K, shape)(dim3(pl.nbx, ny), st, r, P, (int)W, (int)row0, centre, c.e, K, (double *)workspace, pl);
-        if (const int rc = tl_host::launched("enclosed_sums_kernel launch")) return rc;
-    }
+    if (const int rc = launch_rows(rows, pl.nbx, "enclosed_sums_kernel launch", [&](dim3 grid, int row0) {
+            sums_launcher(K, shape)(grid, st, r, P, (int)W, row0, centre, c.e, K, (double *)workspace, pl);
+        }))
+        return rc;
     return reduce((const double *)workspace, sums, rows, pl.nbx, K, st);
 }
 
@@ -447,25 +329,21 @@ int tl_enclosed_seed(int32_t device, int64_t F, int64_t P, int64_t W, const floa
                      int K, int shape, const double *g_sums, const double *g_lin, float *gx, float *gy, double *g_centre,
                      void *workspace, size_t workspace_bytes, void *stream)
 {
-    static const char *name = "tl_enclosed_seed";
     const Rays r = {x, y, ok, s_f, s_p, s_w};
-    if (const int rc = check_rays(name, F, P, W, r, !centre ? "the centre pointer is NULL" : !g_sums ? "the g_sums pointer is NULL" :
-                                  !gx && !gy && !g_centre ? "gx, gy and g_centre are all NULL" : nullptr))
-        return rc;
-    const Checked c = check_edge(name, radii, inv_soft, K, shape);
+    const Checked c = check_call("tl_enclosed_seed", F, P, W, r, !centre ? "the centre pointer is NULL" : !g_sums ? "the g_sums pointer is NULL" :
+                                 !gx && !gy && !g_centre ? "gx, gy and g_centre are all NULL" : nullptr, radii, inv_soft, K, shape,
+                                 workspace, workspace_bytes);
     if (c.rc) return c.rc;
-    if (const int rc = check_workspace(name, workspace, workspace_bytes, tl_enclosed_workspace_bytes(F, P, W, K))) return rc;
     if (const int rc = tl_host::use_device(device)) return rc;
     const int64_t rows = F * W;
-    const Plan pl = enclosed_plan(rows, P);
+    const Plan pl = row_plan(rows, P);
     hipStream_t st = (hipStream_t)stream;
     double *part = g_centre ? (double *)workspace : nullptr;
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-        (shape == kCircle ? launch_seed<kCircle> : launch_seed<kSquare>)(dim3(pl.nbx, ny), st, r, P, (int)W, (int)row0, centre, c.e, K,
-                                                                         g_sums, g_lin, gx, gy, part, pl);
-        if (const int rc = tl_host::launched("enclosed_seed_kernel launch")) return rc;
-    }
+    if (const int rc = launch_rows(rows, pl.nbx, "enclosed_seed_kernel launch", [&](dim3 grid, int row0) {
+            (shape == kCircle ? launch_seed<kCircle> : launch_seed<kSquare>)(grid, st, r, P, (int)W, row0, centre, c.e, K, g_sums, g_lin,
+                                                                             gx, gy, part, pl);
+        }))
+        return rc;
     return g_centre ? reduce(part, g_centre, rows, pl.nbx, 2, st) : TL_OK;
 }
 

@@ -10,50 +10,21 @@
 // ray's eleven terms have the bits of the definition evaluated in any IEEE fp64 arithmetic, only the ORDER of the sums is
 // this file's.
 //
-// FORWARD.  focus_moments_kernel: grid (nbx, rows of this launch), 256 lanes.  Block bx of a row takes the rays
-// [bx R 1024, (bx + 1) R 1024): where the ray stride is 1 and the row's five base addresses are aligned, a lane takes four
-// consecutive rays with 16-byte loads (ok as one dword) and strides by 1024; otherwise one ray at a time, striding by 256.
-// Eleven fp64 accumulators per lane, a butterfly over the wave, the four waves added in order through LDS: one partial of
-// eleven doubles per block in the workspace.  focus_reduce_kernel adds the nbx partials of a row in order.  No atomics: the
-// same bits on every run.  The plan aims at ~2048 blocks (8 per CU) whatever the size, so the partials stay far below a byte
-// per ray; rows beyond 65535 go in further launches (grid y), back to back on the stream.
+// FORWARD.  focus_moments_kernel: layout, plan, partials and reduce are the row frame's (tl_rows.h), with five base addresses to
+// be aligned for the 16-byte path and eleven fp64 accumulators per lane: one partial of eleven doubles per block.
 // SEED.  focus_seed_kernel: one lane per four rays (the same two load paths), the eleven seeds of the row read once
 // (wave-uniform), everything in fp64, one rounding to fp32 at the store.  Dead rays get zeros.
-#include "tl_common.h"
-
-#include <stdio.h>
-
-#include <algorithm>
+#include "tl_rows.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kNF = 11;                         // moments per row
-constexpr int kVec = 4;                         // rays per lane and load on the aligned path
-constexpr int kChunk = kBlock * kVec;           // rays a block takes per step: the unit of the plan
-constexpr int kMaxY = 65535;                    // rows per launch (grid y)
-constexpr int64_t kTargetBlocks = 2048;         // 256 CUs x 8 blocks of 4 waves
-constexpr int64_t kMaxDim = ((int64_t)1 << 31) - 1;
 
 struct Rays {
     const float *x, *y, *cx, *cy;
     const uint8_t *ok;
     int64_t s_f, s_p, s_w;
 };
-
-struct Plan { int nbx, R; };                    // blocks per row, steps of kChunk rays per block
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-Plan focus_plan(int64_t rows, int64_t P)
-{
-    const int64_t chunks = cdiv(P, kChunk);
-    const int64_t want = std::max<int64_t>(1, cdiv(kTargetBlocks, rows));
-    const int64_t R = cdiv(chunks, std::min(chunks, want));
-    return {(int)cdiv(chunks, R), (int)R};
-}
-
-__device__ __forceinline__ bool aligned_to(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
 // the eleven terms of one ray, added to m
 __device__ __forceinline__ void add_ray(double (&m)[kNF], float xf, float yf, float cxf, float cyf, unsigned okb)
@@ -106,35 +77,14 @@ __global__ __launch_bounds__(kBlock) void focus_moments_kernel(Rays r, int64_t P
             add_ray(m, x[o], y[o], cx[o], cy[o], ok[o]);
         }
     }
-    __shared__ double red[kBlock / 64][kNF];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < kNF; ++j) {
-        double v = m[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wv][j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kNF) {
-        double s = 0.0;
-#pragma unroll
-        for (int q = 0; q < kBlock / 64; ++q) s += red[q][threadIdx.x];
-        part[((int64_t)row * nbx + blockIdx.x) * kNF + threadIdx.x] = s;
-    }
+    block_partial(m, part, row, nbx, kNF);
 }
 
-// moments[row][k] = the row's nbx partials added in order
+// (kNF as a literal: the division by it folds)
 __global__ __launch_bounds__(kBlock) void focus_reduce_kernel(const double *__restrict__ part, double *__restrict__ moments,
                                                               int64_t total, int nbx)
 {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= total) return;
-    const int64_t row = i / kNF;
-    const double *p = part + row * nbx * kNF + (i - row * kNF);
-    double s = 0.0;
-    for (int b = 0; b < nbx; ++b) s += p[(int64_t)b * kNF];
-    moments[i] = s;
+    reduce_rows(part, moments, total, nbx, kNF);
 }
 
 struct Seeds { float *gx, *gy, *gcx, *gcy; };
@@ -211,15 +161,10 @@ __global__ __launch_bounds__(kBlock) void focus_seed_kernel(Rays r, int64_t P, i
 // the argument check both calls share; `name` opens the message
 int check_rays(const char *name, int64_t F, int64_t P, int64_t W, const Rays &r, const void *moments)
 {
-    static thread_local char msg[160];
-    const char *what = nullptr;
-    if (F < 1 || P < 1 || W < 1) what = "F, P and W must be at least 1";
-    else if (F > kMaxDim || W > kMaxDim || F * W > kMaxDim || P > kMaxDim) what = "F W and P must stay below 2^31";
-    else if (!r.x || !r.y || !r.cx || !r.cy || !r.ok) what = "x, y, cx, cy and ok are required";
-    else if (!moments) what = "the moments pointer is NULL";
-    if (!what) return TL_OK;
-    snprintf(msg, sizeof msg, "%s: %s", name, what);
-    return tl_host::fail(TL_EINVAL, msg);
+    if (const char *what = size_fault(F, P, W)) return refuse(name, what);
+    if (!r.x || !r.y || !r.cx || !r.cy || !r.ok) return refuse(name, "x, y, cx, cy and ok are required");
+    if (!moments) return refuse(name, "the moments pointer is NULL");
+    return TL_OK;
 }
 
 }  // namespace
@@ -228,31 +173,29 @@ extern "C" {
 
 size_t tl_focus_workspace_bytes(int64_t F, int64_t P, int64_t W)
 {
-    if (F < 1 || P < 1 || W < 1 || F > kMaxDim || W > kMaxDim || F * W > kMaxDim || P > kMaxDim) return 0;
-    return (size_t)(F * W) * (size_t)focus_plan(F * W, P).nbx * kNF * sizeof(double);
+    if (size_fault(F, P, W)) return 0;
+    return (size_t)(F * W) * (size_t)row_plan(F * W, P).nbx * kNF * sizeof(double);
 }
 
 int tl_focus_moments(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const float *cx,
                      const float *cy, const uint8_t *ok, int64_t s_f, int64_t s_p, int64_t s_w, double *moments,
                      void *workspace, size_t workspace_bytes, void *stream)
 {
+    static const char *name = "tl_focus_moments";
     const Rays r = {x, y, cx, cy, ok, s_f, s_p, s_w};
-    if (const int rc = check_rays("tl_focus_moments", F, P, W, r, moments)) return rc;
-    if (!workspace || workspace_bytes < tl_focus_workspace_bytes(F, P, W))
-        return tl_host::fail(TL_EWORKSPACE, "tl_focus_moments: workspace NULL or below tl_focus_workspace_bytes");
+    if (const int rc = check_rays(name, F, P, W, r, moments)) return rc;
+    if (const int rc = check_workspace(name, workspace, workspace_bytes, tl_focus_workspace_bytes(F, P, W), "tl_focus_workspace_bytes"))
+        return rc;
     if (const int rc = tl_host::use_device(device)) return rc;
     const int64_t rows = F * W;
-    const Plan pl = focus_plan(rows, P);
+    const Plan pl = row_plan(rows, P);
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-        hipLaunchKernelGGL(focus_moments_kernel, dim3(pl.nbx, ny), dim3(kBlock), 0, st, r, P, (int)W, (int)row0,
-                           (double *)workspace, pl.nbx, pl.R);
-        if (const int rc = tl_host::launched("focus_moments_kernel launch")) return rc;
-    }
-    const int64_t total = rows * kNF;
-    hipLaunchKernelGGL(focus_reduce_kernel, dim3((unsigned)cdiv(total, kBlock)), dim3(kBlock), 0, st, (const double *)workspace,
-                       moments, total, pl.nbx);
+    if (const int rc = launch_rows(rows, pl.nbx, "focus_moments_kernel launch", [&](dim3 grid, int row0) {
+            hipLaunchKernelGGL(focus_moments_kernel, grid, dim3(kBlock), 0, st, r, P, (int)W, row0, (double *)workspace, pl.nbx, pl.R);
+        }))
+        return rc;
+    hipLaunchKernelGGL(focus_reduce_kernel, dim3((unsigned)cdiv(rows * kNF, kBlock)), dim3(kBlock), 0, st, (const double *)workspace,
+                       moments, rows * kNF, pl.nbx);
     return tl_host::launched("focus_reduce_kernel launch");
 }
 
@@ -262,17 +205,12 @@ int tl_focus_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *
 {
     const Rays r = {x, y, cx, cy, ok, s_f, s_p, s_w};
     if (const int rc = check_rays("tl_focus_seed", F, P, W, r, g_moments)) return rc;
-    if (!gx && !gy && !gcx && !gcy) return tl_host::fail(TL_EINVAL, "tl_focus_seed: gx, gy, gcx and gcy are all NULL");
+    if (!gx && !gy && !gcx && !gcy) return refuse("tl_focus_seed", "gx, gy, gcx and gcy are all NULL");
     if (const int rc = tl_host::use_device(device)) return rc;
-    const int64_t rows = F * W;
     const Seeds out = {gx, gy, gcx, gcy};
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-        hipLaunchKernelGGL(focus_seed_kernel, dim3((unsigned)cdiv(P, kChunk), ny), dim3(kBlock), 0, (hipStream_t)stream, r, P,
-                           (int)W, (int)row0, g_moments, out);
-        if (const int rc = tl_host::launched("focus_seed_kernel launch")) return rc;
-    }
-    return TL_OK;
+    return launch_rows(F * W, cdiv(P, kChunk), "focus_seed_kernel launch", [&](dim3 grid, int row0) {
+        hipLaunchKernelGGL(focus_seed_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, r, P, (int)W, row0, g_moments, out);
+    });
 }
 
 }  // extern "C"

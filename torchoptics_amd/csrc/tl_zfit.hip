@@ -12,9 +12,7 @@
 // the sums is this file's.  Triangle index of (a, b): tri = (a + b)(a + b + 1) / 2 + b; a row's K sums are mu, xi, eta, sum x^2,
 // sum y^2 in that order.
 //
-// MOMENTS.  zfit_moments_kernel<N, PART>: layout handling, launch plan and reduction are tl_focus.hip's (256 lanes; four rays per
-// lane with 16-byte loads where the ray strides are 1 and the row's bases are aligned, one ray at a time elsewhere; ~2048 blocks;
-// one partial per block, zfit_reduce_kernel adds a row's partials in order; rows beyond 65535 in further launches; no atomics).
+// MOMENTS.  zfit_moments_kernel<N, PART>: layout, plan, partials and reduce are the row frame's (tl_rows.h).
 // PART 0 holds all K accumulators (order 5: 77 of them in 230 VGPRs, two waves per SIMD); order 6 goes as PART 1 (the 66 mu) and
 // PART 2 (xi, eta, sum x^2, sum y^2: 44) in two launches, as 110 fp64 accumulators would leave one wave per SIMD.  The pupil coordinates have a stride triple of their own (0 over f and w
 // for a shared pupil).
@@ -26,20 +24,10 @@
 // solves the backward's system from the stored factor and turns b_bar into the monomial coefficients the seed kernel evaluates.
 // SEED.  zfit_seed_kernel<N>: one lane per four rays, the row's J + 1 numbers read once, the two polynomials by Horner in fp64,
 // one rounding to fp32 at the store.  Dead rays and invalid rows get zeros.
-#include "tl_common.h"
-
-#include <stdio.h>
-
-#include <algorithm>
+#include "tl_rows.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kVec = 4;                         // rays per lane and load on the aligned path
-constexpr int kChunk = kBlock * kVec;           // rays a block takes per step: the unit of the plan
-constexpr int kMaxY = 65535;                    // rows per launch
-constexpr int64_t kTargetBlocks = 2048;         // 256 CUs x 8 blocks of 4 waves
-constexpr int64_t kMaxDim = ((int64_t)1 << 31) - 1;
 constexpr int kMinN = 2, kMaxN = 6, kMaxJ = 27;
 constexpr double kPivotFloor = 9.313225746154785e-10;       // 2^-30 (ZFIT_PIVOT_FLOOR)
 
@@ -96,20 +84,6 @@ struct Rays {
     const float *px, *py;
     int64_t ps_f, ps_p, ps_w;
 };
-
-struct Plan { int nbx, R; };                    // blocks per row, steps of kChunk rays per block
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-Plan zfit_plan(int64_t rows, int64_t P)
-{
-    const int64_t chunks = cdiv(P, kChunk);
-    const int64_t want = std::max<int64_t>(1, cdiv(kTargetBlocks, rows));
-    const int64_t R = cdiv(chunks, std::min(chunks, want));
-    return {(int)cdiv(chunks, R), (int)R};
-}
-
-__device__ __forceinline__ bool aligned_to(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
 // accumulators and first moment of a part: 0 all, 1 the mu, 2 xi, eta, sum x^2, sum y^2
 constexpr int part_size(int N, int part) { return part == 0 ? n_mom(N) : part == 1 ? n_mu(N) : n_mom(N) - n_mu(N); }
@@ -189,35 +163,13 @@ __global__ __launch_bounds__(kBlock) void zfit_moments_kernel(Rays r, int64_t P,
             add_ray<N, PART>(m, x[o], y[o], px[po], py[po], ok[o]);
         }
     }
-    __shared__ double red[kBlock / 64][KP];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < KP; ++j) {
-        double v = m[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wv][j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < KP) {
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < kBlock / 64; ++i) s += red[i][threadIdx.x];
-        part[((int64_t)row * nbx + blockIdx.x) * n_mom(N) + part_base(N, PART) + threadIdx.x] = s;
-    }
+    block_partial(m, part, row, nbx, KP, n_mom(N), part_base(N, PART));
 }
 
-// moments[row][k] = the row's nbx partials added in order
 __global__ __launch_bounds__(kBlock) void zfit_reduce_kernel(const double *__restrict__ part, double *__restrict__ moments,
                                                              int64_t total, int nbx, int K)
 {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= total) return;
-    const int64_t row = i / K;
-    const double *p = part + row * nbx * K + (i - row * K);
-    double s = 0.0;
-    for (int b = 0; b < nbx; ++b) s += p[(int64_t)b * K];
-    moments[i] = s;
+    reduce_rows(part, moments, total, nbx, K);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the solve
@@ -461,23 +413,10 @@ __global__ __launch_bounds__(kBlock) void zfit_seed_kernel(Rays r, int64_t P, in
 }
 
 // ------------------------------------------------------------------------------------------------------------------- the host
-bool sizes_ok(int64_t F, int64_t P, int64_t W)
-{
-    return F >= 1 && P >= 1 && W >= 1 && F <= kMaxDim && W <= kMaxDim && F * W <= kMaxDim && P <= kMaxDim;
-}
-
-int refuse(const char *name, const char *what)
-{
-    static thread_local char msg[160];
-    snprintf(msg, sizeof msg, "%s: %s", name, what);
-    return tl_host::fail(TL_EINVAL, msg);
-}
-
 // the argument check the ray calls share; `name` opens the message
 int check_rays(const char *name, int64_t F, int64_t P, int64_t W, int order, const Rays &r, const void *table)
 {
-    if (F < 1 || P < 1 || W < 1) return refuse(name, "F, P and W must be at least 1");
-    if (!sizes_ok(F, P, W)) return refuse(name, "F W and P must stay below 2^31");
+    if (const char *what = size_fault(F, P, W)) return refuse(name, what);
     if (order < kMinN || order > kMaxN) return refuse(name, "the order must be 2 .. 6");
     if (!r.x || !r.y || !r.ok || !r.px || !r.py) return refuse(name, "x, y, ok, px and py are required");
     if (!table) return refuse(name, "the moments / coefficients pointer is NULL");
@@ -485,19 +424,19 @@ int check_rays(const char *name, int64_t F, int64_t P, int64_t W, int order, con
 }
 
 template <int N, int PART>
-void launch_moments(const Rays &r, int64_t P, int W, int row0, int ny, double *part, Plan pl, hipStream_t st)
+void launch_moments(dim3 grid, const Rays &r, int64_t P, int W, int row0, double *part, Plan pl, hipStream_t st)
 {
-    hipLaunchKernelGGL((zfit_moments_kernel<N, PART>), dim3(pl.nbx, ny), dim3(kBlock), 0, st, r, P, W, row0, part, pl.nbx, pl.R);
+    hipLaunchKernelGGL((zfit_moments_kernel<N, PART>), grid, dim3(kBlock), 0, st, r, P, W, row0, part, pl.nbx, pl.R);
 }
 
 template <int N>
-void launch_moments_of(const Rays &r, int64_t P, int W, int row0, int ny, double *part, Plan pl, hipStream_t st)
+void launch_moments_of(dim3 grid, const Rays &r, int64_t P, int W, int row0, double *part, Plan pl, hipStream_t st)
 {
     if constexpr (N >= 6) {                               // 110 accumulators in one kernel would leave one wave per SIMD: two launches
-        launch_moments<N, 1>(r, P, W, row0, ny, part, pl, st);
-        launch_moments<N, 2>(r, P, W, row0, ny, part, pl, st);
+        launch_moments<N, 1>(grid, r, P, W, row0, part, pl, st);
+        launch_moments<N, 2>(grid, r, P, W, row0, part, pl, st);
     } else {
-        launch_moments<N, 0>(r, P, W, row0, ny, part, pl, st);
+        launch_moments<N, 0>(grid, r, P, W, row0, part, pl, st);
     }
 }
 
@@ -516,33 +455,30 @@ extern "C" {
 
 size_t tl_zfit_workspace_bytes(int64_t F, int64_t P, int64_t W, int order)
 {
-    if (!sizes_ok(F, P, W) || order < kMinN || order > kMaxN) return 0;
-    return (size_t)(F * W) * (size_t)zfit_plan(F * W, P).nbx * n_mom(order) * sizeof(double);
+    if (size_fault(F, P, W) || order < kMinN || order > kMaxN) return 0;
+    return (size_t)(F * W) * (size_t)row_plan(F * W, P).nbx * n_mom(order) * sizeof(double);
 }
 
 int tl_zfit_moments(int32_t device, int64_t F, int64_t P, int64_t W, int order, const float *x, const float *y, const uint8_t *ok,
                     int64_t s_f, int64_t s_p, int64_t s_w, const float *px, const float *py, int64_t ps_f, int64_t ps_p,
                     int64_t ps_w, double *moments, void *workspace, size_t workspace_bytes, void *stream)
 {
+    static const char *name = "tl_zfit_moments";
     const Rays r = {x, y, ok, s_f, s_p, s_w, px, py, ps_f, ps_p, ps_w};
-    if (const int rc = check_rays("tl_zfit_moments", F, P, W, order, r, moments)) return rc;
-    if (!workspace || workspace_bytes < tl_zfit_workspace_bytes(F, P, W, order))
-        return tl_host::fail(TL_EWORKSPACE, "tl_zfit_moments: workspace NULL or below tl_zfit_workspace_bytes");
+    if (const int rc = check_rays(name, F, P, W, order, r, moments)) return rc;
+    if (const int rc = check_workspace(name, workspace, workspace_bytes, tl_zfit_workspace_bytes(F, P, W, order), "tl_zfit_workspace_bytes"))
+        return rc;
     if (const int rc = tl_host::use_device(device)) return rc;
     const int64_t rows = F * W;
-    const Plan pl = zfit_plan(rows, P);
+    const Plan pl = row_plan(rows, P);
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-#define CALL(N) launch_moments_of<N>(r, P, (int)W, (int)row0, ny, (double *)workspace, pl, st)
-        ZFIT_ORDERS(CALL)
+    if (const int rc = launch_rows(rows, pl.nbx, "zfit_moments_kernel launch", [&](dim3 grid, int row0) {
+#define CALL(N) launch_moments_of<N>(grid, r, P, (int)W, row0, (double *)workspace, pl, st)
+            ZFIT_ORDERS(CALL)
 #undef CALL
-        if (const int rc = tl_host::launched("zfit_moments_kernel launch")) return rc;
-    }
-    const int64_t total = rows * n_mom(order);
-    hipLaunchKernelGGL(zfit_reduce_kernel, dim3((unsigned)cdiv(total, kBlock)), dim3(kBlock), 0, st, (const double *)workspace,
-                       moments, total, pl.nbx, n_mom(order));
-    return tl_host::launched("zfit_reduce_kernel launch");
+        }))
+        return rc;
+    return launch_reduce(zfit_reduce_kernel, "zfit_reduce_kernel launch", (const double *)workspace, moments, rows, pl.nbx, n_mom(order), st);
 }
 
 int tl_zfit_solve(int32_t device, int64_t rows, int order, const double *moments, const double *g_a, const double *g_q, double *a,
@@ -581,16 +517,11 @@ int tl_zfit_seed(int32_t device, int64_t F, int64_t P, int64_t W, int order, con
     if (const int rc = check_rays("tl_zfit_seed", F, P, W, order, r, coef)) return rc;
     if (!gx && !gy) return refuse("tl_zfit_seed", "gx and gy are both NULL");
     if (const int rc = tl_host::use_device(device)) return rc;
-    const int64_t rows = F * W;
-    for (int64_t row0 = 0; row0 < rows; row0 += kMaxY) {
-        const int ny = (int)std::min<int64_t>(kMaxY, rows - row0);
-#define CALL(N) hipLaunchKernelGGL(zfit_seed_kernel<N>, dim3((unsigned)cdiv(P, kChunk), ny), dim3(kBlock), 0, (hipStream_t)stream, r, P, \
-                                   (int)W, (int)row0, coef, gx, gy)
+    return launch_rows(F * W, cdiv(P, kChunk), "zfit_seed_kernel launch", [&](dim3 grid, int row0) {
+#define CALL(N) hipLaunchKernelGGL(zfit_seed_kernel<N>, grid, dim3(kBlock), 0, (hipStream_t)stream, r, P, (int)W, row0, coef, gx, gy)
         ZFIT_ORDERS(CALL)
 #undef CALL
-        if (const int rc = tl_host::launched("zfit_seed_kernel launch")) return rc;
-    }
-    return TL_OK;
+    });
 }
 
 }  // extern "C"

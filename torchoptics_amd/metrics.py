@@ -235,13 +235,23 @@ class ThroughFocus(NamedTuple):
 FOCUS_SLOPE_FLOOR = 2.0 ** -40      # a centred slope sum at or below this share of its raw sum is rounding noise: no focus
 
 
-def _focus_uses_kernels(fused, tensors, where):
+def _uses_kernels(fused, tensors, n_float32, noun, where, what="tensors"):
+    """Whether the fused path is taken: the `noun` kernels apply where every tensor sits on one AMD GPU and the first n_float32
+    of them are float32; fused=True where they do not apply raises."""
     applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
-               and all(t.dtype == torch.float32 for t in tensors[:4]))
+               and all(t.dtype == torch.float32 for t in tensors[:n_float32]))
     if fused and not applies:
-        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the focus kernels run only "
-                           "on float32 tensors on one AMD GPU (there is no CPU fallback): use fused=False")
+        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the {noun} kernels run only "
+                           f"on float32 {what} on one AMD GPU (there is no CPU fallback): use fused=False")
     return applies if fused is None else bool(fused)
+
+
+def _rays_4d(where, *tensors):
+    """The tensors broadcast against each other (under autograd); they must come out [B, F, P, W]."""
+    tensors = torch.broadcast_tensors(*tensors)
+    if tensors[0].dim() != 4:
+        raise ValueError(f"{where} takes [B, F, P, W] tensors, got {tuple(tensors[0].shape)}")
+    return tensors
 
 
 def _focus_moments_torch(x, y, cx, cy, ray_ok):
@@ -268,10 +278,8 @@ def focus_moments(x, y, cx, cy, ray_ok, fused=None):
     `fused`: False -- these sums in torch ops, upcast to float64, on any device and float dtype; True -- the HIP kernels
     (ops.FocusMomentsFunction: float32 tensors on one AMD GPU, anything else raises); None -- the kernels where they apply.
     Either way every product and sum is in float64: the raw second moment of y is ~4e5 times the variance taken from it."""
-    use = _focus_uses_kernels(fused, (x, y, cx, cy, ray_ok), "focus_moments")
-    x, y, cx, cy, ray_ok = torch.broadcast_tensors(x, y, cx, cy, ray_ok)
-    if x.dim() != 4:
-        raise ValueError(f"focus_moments takes [B, F, P, W] tensors, got {tuple(x.shape)}")
+    use = _uses_kernels(fused, (x, y, cx, cy, ray_ok), 4, "focus", "focus_moments")
+    x, y, cx, cy, ray_ok = _rays_4d("focus_moments", x, y, cx, cy, ray_ok)
     if use:
         return ops.FocusMomentsFunction.apply(x, y, cx, cy, ray_ok)
     return _focus_moments_torch(x, y, cx, cy, ray_ok)
@@ -402,22 +410,6 @@ def _enclosed_torch(x, y, ray_ok, radii, inv_soft, shape, centre):
     return S, sums, c
 
 
-def _enclosed_uses_kernels(fused, tensors, where):
-    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
-               and all(t.dtype == torch.float32 for t in tensors[:2]))
-    if fused and not applies:
-        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the enclosed-energy kernels run "
-                           "only on float32 tensors on one AMD GPU (there is no CPU fallback): use fused=False")
-    return applies if fused is None else bool(fused)
-
-
-def _enclosed_rays(x, y, ray_ok, where):
-    x, y, ray_ok = torch.broadcast_tensors(x, y, ray_ok)
-    if x.dim() != 4:
-        raise ValueError(f"{where} takes [B, F, P, W] tensors, got {tuple(x.shape)}")
-    return x, y, ray_ok
-
-
 def enclosed_energy(x, y, ray_ok, radii, softness, shape="circle", common=("wavelength",), centre="row", fused=None):
     """Encircled (shape="circle") or ensquared ("square") energy of a traced fan: the share of the live rays inside a circle
     of radius R_k, or a square of half side R_k, about a centre, under a smooth edge of half width `softness`.
@@ -450,8 +442,8 @@ def enclosed_energy(x, y, ray_ok, radii, softness, shape="circle", common=("wave
         raise ValueError("common must be a subset of ('field', 'wavelength')")
     radii, inv = _enclosed_edge(radii, softness, shape)
     tensors = (x, y, ray_ok) + (() if isinstance(centre, str) else (centre,))
-    use = _enclosed_uses_kernels(fused, tensors, "enclosed_energy")
-    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "enclosed_energy")
+    use = _uses_kernels(fused, tensors, 2, "enclosed-energy", "enclosed_energy")
+    x, y, ray_ok = _rays_4d("enclosed_energy", x, y, ray_ok)
     if isinstance(centre, str) and centre not in ("row", "field"):
         raise ValueError("centre must be 'row', 'field' or a tensor broadcastable to [B, F, W, 2]")
     if use:
@@ -500,8 +492,8 @@ def spot_centroid(x, y, ray_ok, fused=None):
     """(n [B, F, W], centroid [B, F, W, 2]) of the live rays of every row (lens, field, wavelength), in the dtype of x: the
     per-wavelength centroids are the lateral colour through_focus does not give.  An empty row gets centroid 0.  Sums in
     float64; differentiable in x, y; `fused` as for enclosed_energy (tl_enclosed_centroid forward, tl_enclosed_seed backward)."""
-    use = _enclosed_uses_kernels(fused, (x, y, ray_ok), "spot_centroid")
-    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "spot_centroid")
+    use = _uses_kernels(fused, (x, y, ray_ok), 2, "enclosed-energy", "spot_centroid")
+    x, y, ray_ok = _rays_4d("spot_centroid", x, y, ray_ok)
     if use:
         S, _ = ops.EnclosedEnergyFunction.apply(x, y, ray_ok, "row", (), (), "circle")
     else:
@@ -567,22 +559,6 @@ def zernike_basis(max_order):
     return _ZBASIS[max_order]
 
 
-def _zfit_uses_kernels(fused, tensors, where):
-    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
-               and all(t.dtype == torch.float32 for t in tensors[:2]))
-    if fused and not applies:
-        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the Zernike-fit kernels run only "
-                           "on float32 rays on one AMD GPU (there is no CPU fallback): use fused=False")
-    return applies if fused is None else bool(fused)
-
-
-def _zfit_rays(x, y, ray_ok, px, py, where):
-    x, y, ray_ok, px, py = torch.broadcast_tensors(x, y, ray_ok, px, py)
-    if x.dim() != 4:
-        raise ValueError(f"{where} takes [B, F, P, W] tensors, got {tuple(x.shape)}")
-    return x, y, ray_ok, px, py
-
-
 def _zfit_powers(p, q, top):
     """p^k, q^k for k = 0 .. top as lists: p^0 = 1, p^k = p^(k-1) p."""
     pp, qq = [torch.ones_like(p)], [torch.ones_like(q)]
@@ -616,8 +592,8 @@ def zernike_moments(x, y, ray_ok, px, py, max_order=4, fused=None):
     p^0 = 1, p^k = p^(k-1) p, a term (p^a q^b) and then times x, all in float64.  A dead ray adds exactly 0 whatever it holds.
     An intermediate: it carries no gradient (zernike_fit does).  `fused` as for zernike_fit."""
     ops.zfit_sizes(max_order)
-    use = _zfit_uses_kernels(fused, (x, y, ray_ok, px, py), "zernike_moments")
-    x, y, ray_ok, px, py = _zfit_rays(x, y, ray_ok, px, py, "zernike_moments")
+    use = _uses_kernels(fused, (x, y, ray_ok, px, py), 2, "Zernike-fit", "zernike_moments", "rays")
+    x, y, ray_ok, px, py = _rays_4d("zernike_moments", x, y, ray_ok, px, py)
     if use:
         return ops.ZernikeFitFunction.apply(x, y, ray_ok, px, py, max_order)[0]
     return _zernike_moments_torch(x, y, ray_ok, px, py, max_order).detach()
@@ -695,8 +671,8 @@ def zernike_fit(x, y, ray_ok, px, py, max_order=4, scale=None, fused=None):
     monomial sums per row; None -- the kernels where they apply.  Either way every product and sum is in float64."""
     ops.zfit_sizes(max_order)
     tensors = (x, y, ray_ok, px, py) + ((scale,) if torch.is_tensor(scale) else ())
-    use = _zfit_uses_kernels(fused, tensors, "zernike_fit")
-    x, y, ray_ok, px, py = _zfit_rays(x, y, ray_ok, px, py, "zernike_fit")
+    use = _uses_kernels(fused, tensors, 2, "Zernike-fit", "zernike_fit", "rays")
+    x, y, ray_ok, px, py = _rays_4d("zernike_fit", x, y, ray_ok, px, py)
     if use:
         M, a, q, valid = ops.ZernikeFitFunction.apply(x, y, ray_ok, px, py, max_order)
         n, valid = M[..., 0], valid != 0
@@ -720,15 +696,6 @@ class GeometricMTF(NamedTuple):
     n: torch.Tensor                 # weighted live rays, [B, F, W] less the pooled dimension
     mtf: torch.Tensor               # modulus of the geometric OTF, [..., D, K]: directions x frequencies
     centre: torch.Tensor            # the origin every row's phase was measured from, [B, F, W, 2]
-
-
-def _mtf_uses_kernels(fused, tensors, where):
-    applies = (all(t.is_cuda and t.device == tensors[0].device for t in tensors)
-               and all(t.dtype == torch.float32 for t in tensors[:2]))
-    if fused and not applies:
-        raise RuntimeError(f"{where}(fused=True): x is {tensors[0].dtype} on {tensors[0].device}; the MTF kernels run "
-                           "only on float32 tensors on one AMD GPU (there is no CPU fallback): use fused=False")
-    return applies if fused is None else bool(fused)
 
 
 def _mtf_vectors(frequencies, directions):
@@ -797,8 +764,8 @@ def otf_sums(x, y, ray_ok, origin, nu_x, nu_y, fused=None):
     nu_x, nu_y = tuple(float(v) for v in nu_x), tuple(float(v) for v in nu_y)
     if not nu_x or len(nu_x) != len(nu_y) or not all(math.isfinite(v) for v in nu_x + nu_y):
         raise ValueError("nu_x and nu_y must hold the same number (at least one) of finite floats")
-    use = _mtf_uses_kernels(fused, (x, y, ray_ok, origin), "otf_sums")
-    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "otf_sums")
+    use = _uses_kernels(fused, (x, y, ray_ok, origin), 2, "MTF", "otf_sums")
+    x, y, ray_ok = _rays_4d("otf_sums", x, y, ray_ok)
     B, F, _, W = x.shape
     origin = origin.detach().to(torch.float64).expand(B, F, W, 2)
     if not use:
@@ -864,8 +831,8 @@ def geometric_mtf(x, y, ray_ok, frequencies, directions=("tangential", "sagittal
         if centre == "row" and pooled:
             raise ValueError("centre='row' gives every wavelength its own origin: pooled rows need one (centre='field' or a tensor)")
     tensors = (x, y, ray_ok) + (() if isinstance(centre, str) else (centre,))
-    use = _mtf_uses_kernels(fused, tensors, "geometric_mtf")
-    x, y, ray_ok = _enclosed_rays(x, y, ray_ok, "geometric_mtf")
+    use = _uses_kernels(fused, tensors, 2, "MTF", "geometric_mtf")
+    x, y, ray_ok = _rays_4d("geometric_mtf", x, y, ray_ok)
     B, F, _, W = x.shape
     a = (1.0,) * W if weights is None else tuple(float(v) for v in weights)
     if len(a) != W or not all(0.0 <= v < float("inf") for v in a) or not any(v > 0.0 for v in a):

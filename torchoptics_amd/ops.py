@@ -546,6 +546,37 @@ def _focus_layout(tensors):
     return (F * W * P, W * P, 1, P)
 
 
+def _row_rays(rays, ok, noun, what="tensors"):
+    """The float32 ray tensors `rays` (name -> tensor, all of ONE shape [B,F,P,W]) and `ok` as the row kernels read them:
+    (the tensors placed, oks, st, s_f) -- all at the one stride quadruple st of _focus_layout (only what is expanded or strided
+    differently is copied), ok as uint8, and s_f the field stride once B is folded into F.  The device and dtype checks of the
+    rays come first and raise before anything is copied; a caller's further argument checks (MTFSumsFunction: J and origin,
+    ZernikeFitFunction: the devices of px, py) run after the copies, in the order and with the texts they always had, so only an
+    error path does work it then throws away."""
+    for name, t in rays.items():
+        _require_device(t, name)
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"torchoptics_amd: the {noun} kernels take float32 {what}; `{name}` is {t.dtype} "
+                               "(there is no CPU fallback and no fp64 kernel: use fused=False)")
+    _require_device(ok, "ray_ok")
+    tensors = tuple(rays.values())
+    dev, shape = tensors[0].device, tensors[0].shape
+    st = _focus_layout(tensors)
+
+    def placed(t):
+        return t if _same_layout(t, shape, st) else torch.empty_strided(shape, st, dtype=t.dtype, device=dev).copy_(t)
+    tensors = [placed(t) for t in tensors]
+    oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
+    s_f = st[1] if shape[0] == 1 else st[0] if shape[1] == 1 else st[1]
+    return tensors, oks, st, s_f
+
+
+def _ray_grads(ctx, n, like, st):
+    """The seeds of the first n inputs, laid out as the rays `like` are: None where needs_input_grad says so."""
+    return [torch.empty_strided(like.shape, st, dtype=torch.float32, device=like.device) if need else None
+            for need in ctx.needs_input_grad[:n]]
+
+
 class FocusMomentsFunction(torch.autograd.Function):
     """moments [B, F, W, FOCUS_NMOM] (float64) of per-ray tensors x, y, cx, cy, ok, all of ONE shape [B, F, P, W] (the caller
     broadcasts, under autograd): tl_focus_moments forward, tl_focus_seed backward.  The five arrays are brought to one common
@@ -554,22 +585,9 @@ class FocusMomentsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, cx, cy, ok):
-        rays = {"x": x, "y": y, "cx": cx, "cy": cy}
-        for name, t in rays.items():
-            _require_device(t, name)
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"torchoptics_amd: the focus kernels take float32 tensors; `{name}` is {t.dtype} "
-                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
-        _require_device(ok, "ray_ok")
-        dev, shape = x.device, x.shape
-        B, F, P, W = shape
-        st = _focus_layout((x, y, cx, cy))
-
-        def placed(t):
-            return t if _same_layout(t, shape, st) else torch.empty_strided(shape, st, dtype=t.dtype, device=dev).copy_(t)
-        x, y, cx, cy = (placed(t) for t in (x, y, cx, cy))
-        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
-        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
+        (x, y, cx, cy), oks, st, s_f = _row_rays({"x": x, "y": y, "cx": cx, "cy": cy}, ok, "focus")
+        dev = x.device
+        B, F, P, W = x.shape
         moments = torch.empty((B, F, W, FOCUS_NMOM), dtype=torch.float64, device=dev)
         ws = _workspace(_lib.lib().tl_focus_workspace_bytes(B * F, P, W), dev)
         _call("tl_focus_moments", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], moments, ws, ws.numel(),
@@ -585,8 +603,7 @@ class FocusMomentsFunction(torch.autograd.Function):
         B, F, P, W = shape
         st, s_f = ctx.layout
         gm = gmom.to(torch.float64).contiguous()
-        outs = [torch.empty_strided(shape, st, dtype=torch.float32, device=dev) if need else None
-                for need in ctx.needs_input_grad[:4]]
+        outs = _ray_grads(ctx, 4, x, st)
         if all(o is None for o in outs):
             return (None,) * 5
         _call("tl_focus_seed", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], gm, *outs,
@@ -618,22 +635,10 @@ class EnclosedEnergyFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, ok, centre, radii, inv_soft, shape):
-        for name, t in (("x", x), ("y", y)):
-            _require_device(t, name)
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"torchoptics_amd: the enclosed-energy kernels take float32 tensors; `{name}` is {t.dtype} "
-                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
-        _require_device(ok, "ray_ok")
-        dev, full = x.device, x.shape
-        B, F, P, W = full
+        (x, y), oks, st, s_f = _row_rays({"x": x, "y": y}, ok, "enclosed-energy")
+        dev = x.device
+        B, F, P, W = x.shape
         K = len(radii)
-        st = _focus_layout((x, y))
-
-        def placed(t):
-            return t if _same_layout(t, full, st) else torch.empty_strided(full, st, dtype=t.dtype, device=dev).copy_(t)
-        x, y = placed(x), placed(y)
-        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
-        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
         rays = (dev.index, B * F, P, W, x, y, oks, s_f, st[2], st[3])
         # (no radii: S alone, metrics.spot_centroid; the seed call then runs on one radius whose seed is 0)
         edge = (_host_doubles(radii or (1.0,)), _host_doubles(inv_soft or (1.0,)), max(K, 1), ENCLOSED_SHAPES[shape])
@@ -665,7 +670,7 @@ class EnclosedEnergyFunction(torch.autograd.Function):
         else:
             gs = torch.empty((B, F, W, 1), dtype=torch.float64, device=dev).zero_()
         g_lin = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev).copy_(g_S[..., 1:3])
-        outs = [torch.empty_strided(full, st, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2]]
+        outs = _ray_grads(ctx, 2, x, st)
         ws = _workspace(_lib.lib().tl_enclosed_workspace_bytes(B * F, P, W, edge[2]), dev)
         g_centre = None
         if isinstance(centre, str):
@@ -703,12 +708,7 @@ class MTFSumsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, ok, origin, nu_x, nu_y):
-        for name, t in (("x", x), ("y", y)):
-            _require_device(t, name)
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"torchoptics_amd: the MTF kernels take float32 tensors; `{name}` is {t.dtype} "
-                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
-        _require_device(ok, "ray_ok")
+        (x, y), oks, st, s_f = _row_rays({"x": x, "y": y}, ok, "MTF")
         _require_device(origin, "origin")
         dev, full = x.device, x.shape
         B, F, P, W = full
@@ -717,16 +717,9 @@ class MTFSumsFunction(torch.autograd.Function):
             raise ValueError(f"nu_x and nu_y must hold the same 1 .. {MTF_MAX_J} frequencies, got {J} and {len(nu_y)}")
         if origin.dtype != torch.float64 or tuple(origin.shape) != (B, F, W, 2):
             raise ValueError(f"origin must be a float64 tensor [B, F, W, 2] = {(B, F, W, 2)}, got {origin.dtype} {tuple(origin.shape)}")
-        st = _focus_layout((x, y))
-
-        def placed(t):
-            return t if _same_layout(t, full, st) else torch.empty_strided(full, st, dtype=t.dtype, device=dev).copy_(t)
-        x, y = placed(x), placed(y)
-        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
         o64 = origin.detach()
         if not o64.is_contiguous():
             o64 = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev).copy_(o64)
-        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
         sums = torch.empty((B, F, W, J, 2), dtype=torch.float64, device=dev)
         ctx.save_for_backward(x, y, oks, o64)
         ctx.plan = (st, s_f, (_host_doubles(nu_x), _host_doubles(nu_y), J))
@@ -743,7 +736,7 @@ class MTFSumsFunction(torch.autograd.Function):
         dev, full = x.device, x.shape
         B, F, P, W = full
         st, s_f, freq = ctx.plan
-        outs = [torch.empty_strided(full, st, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2]]
+        outs = _ray_grads(ctx, 2, x, st)
         if all(o is None for o in outs) or x.numel() == 0:
             return (*outs, None, None, None, None)
         gs = torch.empty(g_sums.shape, dtype=torch.float64, device=dev).copy_(g_sums)
@@ -791,22 +784,11 @@ class ZernikeFitFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, ok, px, py, order):
         J, K = zfit_sizes(order)
-        for name, t in (("x", x), ("y", y)):
-            _require_device(t, name)
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"torchoptics_amd: the Zernike-fit kernels take float32 rays; `{name}` is {t.dtype} "
-                                   "(there is no CPU fallback and no fp64 kernel: use fused=False)")
-        for name, t in (("ray_ok", ok), ("px", px), ("py", py)):
+        (x, y), oks, st, s_f = _row_rays({"x": x, "y": y}, ok, "Zernike-fit", "rays")
+        for name, t in (("px", px), ("py", py)):
             _require_device(t, name)
         dev, shape = x.device, x.shape
         B, F, P, W = shape
-        st = _focus_layout((x, y))
-
-        def placed(t):
-            return t if _same_layout(t, shape, st) else torch.empty_strided(shape, st, dtype=t.dtype, device=dev).copy_(t)
-        x, y = placed(x), placed(y)
-        oks = placed(ok.view(torch.uint8) if ok.dtype == torch.bool else ok if ok.dtype == torch.uint8 else (ok != 0).view(torch.uint8))
-        s_f = st[1] if B == 1 else st[0] if F == 1 else st[1]
         px, py, pst = _pupil_layout(px, py, shape, dev)
         rays = (dev.index, B * F, P, W, order, x, y, oks, s_f, st[2], st[3], px, py, *pst)
         moments = torch.empty((B, F, W, K), dtype=torch.float64, device=dev)
@@ -829,7 +811,7 @@ class ZernikeFitFunction(torch.autograd.Function):
         B, F, P, W = shape
         order, st, s_f, pst = ctx.plan
         J, _ = zfit_sizes(order)
-        outs = [torch.empty_strided(shape, st, dtype=torch.float32, device=dev) if need else None for need in ctx.needs_input_grad[:2]]
+        outs = _ray_grads(ctx, 2, x, st)
         if all(o is None for o in outs):
             return (None,) * 6
         ga = torch.empty((B, F, W, J), dtype=torch.float64, device=dev).copy_(g_a)
