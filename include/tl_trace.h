@@ -9,7 +9,8 @@
  * distortion map and multiplies the relative illumination in.  tl_focus_* sums the through-focus
  * moments of a traced fan (best focus, tangential / sagittal foci, axial colour), tl_enclosed_* its
  * encircled / ensquared energy under a smooth edge, tl_zfit_* fits Zernike wavefront coefficients
- * to its transverse ray errors, tl_mtf_* sums its geometric OTF at given spatial frequencies.
+ * to its transverse ray errors, tl_mtf_* sums its geometric OTF at given spatial frequencies, tl_tfmtf_* the
+ * same at equally spaced focal planes from one pass over the rays.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer unless marked "host";
@@ -852,6 +853,54 @@ int tl_mtf_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *x,
                 int64_t s_p, int64_t s_w, const double *origin /* [F,W,2] */, const double *nu_x /* host, J */,
                 const double *nu_y /* host, J */, int J, const double *g_sums /* [F,W,J,2] */, float *gx, float *gy,
                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Through-focus geometric OTF (extension; metrics.otf_sums_through_focus / metrics.through_focus_mtf stand on them): the Fourier
+ * sums of tl_mtf_sums at Z equally spaced focal planes from ONE pass over the traced rays.  Behind the last surface a ray is a
+ * line, so its phase at the plane shifted by d is a + d b, and over equally spaced planes exp(2 pi i (a + d_z b)) is a geometric
+ * sequence: one term and one rotor per ray and frequency vector, then one complex multiplication per further plane.
+ *
+ * x, y, cx, cy (float) and ok (bytes) are [F, P, W] tensors that share ONE stride triple s_f, s_p, s_w (elements).  A ray is LIVE
+ * iff ok != 0 and s = 1 - cx^2 - cy^2 > 0 (tl_focus_moments' rule, in fp64); a dead ray is excluded by a select: it adds +0.0 to
+ * every sum and gets exactly 0 gradient whatever it holds.  origin[f, w, 0..1] (device doubles, contiguous) is a constant, as for
+ * tl_mtf_sums.  nu_x, nu_y are HOST arrays of J <= 16 doubles; shift_first = d0 and shift_step = dd are host doubles and Z <= 16
+ * the number of planes, plane z at d0 + z dd (Z = 1 ignores the step).  All of them travel by value in the kernel argument:
+ * nothing is uploaded, no call synchronises.  Per row over the live rays, every operation in fp64 from the fp32 inputs, uncontracted:
+ *   cz = sqrt(s),  u = cx / cz,  v = cy / cz,  dx = (double)x - o_x,  dy = (double)y - o_y
+ *   a  = nu_x dx + nu_y dy  (cycles),   b = nu_x u + nu_y v  (cycles per unit of shift)
+ *   p0 = a + d0 b,  r0 = p0 - rint(p0),  (c_0, s_0) = sincospi(2 r0)         plane 0
+ *   q  = dd b,      rq = q - rint(q),    (cr, sr)   = sincospi(2 rq)         the rotor
+ *   (c_z, s_z) = (c_{z-1} cr - s_{z-1} sr,  s_{z-1} cr + c_{z-1} sr),  z = 1 .. Z - 1
+ *   sums[f, w, j, z, 0] = C_jz = sum c_z,   sums[f, w, j, z, 1] = S_jz = sum s_z;   OTF = (C - i S) / n,  MTF = sqrt(C^2 + S^2) / n.
+ * nu = 0 gives a = b = 0 and the term (1, 0) at every plane exactly: C = n, S = 0 without a rounding.
+ * BITS.  (i) A (vector, plane) column's bits depend only on the row's rays, its origin, nu_j, shift_first, shift_step and z: not
+ * on J, Z, the register bucket of the launch or the other columns of the call.  (ii) With shift_first = 0 plane 0 has the bits of
+ * tl_mtf_sums on the same x, y, ok and origin wherever the two live rules agree.  (iii) No atomics: the same bytes on every run,
+ * whatever the buffers held before.  Layout handling, launch plan and limits are tl_mtf_sums'; a launch holds JB x ZB columns
+ * in registers, the powers of two that hold J and Z with JB ZB <= 32; a call of more vectors goes in several launches back to
+ * back, each reading the rays again.
+ *
+ * tl_tfmtf_seed: for the seeds g_sums[f, w, j, z, 0..1] = (gC, gS)_jz, with Q_jz = gS_jz c_z - gC_jz s_z:
+ *   gx = 2 pi sum_j nu_xj sum_z Q_jz,   gu = 2 pi sum_j nu_xj sum_z (d0 + z dd) Q_jz,   gy, gv likewise with nu_y,
+ *   gcx = (gu (1 - cy^2) + gv cx cy) / cz^3,   gcy = (gu cx cy + gv (1 - cx^2)) / cz^3,
+ * the sums in fp64 in the order j, then z, rounded once to float and written with the inputs' strides into gx, gy, gcx, gcy (any
+ * may be NULL, not all); dead rays get zeros.  It reduces nothing and leaves the workspace untouched; the workspace is checked as
+ * for tl_tfmtf_sums so that one allocation serves both calls.
+ *
+ * TL_EINVAL before any HIP call, with the function's name in the message: a required pointer NULL, F, P or W below 1, F W or P at
+ * or above 2^31, J or Z outside 1..16, a frequency or a shift not finite, all outputs of the seed NULL.  TL_EWORKSPACE: workspace
+ * NULL or below tl_tfmtf_workspace_bytes(F, P, W, J, Z) (0 for arguments that are refused).
+ */
+size_t tl_tfmtf_workspace_bytes(int64_t F, int64_t P, int64_t W, int J, int Z);
+int tl_tfmtf_sums(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const float *cx, const float *cy,
+                  const uint8_t *ok, int64_t s_f, int64_t s_p, int64_t s_w, const double *origin /* [F,W,2] */,
+                  const double *nu_x /* host, J */, const double *nu_y /* host, J */, int J, double shift_first, double shift_step,
+                  int Z, double *sums /* [F,W,J,Z,2] */, void *workspace, size_t workspace_bytes, void *stream);
+int tl_tfmtf_seed(int32_t device, int64_t F, int64_t P, int64_t W, const float *x, const float *y, const float *cx, const float *cy,
+                  const uint8_t *ok, int64_t s_f, int64_t s_p, int64_t s_w, const double *origin /* [F,W,2] */,
+                  const double *nu_x /* host, J */, const double *nu_y /* host, J */, int J, double shift_first, double shift_step,
+                  int Z, const double *g_sums /* [F,W,J,Z,2] */, float *gx, float *gy, float *gcx, float *gcy, void *workspace,
+                  size_t workspace_bytes, void *stream);
 
 /*
  * Diagnostic: quot[i] = a[i] / b[i] and root[i] = sqrt(b[i]) evaluated by the division and square root the trace kernels of

@@ -194,6 +194,14 @@ _SIGNATURES = {
     # ... | origin | nu_x, nu_y, J | g_sums | gx, gy | workspace, bytes | stream
     "tl_mtf_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 3 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int] + [_VP]
                     + [_VP] * 2 + _WS),
+    "tl_tfmtf_workspace_bytes": (C.c_size_t, [C.c_int64] * 3 + [C.c_int] * 2),
+    # device, F, P, W | x, y, cx, cy, ok | s_f, s_p, s_w | origin | nu_x, nu_y (host doubles), J | shift_first, shift_step, Z | sums
+    # | workspace, bytes | stream
+    "tl_tfmtf_sums": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 5 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int]
+                      + [C.c_double, C.c_double, C.c_int] + [_VP] + _WS),
+    # ... | shift_first, shift_step, Z | g_sums | gx, gy, gcx, gcy | workspace, bytes | stream
+    "tl_tfmtf_seed": (C.c_int, [C.c_int32] + [C.c_int64] * 3 + [_VP] * 5 + [C.c_int64] * 3 + [_VP] + [_VP, _VP, C.c_int]
+                      + [C.c_double, C.c_double, C.c_int] + [_VP] + [_VP] * 4 + _WS),
 }
 EXPORTS = tuple(_SIGNATURES)
 

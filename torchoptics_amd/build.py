@@ -48,13 +48,18 @@ UNITS = {
     "tl_enclosed.hip": [],     # the encircled / ensquared energy of a traced fan (fp64 sums under a smooth edge) and its seeds
     "tl_zfit.hip": [],         # the Zernike wavefront fit of a traced fan from its ray errors (fp64 moments, solve, seeds)
     "tl_mtf.hip": [],          # the geometric OTF of a traced fan (fp64 Fourier sums over the spot at given frequencies) and its seeds
+    "tl_tfmtf.hip": [],        # the same OTF at equally spaced focal planes from one pass over the rays (a rotor per ray) and its seeds
 }
 # -mllvm options of COMMON a unit is compiled WITHOUT.  tl_zfit.hip: under the iterative-ilp scheduler this compiler's greedy
 # register allocator crashes (a segmentation fault in VirtRegAuxInfo::isRematerializable) on the moment kernels with 29 and more
 # fp64 accumulators; the default scheduler compiles them without scratch (profiles/zfit_kernel_resources.txt).
 # tl_mtf.hip: the same crash of the compiler under iterative-ilp, on mtf_sums_kernel (8 to 32 fp64 accumulators around an inlined
 # sincospi); the default scheduler gives 62 / 78 / 110 VGPRs and no scratch (profiles/mtf_kernel_resources.txt).
-WITHOUT = {"tl_zfit.hip": ("-amdgpu-sched-strategy=iterative-ilp",), "tl_mtf.hip": ("-amdgpu-sched-strategy=iterative-ilp",)}
+# tl_tfmtf.hip: the same crash under iterative-ilp, on tfmtf_sums_kernel<8, 2> of the 19 buckets (32 fp64 accumulators around two
+# inlined sincospi per vector); the buckets that do compile under it take more registers than under the default scheduler
+# (<16, 2> 200 against 190 VGPRs, the seed kernel 229 and 22 spilled SGPRs against 196 and 8), which compiles every bucket
+# without scratch (profiles/tfmtf_kernel_resources.txt).
+WITHOUT = {unit: ("-amdgpu-sched-strategy=iterative-ilp",) for unit in ("tl_zfit.hip", "tl_mtf.hip", "tl_tfmtf.hip")}
 DEPS = ["tl_kernels.inc", "tl_common.h", "tl_rows.h", os.path.join("..", "..", "include", "tl_trace.h")]
 
 

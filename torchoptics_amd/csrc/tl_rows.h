@@ -1,5 +1,5 @@
-// tl_rows.h -- the row frame of the spot merits: tl_focus.hip, tl_enclosed.hip, tl_zfit.hip and tl_mtf.hip include it, nothing
-// else does.  Each of them sums per-ray terms over the rays of a ROW (one field f and wavelength w of the F x W the call holds)
+// tl_rows.h -- the row frame of the spot merits: tl_focus.hip, tl_enclosed.hip, tl_zfit.hip, tl_mtf.hip and tl_tfmtf.hip include
+// it, nothing else does.  Each of them sums per-ray terms over the rays of a ROW (one field f and wavelength w of the F x W the call holds)
 // in fp64; what a ray's terms are is the unit's, everything around them is defined here, once.
 //
 // LAYOUT AND PLAN.  A ray array is read at f s_f + i s_p + w s_w (elements).  Grid (nbx, rows of this launch), 256 lanes; rows
@@ -93,6 +93,63 @@ __device__ __forceinline__ void walk_rays(const float *__restrict__ x, const flo
     }
 }
 
+// the same for a unit that reads the direction cosines too: Rays {x, y, cx, cy, ok, s_f, s_p, s_w, ..}
+struct RowBase5 {
+    const float *x, *y, *cx, *cy;
+    const uint8_t *ok;
+    int64_t off;
+    int row;
+};
+
+template <class Rays>
+__device__ __forceinline__ RowBase5 row_base5(const Rays &r, int W, int row0)
+{
+    const int row = row0 + (int)blockIdx.y;
+    const int f = row / W, w = row - f * W;
+    const int64_t off = f * r.s_f + w * r.s_w;
+    return {r.x + off, r.y + off, r.cx + off, r.cy + off, r.ok + off, off, row};
+}
+
+// whether the row's five bases take the 16-byte path (s_p == 1 is the caller's to add)
+__device__ __forceinline__ bool aligned_row(const RowBase5 &b)
+{
+    return aligned_to(b.x, 16) && aligned_to(b.y, 16) && aligned_to(b.cx, 16) && aligned_to(b.cy, 16) && aligned_to(b.ok, 4);
+}
+
+// walk_rays over five arrays: body(o, xs, ys, cxs, cys, oks), the same rays to the same lanes in the same order
+template <class Body>
+__device__ __forceinline__ void walk_rays5(const RowBase5 &b, int64_t s_p, bool vec, int64_t first, int64_t last, int64_t P, Body &&body)
+{
+    const float *__restrict__ x = b.x, *__restrict__ y = b.y, *__restrict__ cx = b.cx, *__restrict__ cy = b.cy;
+    const uint8_t *__restrict__ ok = b.ok;
+    if (vec) {                                              // (uniform over the block)
+        for (int64_t ip = first + kVec * (int64_t)threadIdx.x; ip < last; ip += kChunk) {
+            if (ip + kVec <= P) {
+                const float4 x4 = *reinterpret_cast<const float4 *>(x + ip), y4 = *reinterpret_cast<const float4 *>(y + ip);
+                const float4 c4 = *reinterpret_cast<const float4 *>(cx + ip), d4 = *reinterpret_cast<const float4 *>(cy + ip);
+                const unsigned o4 = *reinterpret_cast<const unsigned *>(ok + ip);
+                const float xs[kVec] = {x4.x, x4.y, x4.z, x4.w}, ys[kVec] = {y4.x, y4.y, y4.z, y4.w};
+                const float cxs[kVec] = {c4.x, c4.y, c4.z, c4.w}, cys[kVec] = {d4.x, d4.y, d4.z, d4.w};
+                const unsigned oks[kVec] = {o4 & 0xffu, o4 & 0xff00u, o4 & 0xff0000u, o4 & 0xff000000u};
+                body(ip, xs, ys, cxs, cys, oks);
+            } else {                                        // the last one to three rays of the row
+                for (int64_t q = ip; q < P; ++q) {
+                    const float xs[1] = {x[q]}, ys[1] = {y[q]}, cxs[1] = {cx[q]}, cys[1] = {cy[q]};
+                    const unsigned oks[1] = {ok[q]};
+                    body(q, xs, ys, cxs, cys, oks);
+                }
+            }
+        }
+    } else {
+        for (int64_t ip = first + threadIdx.x; ip < last; ip += kBlock) {
+            const int64_t o = ip * s_p;
+            const float xs[1] = {x[o]}, ys[1] = {y[o]}, cxs[1] = {cx[o]}, cys[1] = {cy[o]};
+            const unsigned oks[1] = {ok[o]};
+            body(o, xs, ys, cxs, cys, oks);
+        }
+    }
+}
+
 // part[(row nbx + bx) stride + base + j] = the block's sum of m[j], j < n <= N: a butterfly over the wave, the four waves in
 // order.  stride: the doubles a block's partial holds, of which this call stores n from `base` on.
 template <int N>
@@ -133,6 +190,16 @@ __device__ __forceinline__ void reduce_rows(const double *__restrict__ part, dou
     double s = 0.0;
     for (int b = 0; b < nbx; ++b) s += p[(int64_t)b * n];
     out[i] = s;
+}
+
+// the same ordered sum for one slot of partials that hold `stride` doubles per block (a unit whose output is not laid out as its
+// partials are maps an output element to its slot and calls this)
+__device__ __forceinline__ double reduce_slot(const double *__restrict__ part, int64_t row, int nbx, int stride, int slot)
+{
+    const double *p = part + row * nbx * stride + slot;
+    double s = 0.0;
+    for (int b = 0; b < nbx; ++b) s += p[(int64_t)b * stride];
+    return s;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the host

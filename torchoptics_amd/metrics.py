@@ -742,13 +742,7 @@ def _otf_sums_torch(x, y, ray_ok, origin, nu_x, nu_y):
     nx, ny = const_tensor(nu_x, torch.float64, x.device), const_tensor(nu_y, torch.float64, x.device)   # cached: no upload per call
     u = nx * dx[..., None] + ny * dy[..., None]             # cycles, [B, F, P, W, J]
     r = u - torch.round(u)                                  # (round: to nearest even, rint's; its derivative is 0)
-    # sincospi(2 r) as the device library forms it: quarter turns taken off exactly, pi multiplies only into |t| <= 1 / 8, so
-    # that r = 0, 1 / 4, 1 / 2 give (1, 0), (0, 1), (-1, 0) without a rounding (two rays half a period apart cancel exactly)
-    k = torch.round(4.0 * r)
-    phi = (2.0 * math.pi) * (r - 0.25 * k)
-    c0, s0, k = torch.cos(phi), torch.sin(phi), torch.remainder(k, 4.0)
-    cos = torch.where(k == 0, c0, torch.where(k == 1, -s0, torch.where(k == 2, -c0, s0)))
-    sin = torch.where(k == 0, s0, torch.where(k == 1, c0, torch.where(k == 2, -s0, -c0)))
+    cos, sin = _sincos_turns(r)                             # (two rays half a period apart cancel exactly)
     keep = live[..., None]
     return torch.stack([torch.where(keep, cos, zero).sum(dim=2), torch.where(keep, sin, zero).sum(dim=2)], dim=-1)
 
@@ -818,43 +812,256 @@ def geometric_mtf(x, y, ray_ok, frequencies, directions=("tangential", "sagittal
     read the rays again); None -- the kernels where they apply.  The finish (weights, pooling, modulus, division, the zero
     rules) is plain float64 torch on tiny tensors either way.  No host synchronisation.  Designers multiply the curve by
     diffraction_limit_mtf; this function does not."""
+    pooled = _mtf_pooled(common, centre)
+    nu_x, nu_y, D, K = _mtf_vectors(frequencies, directions)
+    tensors = (x, y, ray_ok) + (() if isinstance(centre, str) else (centre,))
+    use = _uses_kernels(fused, tensors, 2, "MTF", "geometric_mtf")
+    x, y, ray_ok = _rays_4d("geometric_mtf", x, y, ray_ok)
+    a = _mtf_weights(weights, x.shape[3])
+    S = _spot_sums(x, y, ray_ok, use)
+    origin = _mtf_origin(S, centre, pooled)
+    sums = otf_sums(x, y, ray_ok, origin, nu_x, nu_y, fused=use)
+    n, mtf = _mtf_finish(sums, S[..., 0], a, pooled)
+    return GeometricMTF(n.detach().to(x.dtype), mtf.reshape(*mtf.shape[:-1], D, K).to(x.dtype), origin.to(x.dtype))
+
+
+def _mtf_pooled(common, centre):
+    """Whether the rows are pooled over the wavelengths; what geometric_mtf refuses of `common` and a named `centre` raises."""
     common = tuple(common)
     if "field" in common:
         raise ValueError("common must not hold 'field': rows at different image points have no common OTF")
     if any(c != "wavelength" for c in common):
         raise ValueError("common must be a subset of ('wavelength',)")
     pooled = bool(common)
-    nu_x, nu_y, D, K = _mtf_vectors(frequencies, directions)
     if isinstance(centre, str):
         if centre not in ("row", "field"):
             raise ValueError("centre must be 'row', 'field' or a tensor broadcastable to [B, F, W, 2]")
         if centre == "row" and pooled:
             raise ValueError("centre='row' gives every wavelength its own origin: pooled rows need one (centre='field' or a tensor)")
-    tensors = (x, y, ray_ok) + (() if isinstance(centre, str) else (centre,))
-    use = _uses_kernels(fused, tensors, 2, "MTF", "geometric_mtf")
-    x, y, ray_ok = _rays_4d("geometric_mtf", x, y, ray_ok)
-    B, F, _, W = x.shape
+    return pooled
+
+
+def _mtf_weights(weights, W):
     a = (1.0,) * W if weights is None else tuple(float(v) for v in weights)
     if len(a) != W or not all(0.0 <= v < float("inf") for v in a) or not any(v > 0.0 for v in a):
         raise ValueError(f"weights must be {W} finite floats >= 0 (one per wavelength), not all 0")
-    S = _spot_sums(x, y, ray_ok, use)
+    return a
+
+
+def _mtf_origin(S, centre, pooled):
+    """The origin [B, F, W, 2] (float64, detached) of S [B, F, W, 3] = (n, sum x, sum y): a named centre rounded to float32 and
+    widened again, or the given tensor."""
+    B, F, W = S.shape[:3]
     if isinstance(centre, str):
-        origin = _enclosed_centre(S, centre).to(torch.float32).to(torch.float64)
-    else:
-        shape = (1,) * (4 - centre.dim()) + tuple(centre.shape)
-        if centre.dim() > 4 or (pooled and shape[2] != 1):
-            raise ValueError("with pooling the centre must not depend on the wavelength: broadcastable from [B, F, 1, 2]")
-        origin = centre.detach().to(torch.float64).expand(B, F, W, 2)
-    sums = otf_sums(x, y, ray_ok, origin, nu_x, nu_y, fused=use)
-    a = const_tensor(a, torch.float64, x.device)
-    sums, n = sums * a[:, None, None], S[..., 0] * a
+        return _enclosed_centre(S, centre).to(torch.float32).to(torch.float64)
+    shape = (1,) * (4 - centre.dim()) + tuple(centre.shape)
+    if centre.dim() > 4 or (pooled and shape[2] != 1):
+        raise ValueError("with pooling the centre must not depend on the wavelength: broadcastable from [B, F, 1, 2]")
+    return centre.detach().to(torch.float64).expand(B, F, W, 2)
+
+
+def _mtf_finish(sums, n, a, pooled):
+    """(n, mtf) of sums [B, F, W, .., 2] and the live counts n [B, F, W]: the weights a (W floats), pooling over the wavelengths,
+    modulus, division and the zero rules, in float64; n and mtf lose the wavelength dimension when pooled."""
+    a = const_tensor(a, torch.float64, sums.device)
+    sums, n = sums * a.reshape(-1, *(1,) * (sums.dim() - 3)), n * a
     if pooled:
         sums, n = sums.sum(dim=2), n.sum(dim=2)
     m2 = sums[..., 0] * sums[..., 0] + sums[..., 1] * sums[..., 1]
-    some, lit = m2 > 0, (n > 0)[..., None]
+    some, lit = m2 > 0, (n > 0).reshape(*n.shape, *(1,) * (m2.dim() - n.dim()))
+    n1 = n.reshape(lit.shape)
     modulus = torch.where(some, torch.sqrt(torch.where(some, m2, torch.ones_like(m2))), torch.zeros_like(m2))
-    mtf = torch.where(lit, modulus / torch.where(lit, n[..., None], torch.ones_like(m2)), torch.zeros_like(m2))
-    return GeometricMTF(n.detach().to(x.dtype), mtf.reshape(*mtf.shape[:-1], D, K).to(x.dtype), origin.to(x.dtype))
+    return n, torch.where(lit, modulus / torch.where(lit, n1, torch.ones_like(m2)), torch.zeros_like(m2))
+
+
+# ---------------------------------------------------------------------------- through-focus MTF: one rotor per ray and frequency
+class ThroughFocusMTF(NamedTuple):
+    """What through_focus_mtf returns."""
+    n: torch.Tensor                 # weighted live rays, [B, F, W] less the pooled dimension
+    mtf: torch.Tensor               # modulus of the geometric OTF, [..., Z, D, K]: planes x directions x frequencies
+    shifts: torch.Tensor            # the Z plane positions along +z (float64)
+    centre: torch.Tensor            # the origin every row's phase was measured from, [B, F, W, 2]
+
+
+def _planes(planes):
+    """(first, step, Z) of `planes` as two Python floats and an int."""
+    try:
+        first, step, count = planes
+        first, step = float(first), float(step)
+    except (TypeError, ValueError):
+        raise ValueError("planes must be (first, step, count): two finite floats and an int >= 1") from None
+    if not (math.isfinite(first) and math.isfinite(step)) or isinstance(count, bool) or not isinstance(count, int) or count < 1:
+        raise ValueError("planes must be (first, step, count): two finite floats and an int >= 1")
+    if count > 1 and step == 0.0:
+        raise ValueError("planes: a step of 0 puts every plane at one shift; two or more planes need a step other than 0")
+    return first, step, count
+
+
+def _plane_chunks(first, step, Z):
+    """[(first of the chunk, planes in it)]: the planes in chunks of ops.TFMTF_MAX_Z, chunk q starting at first + (16 q) step
+    formed on the host in float64, where the recurrence restarts."""
+    return [(first + z0 * step, min(ops.TFMTF_MAX_Z, Z - z0)) for z0 in range(0, Z, ops.TFMTF_MAX_Z)]
+
+
+def plane_shifts(planes):
+    """The positions of the planes (first, step, count) as the through-focus MTF takes them: Python floats, plane 16 q + r at
+    (first + (16 q) step) + r step, every operation in float64."""
+    first, step, Z = _planes(planes)
+    return tuple(f0 + r * step for f0, n in _plane_chunks(first, step, Z) for r in range(n))
+
+
+def _sincos_turns(r):
+    """(cos, sin)(2 pi r) for |r| <= 1 / 2 as the device library's sincospi(2 r) forms them: quarter turns taken off exactly, pi
+    multiplies only into |t| <= 1 / 8, so that r = 0, 1 / 4, 1 / 2 give (1, 0), (0, 1), (-1, 0) without a rounding."""
+    k = torch.round(4.0 * r)
+    phi = (2.0 * math.pi) * (r - 0.25 * k)
+    c0, s0, k = torch.cos(phi), torch.sin(phi), torch.remainder(k, 4.0)
+    cos = torch.where(k == 0, c0, torch.where(k == 1, -s0, torch.where(k == 2, -c0, s0)))
+    sin = torch.where(k == 0, s0, torch.where(k == 1, c0, torch.where(k == 2, -s0, -c0)))
+    return cos, sin
+
+
+def _tfmtf_sums_torch(x, y, cx, cy, ray_ok, origin, nu_x, nu_y, first, step, Z):
+    """The definition of otf_sums_through_focus for one chunk of planes in torch ops, in float64, on any device, the recurrence
+    included.  It holds the ray x J tensors the kernels never form."""
+    x, y, cx, cy = (t.to(torch.float64) for t in (x, y, cx, cy))
+    live = (ray_ok != 0) & (1 - cx * cx - cy * cy > 0)                # (NaN > 0 is false)
+    zero = x.new_zeros(())
+    # a dead ray is the ray at 0 along the axis that is not counted: nothing of what it holds reaches a sum or a gradient
+    x, y, cx, cy = (torch.where(live, t, zero) for t in (x, y, cx, cy))
+    cz = torch.sqrt(1 - cx * cx - cy * cy)
+    u, v = cx / cz, cy / cz
+    o = origin.detach()
+    dx, dy = x - o[:, :, None, :, 0], y - o[:, :, None, :, 1]
+    nx, ny = const_tensor(nu_x, torch.float64, x.device), const_tensor(nu_y, torch.float64, x.device)
+    a = nx * dx[..., None] + ny * dy[..., None]             # cycles, [B, F, P, W, J]
+    b = nx * u[..., None] + ny * v[..., None]               # cycles per unit of shift
+    p0 = a + first * b
+    c, s = _sincos_turns(p0 - torch.round(p0))              # (round: to nearest even, rint's; its derivative is 0)
+    q = (step if Z > 1 else 0.0) * b
+    cr, sr = _sincos_turns(q - torch.round(q))
+    keep = live[..., None]
+    out = []
+    for z in range(Z):
+        out.append(torch.stack([torch.where(keep, c, zero).sum(dim=2), torch.where(keep, s, zero).sum(dim=2)], dim=-1))
+        if z + 1 < Z:
+            c, s = c * cr - s * sr, s * cr + c * sr
+    return torch.stack(out, dim=-2)                         # [B, F, W, J, Z, 2]
+
+
+def otf_sums_through_focus(x, y, cx, cy, ray_ok, origin, nu_x, nu_y, planes, fused=None):
+    """The Fourier sums [B, F, W, J, Z, 2] (float64) of a traced fan at Z equally spaced focal planes; the low-level form of
+    through_focus_mtf, which states the definition.  sums[row, j, z] = (C_jz, S_jz) over the live rays, OTF_jz = (C - i S) / n.
+    Differentiable in x, y, cx, cy.  `origin`, nu_x, nu_y as for otf_sums; planes = (first, step, count).  `fused` as for
+    through_focus_mtf.  More than ops.TFMTF_MAX_J vectors or ops.TFMTF_MAX_Z planes go in several calls: vectors in 16s, planes in
+    16s with chunk q starting at first + (16 q) step, formed on the host in float64, where the recurrence restarts -- that is
+    part of the definition (either path), so a plane's bits do not depend on how many planes follow it."""
+    nu_x, nu_y = tuple(float(v) for v in nu_x), tuple(float(v) for v in nu_y)
+    if not nu_x or len(nu_x) != len(nu_y) or not all(math.isfinite(v) for v in nu_x + nu_y):
+        raise ValueError("nu_x and nu_y must hold the same number (at least one) of finite floats")
+    first, step, Z = _planes(planes)
+    use = _uses_kernels(fused, (x, y, cx, cy, ray_ok, origin), 4, "through-focus MTF", "otf_sums_through_focus")
+    x, y, cx, cy, ray_ok = _rays_4d("otf_sums_through_focus", x, y, cx, cy, ray_ok)
+    B, F, _, W = x.shape
+    origin = origin.detach().to(torch.float64).expand(B, F, W, 2)
+    mj = ops.TFMTF_MAX_J
+    cols = []
+    for f0, nz in _plane_chunks(first, step, Z):
+        if use:
+            parts = [ops.TFMTFSumsFunction.apply(x, y, cx, cy, ray_ok, origin, nu_x[j:j + mj], nu_y[j:j + mj], f0, step, nz)
+                     for j in range(0, len(nu_x), mj)]
+        else:
+            parts = [_tfmtf_sums_torch(x, y, cx, cy, ray_ok, origin, nu_x[j:j + mj], nu_y[j:j + mj], f0, step, nz)
+                     for j in range(0, len(nu_x), mj)]
+        cols.append(parts[0] if len(parts) == 1 else torch.cat(parts, dim=3))
+    return cols[0] if len(cols) == 1 else torch.cat(cols, dim=4)
+
+
+def through_focus_mtf(x, y, cx, cy, ray_ok, frequencies, planes, directions=("tangential", "sagittal"), common=("wavelength",),
+                      centre="field", weights=None, fused=None):
+    """The geometric MTF of a traced fan against focus shift: geometric_mtf at Z equally spaced focal planes, from one pass over
+    the rays as they stand.
+
+    Behind the last surface a ray is a straight line: at an image plane shifted by d along +z (the sign of through_focus) it lands
+    at (x + d u, y + d v), u = cx / cz, v = cy / cz, so its phase there is a + d b with a = nu . (r - o) and b = nu . (u, v), and
+    over equally spaced planes exp(2 pi i (a + d_z b)) is a geometric sequence.
+
+    RAYS.  x, y, cx, cy, ray_ok: [B, F, P, W] as RayTracer.trace_rays returns them, broadcastable.  A ray is LIVE iff ray_ok != 0
+    and s = 1 - cx^2 - cy^2 > 0 (through_focus's rule, in float64).  A dead ray is excluded by a select: it adds +0.0 to every sum
+    and receives exactly 0 gradient whatever it holds.
+    PLANES.  planes = (first, step, count): plane z lies at first + z step; at most ops.TFMTF_MAX_Z = 16 planes share one
+    recurrence, chunk q of a longer list starts at first + (16 q) step (formed on the host in float64) and restarts it.
+    FREQUENCY VECTORS, POOLING, WEIGHTS, ORIGIN: geometric_mtf's, word for word; a named centre and n come from the first three
+    of focus_moments' moments (n, sum x, sum y), so the live rule is the one above.
+    DEFINITION.  Per row over the live rays, every operation in float64 from the inputs and nothing contracted, d0 the chunk's
+    first shift and dd the step:
+        cz = sqrt(s),  u = cx / cz,  v = cy / cz,  dx = x - o_x,  dy = y - o_y
+        a  = nu_x dx + nu_y dy  (cycles),   b = nu_x u + nu_y v  (cycles per unit of shift)
+        p0 = a + d0 b,  r0 = p0 - rint(p0),  (c_0, s_0) = sincospi(2 r0)          plane 0 of the chunk
+        q  = dd b,      rq = q - rint(q),    (cr, sr)   = sincospi(2 rq)          the rotor
+        (c_z, s_z) = (c_{z-1} cr - s_{z-1} sr,  s_{z-1} cr + c_{z-1} sr),  z = 1 .. 15
+        C_jz = sum c_z,  S_jz = sum s_z;   OTF = (C - i S) / n,  MTF = sqrt(C^2 + S^2) / n.
+    nu = 0 gives a = b = 0 and the term (1, 0) at every plane exactly: MTF = 1 with no rounding.  Two sincospi per ray and
+    frequency vector instead of one per plane, and no shifted coordinate is ever rounded to float32.
+    GRADIENTS.  For seeds (gC, gS)_jz, Q_jz = gS c_z - gC s_z:  gx = 2 pi sum_j nu_xj sum_z Q_jz,  gu = 2 pi sum_j nu_xj sum_z
+    d_z Q_jz, gy and gv with nu_y; the slopes pass to the cosines by du/dcx = (1 - cy^2) / cz^3, du/dcy = dv/dcx = cx cy / cz^3,
+    dv/dcy = (1 - cx^2) / cz^3.  No gradient to the origin (the modulus does not depend on it), the frequencies, shifts or weights.
+
+    Returns ThroughFocusMTF(n, mtf, shifts, centre): mtf [B, F, W, Z, D, K], or [B, F, Z, D, K] when pooled, in the dtype of x;
+    shifts the Z plane positions (float64, on the rays' device; plane_shifts gives them on the host); n and centre as
+    geometric_mtf's.  `fused`: False -- the definition above, recurrence included, in float64 torch ops on any device; True --
+    the HIP kernels (ops.TFMTFSumsFunction: float32 x, y, cx, cy on one AMD GPU, anything else raises); None -- the kernels
+    where they apply.  The finish is geometric_mtf's.  No host synchronisation.  mtf_best_focus reads the MTF-best focus off it."""
+    pooled = _mtf_pooled(common, centre)
+    nu_x, nu_y, D, K = _mtf_vectors(frequencies, directions)
+    first, step, Z = _planes(planes)
+    tensors = (x, y, cx, cy, ray_ok) + (() if isinstance(centre, str) else (centre,))
+    use = _uses_kernels(fused, tensors, 4, "through-focus MTF", "through_focus_mtf")
+    x, y, cx, cy, ray_ok = _rays_4d("through_focus_mtf", x, y, cx, cy, ray_ok)
+    a = _mtf_weights(weights, x.shape[3])
+    if use:                                                 # what is expanded or strided differently is copied here, once: both nodes
+        (x, y, cx, cy), ray_ok, _, _ = ops._row_rays({"x": x, "y": y, "cx": cx, "cy": cy}, ray_ok, "through-focus MTF")     # then read in place
+    with torch.no_grad():
+        S = focus_moments(x, y, cx, cy, ray_ok, fused=use)[..., :3]
+    origin = _mtf_origin(S, centre, pooled)
+    sums = otf_sums_through_focus(x, y, cx, cy, ray_ok, origin, nu_x, nu_y, (first, step, Z), fused=use)
+    n, mtf = _mtf_finish(sums, S[..., 0], a, pooled)        # mtf [.., J, Z]
+    mtf = mtf.reshape(*mtf.shape[:-2], D, K, Z).movedim(-1, -3)
+    shifts = const_tensor(plane_shifts((first, step, Z)), torch.float64, x.device)
+    return ThroughFocusMTF(n.detach().to(x.dtype), mtf.to(x.dtype), shifts, origin.to(x.dtype))
+
+
+def mtf_best_focus(mtf, shifts):
+    """The MTF-best focus of a through-focus curve: for mtf [..., Z, D, K] (through_focus_mtf's) and the Z plane positions
+    `shifts`, per (..., D, K) the plane of the largest MTF, refined by the parabola through that sample and its two neighbours.
+
+    Returns (shift, mtf_peak, interior), each [..., D, K]: the vertex of the parabola and its value there; `interior` (bool) is
+    False where the maximum sits on the first or the last plane (or Z < 3) -- there `shift` is that plane and `mtf_peak` its
+    sample.  Of equal maxima the first counts.  The shifts must be distinct (through_focus_mtf's are: it refuses a step of 0).
+    Differentiable in mtf, with the arg-max detached.  Plain torch on the tiny result."""
+    if mtf.dim() < 3 or shifts.dim() != 1 or mtf.shape[-3] != shifts.shape[0]:
+        raise ValueError(f"mtf must be [..., Z, D, K] and shifts [Z], got {tuple(mtf.shape)} and {tuple(shifts.shape)}")
+    Z = shifts.shape[0]
+    m = mtf.to(torch.float64)
+    d = shifts.to(device=m.device, dtype=torch.float64)
+    top = m.detach().argmax(dim=-3, keepdim=True)           # the first of equal maxima
+    interior = (top > 0) & (top < Z - 1)
+    mid = top.clamp(1, Z - 2) if Z >= 3 else top
+    at = lambda i: (m.gather(-3, i).squeeze(-3), d[i.squeeze(-3)])          # noqa: E731
+    y1, x1 = at(torch.where(interior, mid, top))
+    if Z < 3:
+        return x1.to(mtf.dtype), y1.to(mtf.dtype), interior.squeeze(-3)
+    (y0, x0), (y2, x2) = at(mid - 1), at(mid + 1)
+    ym, xm = m.gather(-3, mid).squeeze(-3), d[mid.squeeze(-3)]
+    # Newton's form through (x0, y0), (xm, ym), (x2, y2): y = y0 + d01 (x - x0) + a2 (x - x0) (x - xm)
+    d01, d12 = (ym - y0) / (xm - x0), (y2 - ym) / (x2 - xm)
+    a2 = (d12 - d01) / (x2 - x0)
+    # (the first of the largest samples has a smaller one before it and none larger after it: a2 < 0 wherever it is interior)
+    inside = interior.squeeze(-3)
+    a2 = torch.where(inside, a2, -torch.ones_like(a2))
+    xv = 0.5 * (x0 + xm) - d01 / (2.0 * a2)
+    yv = y0 + d01 * (xv - x0) + a2 * (xv - x0) * (xv - xm)
+    return torch.where(inside, xv, x1).to(mtf.dtype), torch.where(inside, yv, y1).to(mtf.dtype), inside
 
 
 def diffraction_limit_mtf(frequencies, wavelength, f_number):

@@ -173,7 +173,7 @@ def timing_ms() -> dict:
 
 def named_timing_ms() -> dict:
     """Mean GPU milliseconds per call, by entry point, of the timed calls outside the trace (tl_focus_moments, tl_focus_seed,
-    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed, tl_zfit_moments, tl_zfit_solve, tl_zfit_seed, tl_mtf_sums, tl_mtf_seed) since enable_timing();
+    tl_enclosed_centroid, tl_enclosed_sums, tl_enclosed_seed, tl_zfit_moments, tl_zfit_solve, tl_zfit_seed, tl_mtf_sums, tl_mtf_seed, tl_tfmtf_sums, tl_tfmtf_seed) since enable_timing();
     synchronises the device."""
     torch.cuda.synchronize()
     return {k: sum(a.elapsed_time(b) for a, b in v) / len(v) for k, v in (_timing_named or {}).items()}
@@ -746,7 +746,60 @@ class MTFSumsFunction(torch.autograd.Function):
         return (*outs, None, None, None, None)
 
 
-ZFIT_ORDERS = (2, 3, 4, 5, 6)      # radial orders the tl_zfit_* kernels are instantiated for
+TFMTF_MAX_J = 16           # frequency vectors per tl_tfmtf_sums / tl_tfmtf_seed call
+TFMTF_MAX_Z = 16           # focal planes per call
+
+
+class TFMTFSumsFunction(torch.autograd.Function):
+    """sums [B, F, W, J, Z, 2] (float64) = (C_jz, S_jz), the Fourier sums of the live rays at the Z focal planes first + z step, of
+    per-ray tensors x, y, cx, cy, ok of ONE shape [B, F, P, W]: tl_tfmtf_sums forward, tl_tfmtf_seed backward (include/tl_trace.h
+    states the definition).  `origin`, nu_x, nu_y as for MTFSumsFunction; first, step: host floats, Z <= TFMTF_MAX_Z planes.  The
+    five ray arrays are brought to one layout exactly as FocusMomentsFunction does, and B is folded into F.  Nothing of size rays x
+    J or rays x Z is stored, and only the gradients that are asked for are computed."""
+
+    @staticmethod
+    def forward(ctx, x, y, cx, cy, ok, origin, nu_x, nu_y, first, step, Z):
+        (x, y, cx, cy), oks, st, s_f = _row_rays({"x": x, "y": y, "cx": cx, "cy": cy}, ok, "through-focus MTF")
+        _require_device(origin, "origin")
+        dev, full = x.device, x.shape
+        B, F, P, W = full
+        J = len(nu_x)
+        if not 1 <= J <= TFMTF_MAX_J or len(nu_y) != J:
+            raise ValueError(f"nu_x and nu_y must hold the same 1 .. {TFMTF_MAX_J} frequencies, got {J} and {len(nu_y)}")
+        if not 1 <= Z <= TFMTF_MAX_Z:
+            raise ValueError(f"a call takes 1 .. {TFMTF_MAX_Z} planes, got {Z}")
+        if origin.dtype != torch.float64 or tuple(origin.shape) != (B, F, W, 2):
+            raise ValueError(f"origin must be a float64 tensor [B, F, W, 2] = {(B, F, W, 2)}, got {origin.dtype} {tuple(origin.shape)}")
+        o64 = origin.detach()
+        if not o64.is_contiguous():
+            o64 = torch.empty((B, F, W, 2), dtype=torch.float64, device=dev).copy_(o64)
+        sums = torch.empty((B, F, W, J, Z, 2), dtype=torch.float64, device=dev)
+        ctx.save_for_backward(x, y, cx, cy, oks, o64)
+        ctx.plan = (st, s_f, (_host_doubles(nu_x), _host_doubles(nu_y), J, float(first), float(step), Z))
+        if P == 0 or sums.numel() == 0:                     # an empty fan: every sum is 0
+            return sums.zero_()
+        ws = _workspace(_lib.lib().tl_tfmtf_workspace_bytes(B * F, P, W, J, Z), dev)
+        _call("tl_tfmtf_sums", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], o64, *ctx.plan[2], sums, ws,
+              ws.numel(), timed="tl_tfmtf_sums")
+        return sums
+
+    @staticmethod
+    def backward(ctx, g_sums):
+        x, y, cx, cy, oks, o64 = ctx.saved_tensors
+        dev, full = x.device, x.shape
+        B, F, P, W = full
+        st, s_f, planes = ctx.plan
+        outs = _ray_grads(ctx, 4, x, st)
+        if all(o is None for o in outs) or x.numel() == 0:
+            return (*outs, None, None, None, None, None, None, None)
+        gs = torch.empty(g_sums.shape, dtype=torch.float64, device=dev).copy_(g_sums)
+        ws = _workspace(_lib.lib().tl_tfmtf_workspace_bytes(B * F, P, W, planes[2], planes[5]), dev)
+        _call("tl_tfmtf_seed", dev, dev.index, B * F, P, W, x, y, cx, cy, oks, s_f, st[2], st[3], o64, *planes, gs, *outs, ws,
+              ws.numel(), timed="tl_tfmtf_seed")
+        return (*outs, None, None, None, None, None, None, None)
+
+
+ZFIT_ORDERS = (2, 3, 4, 5, 6)     # radial orders the tl_zfit_* kernels are instantiated for
 
 
 def zfit_sizes(order):
